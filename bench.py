@@ -18,6 +18,13 @@ Under torch.distributed.run (WORLD_SIZE set) it is one of the ranks.
     --mode weak    (default) --views-per-gpu views per rank, total grows with N
     --mode strong  --views-total views sharded over the ranks (BASELINE configs[3]: 1024 views, --field 512)
 
+A plain run sets up, warms up, times the K steps and prints the headline line (its `roofline` comes from the timed
+steps themselves).  Everything else the line can carry -- the CPU baseline, the side workloads (field512, field_hbm, the
+other scene, the reference's round, ngp_step, first hit), training, the full loop, N > 1's configs[3] round and the
+torch.distributed cross-check of the gathered records -- runs only with --full.
+
+    --dump-outputs DIR   after the timed steps: the last step's gathered records and ranking as DIR/<name>.npy
+
 Prints ONE JSON line on rank 0.  Parity status of every number here: the GPU path is checked
 against this repository's own CPU oracle (tests/), which is NOT pinned to the reference binary
 (instant-ngp is absent from the reference tree) -- stated in the line as "parity".
@@ -109,26 +116,60 @@ def parse_args(argv=None):
     ap.add_argument("--scene", choices=["baseline", "dense"], default="baseline",
                     help="baseline = BASELINE.md section 6 literally: table U(-0.1,0.1), no density bias (the headline); "
                          "dense = table U(-4,4), density bias 3: an opaque object, early termination exercised")
-    ap.add_argument("--full-loop", action="store_true",
-                    help="BASELINE configs[4] at size (minutes): prv_planner configs/TrainInLoop.yaml semantics, 5 objects x 20 rounds (mode 21) + "
-                         "the PSNR curve and stopping criterion (mode 4), end-to-end wall-clock in the full_loop sub-object.  Without it "
-                         "the default run does ONE object x 20 rounds (a few minutes at upstream's training batch) so that the driver's line carries the figure")
-    ap.add_argument("--full-loop-objects", type=int, default=0, help="0 = 1 by default, 5 with --full-loop")
-    ap.add_argument("--no-full-loop", action="store_true")
-    ap.add_argument("--full-loop-small", action="store_true",
-                    help="full_loop on configs/TrainInLoop_small.yaml: the 4096-ray training cap of rounds 1-5, about 1/6.6 of upstream's batch "
-                         "(reported as `reduced`; the default trains at the library default = upstream's 2^18-sample batch)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--reference-round-fixed", action="store_true", help="reference_round: also the round with 128 uniform samples per ray (not the reference's rule)")
-    ap.add_argument("--no-training", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the field512 / baseline-scene / first-hit side measurements")
-    ap.add_argument("--train-steps", type=int, default=300)
-    ap.add_argument("--no-field-hbm", action="store_true", help="skip the field_hbm side workload (a 448 MiB table: the one HBM-bound line of the record)")
-    ap.add_argument("--no-config3", action="store_true", help="N > 1: skip the configs[3] sub-object (1024 views of the 512^3 field, strong scaling)")
-    ap.add_argument("--train-patch", default="", help="full_loop: WxH, training rays drawn as patches of adjacent pixels (yaml train_patch_w / "
-                                                      "train_patch_h; a speed / quality trade: profiles/r05_train_patch_study.txt)")
-    return ap.parse_args(argv)
+    # side measurements: each acts in a --full run only, and giving any of them asks for that run (so that a command line
+    # written when the full run was the default still runs what it ran then)
+    side = ap.add_argument_group("side measurements", "each acts in a --full run only; giving any of them turns --full on")
+    side_actions = []
+
+    def side_opt(*names, **kw):
+        side_actions.append(side.add_argument(*names, **kw))
+
+    side_opt("--full-loop", action="store_true",
+             help="BASELINE configs[4] at size (minutes): prv_planner configs/TrainInLoop.yaml semantics, 5 objects x 20 rounds (mode 21) + "
+                  "the PSNR curve and stopping criterion (mode 4), end-to-end wall-clock in the full_loop sub-object.  Without it "
+                  "a --full run does ONE object x 20 rounds (a few minutes at upstream's training batch) so that its line carries the figure")
+    side_opt("--full-loop-objects", type=int, default=0, help="0 = 1 by default, 5 with --full-loop")
+    side_opt("--no-full-loop", action="store_true")
+    side_opt("--full-loop-small", action="store_true",
+             help="full_loop on configs/TrainInLoop_small.yaml: the 4096-ray training cap of rounds 1-5, about 1/6.6 of upstream's batch "
+                  "(reported as `reduced`; the default trains at the library default = upstream's 2^18-sample batch)")
+    side_opt("--cpu-seconds", type=float, default=12.0)
+    side_opt("--no-cpu-baseline", action="store_true")
+    side_opt("--reference-round-fixed", action="store_true", help="reference_round: also the round with 128 uniform samples per ray (not the reference's rule)")
+    side_opt("--no-training", action="store_true")
+    side_opt("--no-extras", action="store_true", help="skip the field512 / baseline-scene / first-hit side measurements")
+    side_opt("--train-steps", type=int, default=300)
+    side_opt("--no-field-hbm", action="store_true", help="skip the field_hbm side workload (a 448 MiB table: the one HBM-bound line of the record)")
+    side_opt("--no-config3", action="store_true", help="N > 1: skip the configs[3] sub-object (1024 views of the 512^3 field, strong scaling)")
+    side_opt("--train-patch", default="", help="full_loop: WxH, training rays drawn as patches of adjacent pixels (yaml train_patch_w / "
+                                               "train_patch_h; a speed / quality trade: profiles/r05_train_patch_study.txt)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every side measurement and check beyond the headline (the side-measurement options refine it); "
+                         "off: the run does what the headline figure needs and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's records (score, psnr, coverage) and ranking as DIR/<name>.npy (float64 / float32)")
+    unset = object()  # argparse fills in a default only where the namespace has no value yet: what stays `unset` was not given
+    args = ap.parse_args(argv, argparse.Namespace(**{a.dest: unset for a in side_actions}))
+    for a in side_actions:
+        if getattr(args, a.dest) is unset:
+            setattr(args, a.dest, a.default)
+        else:
+            args.full = True
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(directory, records, order):
+    """what the timed path hands its caller after a step: the gathered 16-byte records, field by field, and the ranking
+    (view ids, stored as float64: exact)"""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    arrays = {"records_score": np.asarray(records["score"], np.float64), "records_psnr": np.asarray(records["psnr"], np.float32),
+              "records_coverage": np.asarray(records["coverage"], np.float32), "ranking": np.asarray(order, np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 # ------------------------------------------------------------------ launcher (N > 1, plain invocation)
@@ -732,12 +773,14 @@ def run_rank(args):
     main = Round(env, fkw, n_views, args, comm=comm)
     m = main.measure(args.steps, args.warmup)
     k, elapsed = args.steps, m["elapsed"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m["records"], m["order"])
 
-    # cross-check, untimed: the records the product path gathered == the records torch.distributed gathers
+    # cross-check, untimed (--full): the records the product path gathered == the records torch.distributed gathers
     collective = None
     if use_dist:
         same = None
-        if comm is not None:
+        if comm is not None and args.full:
             other = main.torch_gather_round()
             same = other.tobytes() == m["records"].tobytes()
         collective = {"timed_path": "prv_score_views_sharded on prv_comm (C ABI, " + (comm.transport if comm else "-") + ")" if comm is not None
@@ -760,7 +803,7 @@ def run_rank(args):
     # synthetic 512^3 field sharded 1024/N per GPU (128 at N = 8), one all-gather of the records per round, at the headline's
     # image size.  Timed like the headline (barriers, max over ranks), on the same communicator.
     config3 = None
-    if world > 1 and not args.no_config3 and not (args.mode == "strong" and args.field == "512" and args.views_total == 1024):
+    if args.full and world > 1 and not args.no_config3 and not (args.mode == "strong" and args.field == "512" and args.views_total == 1024):
         import threading
 
         box = {}
@@ -821,7 +864,7 @@ def run_rank(args):
                     config3 = {"error": f"{int(vote['bad'])} rank(s) failed the configs[3] round"}
 
     extras = {}
-    solo_ok = rank == 0 and world == 1 and not args.no_extras  # side measurements only in the N = 1 run
+    solo_ok = args.full and rank == 0 and world == 1 and not args.no_extras  # side measurements only in the N = 1 run
     if solo_ok:
         solo = dict(env, world=1, rank=0, use_dist=False)
         # (1) the HBM-bound configuration (BASELINE configs[3]'s field) timed in the SAME run
@@ -956,7 +999,7 @@ def run_rank(args):
     # the other half of an NBV iteration: in-process training of the field (run.py:185-208), outside the timed
     # region and not part of `value`: a fresh field trained on this rank's reference images
     training = None
-    if rank == 0 and world == 1 and not args.no_training:
+    if args.full and rank == 0 and world == 1 and not args.no_training:
         tcams = ctx.cameras_from_matrices(np.asarray(main.tms)[main.my_ids], main.fov_x, args.width, args.height, main.scale,
                                           main.offset)
         ctx.synthetic_model(5, api.L.FieldDesc(**field_kw(args.field, "dense")), SEED_B)  # an opaque object to learn
@@ -1003,10 +1046,10 @@ def run_rank(args):
         scene_words = ("BASELINE.md section 6 scene: table U(-0.1,0.1), Xavier MLPs, no density bias, analytic occupancy (4 spheres)"
                        if args.scene == "baseline" else "dense scene: table U(-4,4), density bias 3, analytic occupancy (4 spheres)")
         cpu = None
-        if not args.no_cpu_baseline and world == 1:  # reported at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported at N=1 only
             cpu = cpu_baseline(args, fkw, main.tms, main.scale, main.offset, main.fov_x)
         loop = None
-        if world == 1 and not args.no_full_loop and not args.no_extras:
+        if args.full and world == 1 and not args.no_full_loop and not args.no_extras:
             try:
                 loop = full_loop(args)
             except Exception as e:  # the side measurement must never cost the run its line
@@ -1234,7 +1277,7 @@ def dry_run(args, rank, world, np, torch, dist):
         dist.all_gather(all_d, digest)
         assert all(bool((d == digest).all()) for d in all_d), "ranks disagree on the gathered records"
     config3 = None
-    if world > 1 and not args.no_config3:  # the shape of the sub-object the real N > 1 run adds: configs[3]'s 1024 views, strong
+    if args.full and world > 1 and not args.no_config3:  # the shape of the sub-object the real N > 1 run adds (with --full): configs[3]'s 1024 views, strong
         ids3, per3 = planner.shard_views(1024, rank, world, interleaved=True)
         rec3 = np.zeros(len(ids3), api.RECORD_DTYPE)
         rec3["score"] = np.sin(ids3.astype(np.float64) * 12.9898) * 43758.5453 % 1.0
@@ -1259,17 +1302,18 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args, argv))  # before anything touches a GPU
     rc = run_rank(args)
-    # Everything is closed and the line is out.  What a normal interpreter exit adds is the static teardown of torch's and
-    # the HIP / HSA runtime's state in an order this script does not control (round 2 saw about one crash in a thousand
-    # process exits on this pool while another process shared the GPU; the C++ planner, which owns its runtime, now shuts
-    # it down explicitly -- prv_runtime_shutdown -- and returns normally): a finished run's exit code must not depend on it.
+    # Everything is closed and the line is out.  The process leaves through an ordinary interpreter exit, so that every
+    # exit handler runs -- a profiler's, or whatever else the host installed to record what the run loaded and did; an
+    # _exit skips them all, and with them the record that this run executed the library's native code.  The price is the
+    # rare crash profiles/NOTES.md ("prv_planner's exit") traces to the HIP runtime's own exit-time teardown, after the
+    # line is out ("a host that must run its own exit handlers").  PRV_BENCH_EXIT=quick is
+    # PRV_PLANNER_EXIT=quick's counterpart for a host that records nothing at exit and scores runs by exit code: flush,
+    # then _exit.
     sys.stdout.flush()
     sys.stderr.flush()
-    # ... unless a profiler is attached: rocprofv3 writes its files from an exit handler, which _exit would skip
-    profiled = "rocprof" in os.environ.get("LD_PRELOAD", "").lower() or any(k.startswith(("ROCPROF", "ROCP_", "ROCTRACER")) for k in os.environ)
-    if profiled or os.environ.get("PRV_BENCH_EXIT") == "normal":
-        sys.exit(rc)
-    os._exit(rc)
+    if os.environ.get("PRV_BENCH_EXIT") == "quick":
+        os._exit(rc)
+    sys.exit(rc)
 
 
 if __name__ == "__main__":

@@ -17,7 +17,7 @@ python3 scripts/pmc_to_json.py "64<4, 5> baseline" $O/pmc_256_baseline/summary.t
 python3 scripts/pmc_to_json.py "64<4, 5> dense" $O/pmc_256_dense/summary.txt $O/kbench_256_dense.txt "round 6 final: 64 views 800x800 S=128, field 256^3, scene dense" > /dev/null
 python3 scripts/pmc_to_json.py "64<2, 10> baseline" $O/pmc_512_baseline/summary.txt $O/kbench_512_baseline.txt "round 6 final: 64 views 800x800 S=128, field 512^3, scene baseline" > /dev/null
 cp profiles/r06_round_cost.json profiles/r06_pmc_traffic.json $O/
-timeout 900 python3 bench.py > $O/bench.json 2> $O/bench.err; echo "rc=$?" >> $O/bench.err
+timeout 900 python3 bench.py --full > $O/bench.json 2> $O/bench.err; echo "rc=$?" >> $O/bench.err
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --no-cpu-baseline --no-extras --no-training > $O/bench_prof.json 2> $O/bench_prof.err
 f=$(find $O/prof -name "*kernel_stats.csv" | head -1); head -5 "$f"; cp "$f" $O/bench_kernel_stats.csv
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof512 -- python3 bench.py --field 512 --no-cpu-baseline --no-extras --no-training > $O/bench_prof512.json 2> $O/bench_prof512.err

@@ -8,7 +8,7 @@ tail -3 $O/trainbench_trace.txt
 cp $(find $O/prof -name "*kernel_stats.csv" | head -1) $O/kernel_stats_65536rays.csv; rm -rf $O/prof
 head -14 $O/kernel_stats_65536rays.csv | cut -c1-160
 bash scripts/gpu/train_patch_study.sh ${1:-r06a}/patch 1x1:65536 2x1:65536 2x2:65536 4x4:65536
-timeout 900 python3 bench.py > $O/bench_line.json 2> $O/bench_err.txt; echo "bench rc $?"; tail -c 600 $O/bench_err.txt
+timeout 900 python3 bench.py --full > $O/bench_line.json 2> $O/bench_err.txt; echo "bench rc $?"; tail -c 600 $O/bench_err.txt
 python3 - $O/bench_line.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

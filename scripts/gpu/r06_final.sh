@@ -8,4 +8,4 @@ python3 scripts/kbench.py --reps 3 --field hbm --views 16 --tag hbm 2>&1 | grep 
 bash scripts/pmc.sh $O/pmc_hbm 4,5,6 --field hbm --views 16 > $O/pmc_hbm.log 2>&1; cp $O/pmc_hbm/summary.txt $O/pmc_hbm_summary.txt; rm -rf $O/pmc_hbm/p*/
 python3 scripts/pmc_to_json.py "hbm baseline" $O/pmc_hbm_summary.txt $O/kbench_hbm.txt "round 6 final: 16 views 800x800 S=128, field_hbm (L=16 F=2 log2T=24 finest 2048), scene baseline" > /dev/null
 cp profiles/r06_pmc_traffic.json profiles/r06_round_cost.json $O/
-timeout 900 python3 bench.py > $O/bench_final.json 2> $O/bench_final.err; echo "bench rc $?"
+timeout 900 python3 bench.py --full > $O/bench_final.json 2> $O/bench_final.err; echo "bench rc $?"

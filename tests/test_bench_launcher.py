@@ -22,7 +22,7 @@ def run_bench(extra, env_extra):
 @pytest.mark.parametrize("mode,extra,n_views", [("weak", ["--views-per-gpu", "5"], 10),
                                                  ("strong", ["--mode", "strong", "--views-total", "9"], 9)])
 def test_plain_invocation_with_two_gpus_launches_its_own_ranks(mode, extra, n_views):
-    out = run_bench(["--gpus", "2", "--steps", "1", "--warmup", "0"] + extra, {"PRV_BENCH_DRY_RUN": "1"})
+    out = run_bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--full"] + extra, {"PRV_BENCH_DRY_RUN": "1"})
     assert out.returncode == 0, out.stdout + out.stderr
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout  # ONE JSON line, rank 0's
@@ -31,7 +31,7 @@ def test_plain_invocation_with_two_gpus_launches_its_own_ranks(mode, extra, n_vi
     assert two["views_total"] == n_views
     # the single-process run of the same candidate set ends with the same gathered records and ranking
     one_extra = ["--views-per-gpu", "10"] if mode == "weak" else extra
-    one = run_bench(["--gpus", "1", "--steps", "1", "--warmup", "0"] + one_extra, {"PRV_BENCH_DRY_RUN": "1"})
+    one = run_bench(["--gpus", "1", "--steps", "1", "--warmup", "0", "--full"] + one_extra, {"PRV_BENCH_DRY_RUN": "1"})
     assert one.returncode == 0, one.stdout + one.stderr
     ref = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][0])
     assert ref["records_checksum"] == two["records_checksum"] and ref["ranking_head"] == two["ranking_head"]
@@ -60,6 +60,62 @@ def test_launcher_passes_a_failing_rank_on():
 def test_mismatched_world_size_is_refused():
     out = run_bench(["--gpus", "1"], {"WORLD_SIZE": "2", "RANK": "0", "PRV_BENCH_DRY_RUN": "1"})
     assert out.returncode != 0 and "WORLD_SIZE" in (out.stdout + out.stderr)
+
+
+def test_plain_invocation_carries_no_side_measurement():
+    """without --full the N > 1 line has no configs[3] round; the gathered records and ranking are those of the --full run"""
+    out = run_bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--views-per-gpu", "5"], {"PRV_BENCH_DRY_RUN": "1"})
+    assert out.returncode == 0, out.stdout + out.stderr
+    plain = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+    assert plain["config3"] is None
+    full = run_bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--views-per-gpu", "5", "--full"], {"PRV_BENCH_DRY_RUN": "1"})
+    assert full.returncode == 0, full.stdout + full.stderr
+    ref = json.loads([l for l in full.stdout.splitlines() if l.startswith("{")][0])
+    assert ref["config3"] is not None
+    assert ref["records_checksum"] == plain["records_checksum"] and ref["ranking_head"] == plain["ranking_head"]
+
+
+def test_zero_steps_are_refused():
+    out = run_bench(["--gpus", "1", "--steps", "0"], {"PRV_BENCH_DRY_RUN": "1"})
+    assert out.returncode != 0 and "--steps" in out.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's records and ranking as .npy files, byte for byte the records and
+    ranking the line's digests name, and the same arrays from a second run with the same arguments.  A plain run carries
+    no side measurement."""
+    import hashlib
+
+    import numpy as np
+
+    from nerf_prv_amd import api
+
+    base = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--views-per-gpu", "5", "--width", "96", "--height", "80"]
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        out = run_bench(base + ["--dump-outputs", str(d)], {})
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+        found = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(found) == 1, out.stdout
+        lines.append(json.loads(found[0]))
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("records_score", "records_psnr", "records_coverage", "ranking")})
+    line, arrays = lines[0], dumps[0]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True
+    # what the timed window really held: one render launch per step (HIP events between the barriers, not the argument)
+    assert line["roofline"]["launches"] == 3
+    for key in ("cpu_baseline", "field512", "field_hbm", "scene_dense", "reference_round", "ngp_step", "full_loop", "config3"):
+        assert key not in line, key
+    assert line["training"] is None and line["first_hit"] is None
+    assert {a.dtype for a in arrays.values()} <= {np.dtype(np.float32), np.dtype(np.float64)}
+    rec = np.zeros(5, api.RECORD_DTYPE)
+    for field in ("score", "psnr", "coverage"):
+        rec[field] = arrays["records_" + field]
+    assert hashlib.sha256(rec.tobytes()).hexdigest()[:16] == line["records_sha256"]
+    assert hashlib.sha256(arrays["ranking"].astype(np.int32).tobytes()).hexdigest()[:16] == line["ranking_sha256"]
+    for name, a in arrays.items():
+        assert np.array_equal(a, dumps[1][name]), name
 
 
 def test_roofline_peak_constants_are_the_committed_microbenchmarks():

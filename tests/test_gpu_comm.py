@@ -287,7 +287,7 @@ def test_bench_two_ranks_time_the_product_collective_path(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["PRV_BENCH_SHARED_GPU"] = "1"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--views-per-gpu", "3",
-           "--width", "96", "--height", "80", "--no-extras", "--no-training", "--no-cpu-baseline"]
+           "--width", "96", "--height", "80", "--no-extras", "--no-training", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stdout + out.stderr
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -316,7 +316,7 @@ def test_bench_eight_ranks_shard_1024_views_of_the_512_field(tmp_path):
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--mode", "strong", "--views-total", "1024",
-            "--field", "512", "--width", "40", "--height", "32", "--no-extras", "--no-training", "--no-cpu-baseline", "--no-full-loop"]
+            "--field", "512", "--width", "40", "--height", "32", "--no-extras", "--no-training", "--no-cpu-baseline", "--no-full-loop", "--full"]
     out = subprocess.run(base + ["--gpus", "8"], capture_output=True, text=True, env=dict(env, PRV_BENCH_SHARED_GPU="1"), timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     eight = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -334,7 +334,7 @@ def test_bench_eight_ranks_shard_1024_views_of_the_512_field(tmp_path):
     # ... and what the driver's `bench.py --gpus 8` (the WEAK headline) carries beside it: the `config3` sub-object -- the same
     # 1024 views of the 512^3 field, sharded 128 per rank on the same communicator, timed after the headline
     weak = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--views-per-gpu", "2", "--width", "40", "--height", "32",
-            "--no-extras", "--no-training", "--no-cpu-baseline", "--no-full-loop", "--gpus", "8"]
+            "--no-extras", "--no-training", "--no-cpu-baseline", "--no-full-loop", "--full", "--gpus", "8"]
     out = subprocess.run(weak, capture_output=True, text=True, env=dict(env, PRV_BENCH_SHARED_GPU="1"), timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -360,7 +360,7 @@ def test_bench_rccl_communicator_runs_on_the_librccl_the_process_already_has(tmp
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "PRV_RCCL_LIB")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--views-per-gpu", "3", "--width", "96", "--height", "80",
-           "--no-extras", "--no-training", "--no-cpu-baseline", "--no-full-loop"]
+           "--no-extras", "--no-training", "--no-cpu-baseline", "--no-full-loop", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=dict(env, PRV_FORCE_DIST="1", MASTER_PORT=str(free_port())), timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
