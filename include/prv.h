@@ -313,6 +313,42 @@ int prv_splat_points(prv_ctx* ctx, const float* xyz_dev, const uint8_t* rgb_dev,
                      const double offset[3], const prv_camset* cs, const int* view_ids, int n_views, int width,
                      int height, int point_size, int flip180, uint8_t* out_rgba8_dev);
 
+/* ---- mesh extraction ------------------------------------------------------- */
+/* replaces: testbed.compute_and_save_marching_cubes_mesh(path, [res, res, res]) (run.py:59-60, 279-282).
+ * A grid of res[0] x res[1] x res[2] points over [aabb_lo, aabb_hi] (engine frame), x fastest: point i on axis a at
+ * lo[a] + (float)i * step[a], step[a] = (hi[a] - lo[a]) / (float)(res[a] - 1).  sigma = the field's density at each point;
+ * a corner is inside iff sigma > threshold (strict; NaN is outside).  Vertices come in edge-id order (3 * point + axis),
+ * triangles in cell order, counter-clockwise seen from outside (lower sigma); normals = -grad sigma, normalised; colours =
+ * the full field at the vertex seen from outside (direction -normal), quantised as an opaque pixel (prv_quantize_rgba8).
+ * Everything is deterministic: two runs give identical bytes.  A grid without a surface is not an error (0 vertices). */
+typedef struct prv_mesh prv_mesh; /* owns its device buffers; inert (PRV_E_STATE, not a crash) if it outlives its context */
+typedef struct prv_mesh_opts {
+  int32_t res[3];               /* grid points per axis, 2..1024 each, product <= 2^30 */
+  float aabb_lo[3], aabb_hi[3]; /* engine frame, 0 <= lo < hi <= 1; default the unit cube (upstream's render_aabb) */
+  float threshold;              /* sigma iso-level, default 2.5 (instant-ngp's default) */
+  int32_t use_occupancy;        /* default 0 = every point evaluated; 1: sigma = 0 where the occupancy bit is clear */
+  int32_t colors;               /* default 1 */
+} prv_mesh_opts;
+int prv_mesh_default_opts(prv_mesh_opts* o); /* res 256^3, unit cube, threshold 2.5, no occupancy, colours */
+/* sigma_dev: res[0]*res[1]*res[2] float32 (device), x fastest */
+int prv_density_grid(prv_ctx* ctx, int model_slot, const prv_mesh_opts* o, float* sigma_dev);
+int prv_marching_cubes(prv_ctx* ctx, int model_slot, const prv_mesh_opts* o, prv_mesh** out);
+/* marching cubes on a caller's sigma grid (device, layout of prv_density_grid); no colours (rgb reads as 0) */
+int prv_marching_cubes_grid(prv_ctx* ctx, const float* sigma_dev, const prv_mesh_opts* o, prv_mesh** out);
+int prv_mesh_counts(const prv_mesh* m, uint64_t* n_vertices, uint64_t* n_triangles);
+/* host arrays: xyz / normals n_vertices*3 floats, rgb n_vertices*3 bytes, tri n_triangles*3 vertex ids; any may be NULL */
+int prv_mesh_get(const prv_mesh* m, float* xyz, float* normals, uint8_t* rgb, uint32_t* tri);
+/* Files are written in the dataset (transforms.json) frame: engine position e -> q = (e2, e0, e1) -> (q - offset) / scale,
+ * the inverse of nerf_to_ngp (cameras) and prv_splat_points; normals get the same axis cycle (an even permutation: the
+ * winding is kept).  By extension: .ply = binary_little_endian 1.0, float x y z nx ny nz, uchar red green blue, faces
+ * `list uchar int vertex_indices`; .obj = ASCII `v x y z r g b` (colours in [0,1]), `vn`, `f a//a b//b c//c` (1-based).
+ * Any other extension: PRV_E_INVALID.  offset NULL = (0, 0, 0). */
+int prv_mesh_save(const prv_mesh* m, const char* path, double scale, const double offset[3]);
+/* the writer alone, on host arrays (no GPU; rgb / normals may be NULL: written as 0); errors via prv_last_error(NULL) */
+int prv_mesh_write_file(const char* path, uint64_t n_vertices, const float* xyz, const float* normals, const uint8_t* rgb,
+                        uint64_t n_triangles, const uint32_t* tri, double scale, const double offset[3]);
+void prv_mesh_destroy(prv_mesh* m);
+
 /* ---- several GPUs: view sharding + one all-gather ----------------------------- */
 /* replaces: nothing in the reference -- its loops over the candidates are serial (main.cpp:2045-2094, 2105-2158;
  * run.py:293) and it has no multi-GPU path.  One process per GPU (RANK / WORLD_SIZE / LOCAL_RANK as torchrun exports
@@ -453,6 +489,8 @@ int prv_debug_render_clock(prv_ctx* ctx, uint64_t* shader_cycles, uint64_t* ref_
 /* rays of view i at (w,h): o,d = n*3, t = n*2 (AABB entry/exit; exit<=entry => miss) */
 int prv_debug_raygen(prv_ctx* ctx, const prv_camset* cs, int view, int width, int height,
                      int spp_index, float* o, float* d, float* t);
+/* milliseconds of the last mesh extraction's stages: density grid, classify + scans, emit, colours (HIP events) */
+int prv_debug_mesh_stages(prv_ctx* ctx, float ms[4]);
 /* 32 fp16 features per position (bit patterns) */
 int prv_debug_encode(prv_ctx* ctx, int model_slot, const float* pos, int n, uint16_t* feat);
 /* per point: out[0]=sigma, out[1..3]=rgb, out[4..19]=density MLP outputs, out[20..35]=rgb MLP

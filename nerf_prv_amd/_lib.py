@@ -66,6 +66,11 @@ class ModelLayout(C.Structure):
                 ("kernel_slots", C.c_int32), ("n_dense_levels", C.c_int32)]
 
 
+class MeshOpts(C.Structure):
+    _fields_ = [("res", C.c_int32 * 3), ("aabb_lo", C.c_float * 3), ("aabb_hi", C.c_float * 3), ("threshold", C.c_float),
+                ("use_occupancy", C.c_int32), ("colors", C.c_int32)]
+
+
 class ScoreRecord(C.Structure):
     _fields_ = [("score", C.c_double), ("psnr", C.c_float), ("coverage", C.c_float)]
 
@@ -133,6 +138,15 @@ SIGNATURES = {
     "prv_first_hit": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, C.c_float, _vp]),
     "prv_precept": (_i, [_vp, _i, _vp, _i, _vp, _P(Rs2Intrinsics), C.c_float, _vp]),
     "prv_quantize_rgba8": (_i, [_vp, _vp, C.c_size_t, _vp, _vp]),
+    "prv_mesh_default_opts": (_i, [_P(MeshOpts)]),
+    "prv_density_grid": (_i, [_vp, _i, _P(MeshOpts), _vp]),
+    "prv_marching_cubes": (_i, [_vp, _i, _P(MeshOpts), _P(_vp)]),
+    "prv_marching_cubes_grid": (_i, [_vp, _vp, _P(MeshOpts), _P(_vp)]),
+    "prv_mesh_counts": (_i, [_vp, _P(C.c_uint64), _P(C.c_uint64)]),
+    "prv_mesh_get": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "prv_mesh_save": (_i, [_vp, C.c_char_p, C.c_double, _vp]),
+    "prv_mesh_write_file": (_i, [C.c_char_p, C.c_uint64, _vp, _vp, _vp, C.c_uint64, _vp, C.c_double, _vp]),
+    "prv_mesh_destroy": (None, [_vp]),
     "prv_score_ensemble_images": (_i, [_vp, _i, _vp, _i, _i, C.c_size_t, _vp]),
     "prv_score_psnr_images": (_i, [_vp, _vp, _vp, _i, C.c_size_t, _vp, _vp]),
     "prv_evaluate_images": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
@@ -167,6 +181,7 @@ SIGNATURES = {
     "prv_debug_model_layout": (_i, [_vp, _i, C.POINTER(ModelLayout)]),
     "prv_debug_render_clock": (_i, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "prv_debug_raygen": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "prv_debug_mesh_stages": (_i, [_vp, _P(C.c_float)]),
     "prv_debug_encode": (_i, [_vp, _i, _vp, _i, _vp]),
     "prv_debug_field": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp]),
 }

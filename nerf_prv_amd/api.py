@@ -398,6 +398,124 @@ class Context:
         return out, occ
 
 
+    # -- mesh extraction (include/prv.h, mesh section)
+    def density_grid(self, slot, res, aabb=None, use_occupancy=False):
+        """the field's sigma at every grid point -> torch float32 tensor (rz, ry, rx) on the context's device; point i on axis
+        a at lo[a] + float32(i) * step[a] (engine frame, aabb = (lo, hi), default the unit cube)"""
+        o = mesh_opts(res, aabb, use_occupancy=use_occupancy)
+        out = self.torch.empty((o.res[2], o.res[1], o.res[0]), dtype=self.torch.float32, device=self.device)
+        self._chk(self.lib.prv_density_grid(self.handle, slot, C.byref(o), _ptr(out)))
+        return out
+
+    def marching_cubes(self, slot, res=256, aabb=None, threshold=2.5, use_occupancy=False, colors=True):
+        """marching cubes on the field's density grid -> Mesh (engine frame)"""
+        o = mesh_opts(res, aabb, threshold, use_occupancy, colors)
+        h = C.c_void_p()
+        self._chk(self.lib.prv_marching_cubes(self.handle, slot, C.byref(o), C.byref(h)))
+        return Mesh(self, h)
+
+    def marching_cubes_grid(self, sigma, aabb=None, threshold=2.5):
+        """marching cubes on a caller's sigma grid (torch float32 (rz, ry, rx) on the device) -> Mesh without colours"""
+        if sigma.dim() != 3 or sigma.dtype != self.torch.float32 or not sigma.is_cuda:
+            raise ValueError("sigma must be a float32 (rz, ry, rx) device tensor")
+        sigma = sigma.contiguous()
+        rz, ry, rx = sigma.shape
+        o = mesh_opts((rx, ry, rz), aabb, threshold, colors=False)
+        h = C.c_void_p()
+        self._chk(self.lib.prv_marching_cubes_grid(self.handle, _ptr(sigma), C.byref(o), C.byref(h)))
+        return Mesh(self, h)
+
+    def mesh_stage_ms(self):
+        """milliseconds of the last extraction's stages: density grid, classify + scans, emit, colours"""
+        ms = (C.c_float * 4)()
+        self._chk(self.lib.prv_debug_mesh_stages(self.handle, ms))
+        return dict(grid=ms[0], classify_scan=ms[1], emit=ms[2], colors=ms[3])
+
+
+def mesh_opts(res=256, aabb=None, threshold=2.5, use_occupancy=False, colors=True):
+    """prv_mesh_opts: res = N or (rx, ry, rz); aabb = (lo[3], hi[3]) in the engine frame (None: the unit cube)"""
+    lib = L.load()
+    o = L.MeshOpts()
+    lib.prv_mesh_default_opts(C.byref(o))
+    r = [int(res)] * 3 if np.isscalar(res) else [int(x) for x in res]
+    if len(r) != 3:
+        raise ValueError("res must be an int or three ints (x, y, z)")
+    for a in range(3):
+        o.res[a] = r[a]
+    if aabb is not None:
+        lo, hi = aabb
+        for a in range(3):
+            o.aabb_lo[a], o.aabb_hi[a] = float(lo[a]), float(hi[a])
+    o.threshold = float(threshold)
+    o.use_occupancy = int(bool(use_occupancy))
+    o.colors = int(bool(colors))
+    return o
+
+
+def _mesh_file_error(rc):
+    raise PrvError(rc, (L.load().prv_last_error(None) or b"").decode())
+
+
+def write_mesh(path, vertices, triangles, normals=None, colors=None, scale=1.0, offset=(0.0, 0.0, 0.0)):
+    """prv_mesh_write_file: engine-frame host arrays -> .ply / .obj in the dataset frame (no GPU involved)"""
+    lib = L.load()
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+    n = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    c = None if colors is None else np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+    off = np.ascontiguousarray(offset, np.float64).reshape(3)
+    rc = lib.prv_mesh_write_file(str(path).encode(), v.shape[0], _ptr(v), _ptr(n), _ptr(c), t.shape[0], _ptr(t), float(scale),
+                                 _ptr(off))
+    if rc != 0:
+        _mesh_file_error(rc)
+
+
+class Mesh:
+    """a marching-cubes mesh (engine frame) owned by the library; the arrays are host copies taken at construction:
+    vertices / normals (n, 3) float32, colors (n, 3) uint8, triangles (m, 3) uint32 (counter-clockwise seen from outside)"""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.handle = ctx, handle
+        nv, nt = C.c_uint64(), C.c_uint64()
+        ctx._chk(ctx.lib.prv_mesh_counts(handle, C.byref(nv), C.byref(nt)))
+        self.vertices = np.zeros((nv.value, 3), np.float32)
+        self.normals = np.zeros((nv.value, 3), np.float32)
+        self.colors = np.zeros((nv.value, 3), np.uint8)
+        self.triangles = np.zeros((nt.value, 3), np.uint32)
+        ctx._chk(ctx.lib.prv_mesh_get(handle, _ptr(self.vertices), _ptr(self.normals), _ptr(self.colors), _ptr(self.triangles)))
+
+    def counts(self):
+        nv, nt = C.c_uint64(), C.c_uint64()
+        rc = self.ctx.lib.prv_mesh_counts(self.handle, C.byref(nv), C.byref(nt))
+        if rc != 0:
+            _mesh_file_error(rc)
+        return nv.value, nt.value
+
+    def save(self, path, scale=0.33, offset=(0.5, 0.5, 0.5)):
+        """.ply / .obj in the dataset frame: (cycle(e) - offset) / scale (prv_mesh_save)"""
+        off = np.ascontiguousarray(offset, np.float64).reshape(3)
+        rc = self.ctx.lib.prv_mesh_save(self.handle, str(path).encode(), float(scale), _ptr(off))
+        if rc != 0:
+            _mesh_file_error(rc)
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.prv_mesh_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def engine_to_dataset(xyz, scale, offset):
+    """engine-frame positions -> the dataset (transforms.json) frame: q = (e2, e0, e1), (q - offset) / scale"""
+    e = np.asarray(xyz, np.float64).reshape(-1, 3)
+    return (e[:, [2, 0, 1]] - np.asarray(offset, np.float64)) / float(scale)
+
+
 class Comm:
     """the ranks of one job as the C ABI sees them (include/prv.h, "several GPUs"): RCCL on device buffers, or the
     host-staged socket transport for ranks that share a GPU"""
@@ -748,6 +866,30 @@ class Testbed:
         bg = self.ctx.torch.tensor(self.background_color, dtype=img.dtype, device=img.device)
         img = img + (1.0 - img[..., 3:4]) * bg  # composite over the background colour
         return img.cpu().numpy()
+
+    # ASSUMED: pyngp's signatures (upstream testbed.compute_marching_cubes_mesh / compute_and_save_marching_cubes_mesh are
+    # not in the reference tree; run.py:282 passes (filename, [res, res, res])).  resolution = (x, y, z) grid points; aabb =
+    # (lo, hi) in the engine frame (None: the unit cube, upstream's render_aabb); thresh = the sigma iso-level.
+    def compute_marching_cubes_mesh(self, resolution=(256, 256, 256), aabb=None, thresh=2.5):
+        """-> {"V": positions, "N": normals, "C": colours in [0, 1], "F": triangles}, in the dataset frame"""
+        if not self._have_model:
+            raise PrvError(L.PRV_E_STATE, "no model loaded")
+        m = self.ctx.marching_cubes(self._slot, resolution, aabb, thresh)
+        try:
+            return {"V": engine_to_dataset(m.vertices, self.scale, self.offset).astype(np.float32),
+                    "N": m.normals[:, [2, 0, 1]].copy(), "C": m.colors.astype(np.float32) / 255.0,
+                    "F": m.triangles.astype(np.int32)}
+        finally:
+            m.close()
+
+    def compute_and_save_marching_cubes_mesh(self, filename, resolution=(256, 256, 256), aabb=None, thresh=2.5):  # run.py:282
+        if not self._have_model:
+            raise PrvError(L.PRV_E_STATE, "no model loaded")
+        m = self.ctx.marching_cubes(self._slot, resolution, aabb, thresh)
+        try:
+            m.save(filename, self.scale, self.offset)
+        finally:
+            m.close()
 
     def _ground_truth(self, i, width, height):
         """render_ground_truth (run.py:241-244): the dataset image of view i, linear premultiplied RGBA"""

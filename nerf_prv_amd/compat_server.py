@@ -12,6 +12,8 @@ out of the script and answers it in-process through the C ABI:
                                                     (run.py:284-309)
   --test_transforms J --save_metrics M           -> evaluate against reference images, write M
                                                     (run.py:213-277)
+  --save_mesh P [--marching_cubes_res N]         -> marching-cubes mesh of the field at N^3 (default 256), written to
+                                                    P (.ply / .obj) in the dataset frame (run.py:59-60, 279-282)
   --train --n_steps N --scene J                  -> a fresh field trained N steps in process on J's views
                                                     (run.py:109, 185-208; `train_desc=` names the field),
                                                     unless a `load_model(scene, ctx) -> slot` callable supplies
@@ -122,6 +124,12 @@ class CompatServer:
     def serve_one(self, args):
         self._args = args
         slot = self.load_model(args.get("scene"), self.ctx)  # load_training_data + training, or supplied weights
+        # run.py's order: evaluation (213-277), the mesh (279-282), screenshots (284-309); a request with screenshots is
+        # not evaluated here (as before the mesh was honoured)
+        if "test_transforms" in args and "screenshot_transforms" not in args:
+            self._evaluate(slot, args)
+        if args.get("save_mesh"):
+            self._save_mesh(slot, args)
         if "screenshot_transforms" in args:
             from PIL import Image
 
@@ -139,17 +147,36 @@ class CompatServer:
                     name += ".png"
                 Image.fromarray(img, "RGBA").save(os.path.join(args["screenshot_dir"], name))
             cams.close()
-        elif "test_transforms" in args:
-            from . import planner
 
-            # the dataset's own cameras: fl_x/fl_y, principal point, lens (run.py:238-242)
-            cams = self.ctx.cameras_from_dataset_json(args["test_transforms"])
-            w, h = cams.size
-            gt = self.reference_images(args["test_transforms"])
-            opts = api.engine_render_opts(w, h, self.samples_per_ray, 1, 1e-4, background=(0.0, 0.0, 0.0, 1.0))  # run.py:226-235
-            psnr, ssim = self.ctx.evaluate(slot, cams, None, opts, gt)
-            planner.write_metrics(args["save_metrics"], psnr, ssim)
-            cams.close()
+    def _evaluate(self, slot, args):
+        from . import planner
+
+        # the dataset's own cameras: fl_x/fl_y, principal point, lens (run.py:238-242)
+        cams = self.ctx.cameras_from_dataset_json(args["test_transforms"])
+        w, h = cams.size
+        gt = self.reference_images(args["test_transforms"])
+        opts = api.engine_render_opts(w, h, self.samples_per_ray, 1, 1e-4, background=(0.0, 0.0, 0.0, 1.0))  # run.py:226-235
+        psnr, ssim = self.ctx.evaluate(slot, cams, None, opts, gt)
+        planner.write_metrics(args["save_metrics"], psnr, ssim)
+        cams.close()
+
+    def _save_mesh(self, slot, args):
+        """run.py:279-282: compute_and_save_marching_cubes_mesh(save_mesh, [res, res, res]) in the dataset frame of the
+        request's scene json (its scale / offset; upstream's defaults 0.33 / 0.5 without one)"""
+        res = int(args.get("marching_cubes_res") or 256)  # run.py:280
+        scale, offset = 0.33, [0.5, 0.5, 0.5]
+        if args.get("scene") and os.path.exists(args["scene"]):
+            with open(args["scene"]) as f:
+                meta = json.load(f)
+            scale = float(meta.get("scale", scale))
+            offset = [float(x) for x in meta.get("offset", offset)]
+        mesh = self.ctx.marching_cubes(slot, res)
+        try:
+            d = os.path.dirname(os.path.abspath(args["save_mesh"]))
+            os.makedirs(d, exist_ok=True)
+            mesh.save(args["save_mesh"], scale, offset)
+        finally:
+            mesh.close()
 
     def poll_once(self):
         """one iteration of the train_server.py loop; returns True when a request was served"""

@@ -754,6 +754,34 @@ __device__ __forceinline__ MlpOut2 mlp_forward2(const half8* __restrict__ wl, in
   return out;
 }
 
+// The density MLP alone (the first 8 of the 24 fragment sets), for both column groups: mlp_forward2's first two layers with
+// the same fragments (`frags64`), the same operation order and the same packing, so the density outputs -- and
+// sigma = fast_exp(out0 + bias), read from register 0 of group A / register 8 of group B -- are bit-identical to it.
+__device__ __forceinline__ void mlp_density2(const half8* __restrict__ wl, int lane, const half8 fA[2], const half8 fB[2], f32x16& densA,
+                                             f32x16& densB) {
+  const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  half8 hA[4], hB[4];
+  { // density layer 1: 32 -> 64
+    const half8 w0 = wl[0 * 64 + lane], w1 = wl[1 * 64 + lane], w2 = wl[2 * 64 + lane], w3 = wl[3 * 64 + lane];
+    f32x16 a0 = mfma(w0, fA[0], zero), a1 = mfma(w2, fA[0], zero);
+    a0 = mfma(w1, fA[1], a0);
+    a1 = mfma(w3, fA[1], a1);
+    f32x16 b0 = mfma(w0, fB[0], zero), b1 = mfma(w2, fB[0], zero);
+    b0 = mfma(w1, fB[1], b0);
+    b1 = mfma(w3, fB[1], b1);
+    hA[0] = pack8<true>(a0, 0); hA[1] = pack8<true>(a0, 8); hA[2] = pack8<true>(a1, 0); hA[3] = pack8<true>(a1, 8);
+    hB[0] = pack8<true>(b0, 0); hB[1] = pack8<true>(b0, 8); hB[2] = pack8<true>(b1, 0); hB[3] = pack8<true>(b1, 8);
+  }
+  densA = zero; // density layer 2: 64 -> 16 (+ copies in the padding rows)
+  densB = zero;
+#pragma unroll
+  for (int s = 0; s < 4; s++) {
+    const half8 w = wl[(4 + s) * 64 + lane];
+    densA = mfma(w, hA[s], densA);
+    densB = mfma(w, hB[s], densB);
+  }
+}
+
 // SH fragment of lane half h: coefficients [8h, 8h+8) as fp16
 __device__ __forceinline__ half8 sh_fragment(int h, float dx, float dy, float dz) {
   float s[16];

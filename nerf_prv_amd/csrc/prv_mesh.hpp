@@ -1,0 +1,39 @@
+// prv_mesh.hpp -- mesh extraction (prv_mesh.hip): the density grid of a field and marching cubes on a sigma grid.
+#pragma once
+#include "prv_device.hpp"
+
+namespace prv {
+
+// A grid of res[0] x res[1] x res[2] points, x fastest; point i on axis a sits at lo[a] + (float)i * step[a]
+// (one multiply, one add: -ffp-contract=off), step[a] = (hi[a] - lo[a]) / (float)(res[a] - 1), computed by the host.
+struct MeshGrid {
+  int res[3];
+  float lo[3], step[3];
+};
+
+inline size_t mesh_points(const MeshGrid& g) { return (size_t)g.res[0] * g.res[1] * g.res[2]; }
+// waves of 64 points the per-point passes run: whole blocks of 4 (the per-point buffers hold mesh_waves * 64 bytes)
+inline size_t mesh_waves(const MeshGrid& g) { return (mesh_points(g) + 255) / 256 * 4; }
+// uint64 elements of scratch the scan of n elements needs (launch_mesh_scan)
+size_t mesh_scan_scratch(size_t n);
+
+// sigma[point] = fast_exp(density MLP output 0 + bias) of the field at every grid point; use_occ: 0 where the point's
+// occupancy bit is clear.  brick: one wave = a 4x4x4 brick of points, else 64 consecutive points of a row (the default:
+// measured faster, scripts/meshbench.py).
+hipError_t launch_mesh_density(const FieldDev& fd, const MeshGrid& g, int use_occ, int brick, float* sigma, hipStream_t s);
+// per point: crossing flags of its +x/+y/+z edge (bits 0..2) and the case of the cell it is the low corner of; per wave of
+// 64 points: vertices (crossing edges) and triangles.  flags / cases: mesh_waves * 64 bytes (the tail is written as 0).
+hipError_t launch_mesh_classify(const float* sigma, const MeshGrid& g, float thr, uint8_t* flags, uint8_t* cases, uint64_t* wave_v,
+                                uint64_t* wave_t, hipStream_t s);
+// exclusive scan of n uint64 in place; the grand total to *total (device); scratch: mesh_scan_scratch(n) elements
+hipError_t launch_mesh_scan(uint64_t* a, size_t n, uint64_t* scratch, uint64_t* total, hipStream_t s);
+// vertices in edge-id order (3 * point + axis): position and normal (-grad sigma)
+hipError_t launch_mesh_vertices(const float* sigma, const MeshGrid& g, float thr, const uint8_t* flags, const uint64_t* wave_v,
+                                float* xyz, float* nrm, hipStream_t s);
+// triangles in cell order, each cell's in table order, as vertex ids
+hipError_t launch_mesh_triangles(const MeshGrid& g, const uint8_t* flags, const uint8_t* cases, const uint64_t* wave_v,
+                                 const uint64_t* wave_t, uint32_t* tri, hipStream_t s);
+// the full field at each vertex seen from outside (dir = -normal), quantised as an opaque pixel
+hipError_t launch_mesh_colors(const FieldDev& fd, const float* xyz, const float* nrm, uint64_t nv, uint8_t* rgb, hipStream_t s);
+
+} // namespace prv
