@@ -88,16 +88,16 @@ struct prv_ctx {
   void* pin = nullptr;                         // pinned host staging of the per-call camera upload (no pageable copy, no stream sync)
   size_t pin_cap = 0;
   hipEvent_t pin_ev = nullptr; // recorded after the upload: the staging is rewritten only once that copy has run
-  int blocks_per_cu = -1; // persistent render blocks per CU (PRV_BLOCKS_PER_CU); -1 = by table and image size, see render_views
-  int cell_cache = -1;    // render_queue64 per-lane corner cache (PRV_CELL_CACHE=0/1; -1 = by stepping rule and image size, see render_views)
+  int blocks_per_cu = -1; // persistent render blocks per CU (PRV_BLOCKS_PER_CU); -1 = by table and image size, see render_blocks
+  int cell_cache = -1;    // render_queue64 per-lane corner cache (PRV_CELL_CACHE=0/1; -1 = by stepping rule and image size, see render_policy)
   std::vector<struct prv_trainer*> trainers; // live trainers of this context (detached by prv_destroy)
   std::vector<struct prv_comm*> comms;       // live communicators of this context (detached by prv_destroy)
   std::vector<struct prv_mesh*> meshes;      // live meshes of this context (detached by prv_destroy)
   float mesh_ms[4] = {0, 0, 0, 0};           // stages of the last mesh extraction (prv_mesh_api.inc: prv_debug_mesh_stages)
   int queue_segments = 8; // ray-queue segments = XCDs (PRV_QUEUE_SEGMENTS: 1 = single shared head)
   int spatial_regions = 1; // a wave's records go to the region of its first live ray's octant (PRV_SPATIAL_REGIONS=0: block id % regions, rounds 1-5)
-  int pool_on = -1;       // render_queue64 block-level tail pool (PRV_POOL=0/1; -1 = by table and image size, see render_views)
-  int merge_max = -1;     // render_queue64 tail merge threshold (PRV_MERGE_MAX; 0 = off; -1 = by table size, see render_views)
+  int pool_on = -1;       // render_queue64 block-level tail pool (PRV_POOL=0/1; -1 = by table and image size, see render_policy)
+  int merge_max = -1;     // render_queue64 tail merge threshold (PRV_MERGE_MAX; 0 = off; -1 = by table size, see render_policy)
   size_t stage_budget = (size_t)4 << 30; // staging bytes for multi-sample renders (spp x batch x image)
   size_t queue_budget = (size_t)8 << 30; // ray-queue bytes per batch of views (288 GB of HBM): one batch for 64 views at 800x800 and for the
                                          // reference's whole candidate set under the engine's rule (540 x 80x45 x 16 spp x 208 B = 6.5 GB:
@@ -535,6 +535,16 @@ CamDev cam_at(const prv_camset* cs, int i, int w, int h) {
   return r;
 }
 
+// cams[i] = camera view_ids[i] of the set (camera i when view_ids is null) at w x h
+int gather_cams(prv_ctx* c, const prv_camset* cs, const int* view_ids, int n_views, int w, int h, CamDev* cams) {
+  for (int i = 0; i < n_views; i++) {
+    const int v = view_ids ? view_ids[i] : i;
+    if (v < 0 || v >= (int)cs->cams.size()) return fail(c, PRV_E_INVALID, "view id %d out of range", v);
+    cams[i] = cam_at(cs, v, w, h);
+  }
+  return PRV_OK;
+}
+
 // The pixel rectangle that contains every ray of a pinhole view that can meet the occupied cells' box (grown like the march
 // pass's own rejection test): a ray through pixel p meets a convex box only if p lies in the box's projection, which lies
 // in the bounding rectangle of its eight projected corners -- provided all eight are in front of the camera.  The march
@@ -585,18 +595,148 @@ void set_cull_rect(CamDev& cam, const OccBox& m, int W, int H) {
   cam.cull[3] = (int)std::max<long>(0, std::min<long>(H, y1));
 }
 
-void set_cull_rect(CamDev& cam, const Model& m, int W, int H) {
+OccBox box_of(const Model& m) {
   OccBox b;
   for (int a = 0; a < 3; a++) {
     b.occ_lo[a] = m.occ_lo[a];
     b.occ_hi[a] = m.occ_hi[a];
   }
-  set_cull_rect(cam, b, W, H);
+  return b;
+}
+
+// the union of the members' boxes (an empty grid adds nothing; all empty: an empty box)
+OccBox union_box(const prv_ctx* c, const int* slots, int E) {
+  OccBox u{{1e30f, 1e30f, 1e30f}, {-1e30f, -1e30f, -1e30f}};
+  bool any = false;
+  for (int e = 0; e < E; e++) {
+    const OccBox b = box_of(c->models[slots[e]]);
+    if (!(b.occ_hi[0] > b.occ_lo[0])) continue;
+    any = true;
+    for (int a = 0; a < 3; a++) {
+      u.occ_lo[a] = std::min(u.occ_lo[a], b.occ_lo[a]);
+      u.occ_hi[a] = std::max(u.occ_hi[a], b.occ_hi[a]);
+    }
+  }
+  return any ? u : OccBox{};
+}
+
+// The cameras of a render call, uploaded per call (tiny): built with their cull rectangles against `box` in pinned memory
+// and sent with one asynchronous copy to c->view_ids = {cams[n_views], ids[n_views] = 0, 1, ...}.  The staging is rewritten
+// only once the previous upload has run (pin_ev).
+struct Upload {
+  const CamDev* cams; // the pinned host copy
+  const CamDev* cams_dev;
+  const int* ids_dev;
+};
+int upload_views(prv_ctx* c, const prv_camset* cs, const int* view_ids, int n_views, int W, int H, const OccBox& box, Upload& up) {
+  const size_t up_bytes = (size_t)n_views * (sizeof(CamDev) + sizeof(int));
+  if (c->pin_cap < up_bytes) {
+    if (c->pin_ev) HIPCHK(c, hipEventSynchronize(c->pin_ev));
+    if (c->pin) (void)hipHostFree(c->pin);
+    c->pin = nullptr;
+    c->pin_cap = 0;
+    HIPCHK(c, hipHostMalloc(&c->pin, std::max<size_t>(up_bytes, 8192), hipHostMallocDefault));
+    c->pin_cap = std::max<size_t>(up_bytes, 8192);
+  }
+  if (!c->pin_ev) HIPCHK(c, hipEventCreateWithFlags(&c->pin_ev, hipEventDisableTiming));
+  else HIPCHK(c, hipEventSynchronize(c->pin_ev));
+  CamDev* cams = (CamDev*)c->pin;
+  int* ids = (int*)((char*)c->pin + (size_t)n_views * sizeof(CamDev));
+  int rc;
+  if ((rc = gather_cams(c, cs, view_ids, n_views, W, H, cams)) != PRV_OK) return rc;
+  for (int i = 0; i < n_views; i++) {
+    set_cull_rect(cams[i], box, W, H);
+    ids[i] = i;
+  }
+  if ((rc = ensure(c, c->view_ids, up_bytes)) != PRV_OK) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->view_ids.p, c->pin, up_bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(c->pin_ev, c->stream));
+  up.cams = cams;
+  up.cams_dev = (const CamDev*)c->view_ids.p;
+  up.ids_dev = (const int*)((char*)c->view_ids.p + (size_t)n_views * sizeof(CamDev));
+  return PRV_OK;
 }
 
 constexpr int kSubRegions = 8, kMaxSegments = 8 * kSubRegions; // queue regions (<= 8: one per XCD) x their sub-regions
 constexpr size_t kStatOffset = (size_t)kMaxSegments * 128;  // counters buffer: heads (64 B apart), then counts (64 B apart), then the statistics
 constexpr size_t kCountersBytes = kStatOffset + 72 * 8; // {evaluated, wave rounds, clock sums and stamps}, then 8 live-sample shards a cache line apart
+
+// The geometry of a march launch and of its queue.  A 256-thread block is a Morton-ordered tile of (256 / spp) pixels x spp
+// sub-samples on adjacent lanes when spp is a power of two <= 64 (x gets the extra bit), else a tile of 256 pixels with the
+// sub-samples on grid.z.  The queue is n_seg regions: a march block appends to one region, so a region holds at most
+// ceil(blocks / n_seg) * 256 records (+ 64: a wave moves to the next region when its own is full, region_reserve).
+// Spatial regions: every octant's region is cut into kSubRegions sub-regions with a counter each (a march block appends to
+// sub-region `linear block id % kSubRegions` of its octant's region): the waves running at any one time are neighbours in
+// the image, i.e. in ONE octant, and one returning-atomic word serves ~90 of them per microsecond.
+struct MarchLayout {
+  int spp, n_sub, n_seg;
+  int spp_inner_log2 = 0, tile_w_log2, tile_h_log2;
+  uint32_t tiles_x, tiles_y;
+  MarchLayout(const prv_ctx* c, int W, int H, int spp_) : spp(spp_) {
+    n_sub = c->spatial_regions ? kSubRegions : 1;
+    n_seg = c->queue_segments * n_sub;
+    if (spp > 1 && spp <= 64 && (spp & (spp - 1)) == 0)
+      while ((1 << spp_inner_log2) < spp) spp_inner_log2++;
+    const int pix_log2 = 8 - spp_inner_log2;
+    tile_w_log2 = (pix_log2 + 1) / 2;
+    tile_h_log2 = pix_log2 / 2;
+    tiles_x = (uint32_t)((W + (1 << tile_w_log2) - 1) >> tile_w_log2);
+    tiles_y = (uint32_t)((H + (1 << tile_h_log2) - 1) >> tile_h_log2);
+  }
+  size_t blocks(size_t n_views) const { return (size_t)tiles_x * tiles_y * n_views * (size_t)(spp_inner_log2 > 0 ? 1 : spp); }
+  size_t seg_cap(size_t n_views) const { return ((blocks(n_views) + n_seg - 1) / n_seg) * 256 + 64; }
+};
+
+// the fields MarchParams and MarchMultiParams share (same names), for views [v0, v0 + n_views) of the upload
+template <class PT>
+void march_common(PT& mp, const prv_ctx* c, const MarchLayout& L, const prv_render_opts* o, const Upload& up, size_t v0,
+                  size_t n_views, unsigned long long* stat) {
+  memset(&mp, 0, sizeof(mp));
+  mp.cams = up.cams_dev;
+  mp.view_ids = up.ids_dev + v0;
+  mp.W = o->width;
+  mp.H = o->height;
+  mp.spp_inner_log2 = L.spp_inner_log2;
+  mp.tile_w_log2 = L.tile_w_log2;
+  mp.tile_h_log2 = L.tile_h_log2;
+  mp.tiles_x = L.tiles_x;
+  mp.tiles_y = L.tiles_y;
+  mp.stat = stat;
+  mp.n_seg = L.n_seg;
+  mp.n_sub = L.n_sub;
+  mp.seg_cap = (uint32_t)L.seg_cap(n_views);
+  mp.spatial_regions = c->spatial_regions;
+  mp.last_pass = o->spp == 1; // staged sub-samples are written raw; scaling / bytes happen in the reduce
+  memcpy(mp.bg, o->background, sizeof(mp.bg));
+}
+
+// Persistent render blocks per CU.  More resident waves hide more gather latency but also put more random requests in
+// flight and draw more power: measured per workload (64-slot kernel, profiles/archive/r02_bm_blocks_per_cu.txt) -- the
+// cache-resident table at large images is flat from 3 up (3 waves per SIMD is what its registers allow), small images
+// (incoherent gathers: the reference's 80x45 candidates, 320x320) are 6 % faster with 2, and the HBM-bound 512^3 table
+// is 10 % faster with ONE wave per SIMD: fewer requests in flight, a better L2 hit rate.
+int render_blocks(const prv_ctx* c, const Model& m, size_t npix) {
+  int bpc = c->blocks_per_cu;
+  if (bpc <= 0) bpc = m.table_halfs * 2 > ((size_t)32 << 20) ? 1 : npix < ((size_t)1 << 17) ? 2 : 4;
+  return c->n_cu * bpc;
+}
+
+// one launch, bracketed by a start / stop event pair on `events` while a profiling window is open
+template <class Launch>
+int timed(prv_ctx* c, std::vector<hipEvent_t>& events, Launch launch) {
+  if (c->profiling) {
+    hipEvent_t a, b;
+    HIPCHK(c, take_event(c, &a));
+    HIPCHK(c, take_event(c, &b));
+    events.push_back(a);
+    events.push_back(b);
+    HIPCHK(c, hipEventRecord(a, c->stream));
+  }
+  const int rc = launch();
+  if (rc != PRV_OK) return rc;
+  if (c->profiling) HIPCHK(c, hipEventRecord(events.back(), c->stream));
+  return PRV_OK;
+}
 
 
 // which render_queue64 instance and relocation policy a launch gets (results are identical either way)
@@ -624,13 +764,37 @@ void render_policy(prv_ctx* c, const Model& m, size_t npix, bool ngp, RenderPara
   rp.pool_on = (c->pool_on >= 0 ? c->pool_on != 0 : (coherent || cached)) && rp.merge_max > 0;
 }
 
+// the render launch over one queue the march filled (q: its records, counts and images; queue_head: its heads)
+RenderParams render_params(prv_ctx* c, const Model& m, const prv_render_opts* o, const MarchLayout& L, uint32_t seg_cap,
+                           const MarchMember& q, uint32_t* queue_head, unsigned long long* stat) {
+  RenderParams rp;
+  memset(&rp, 0, sizeof(rp));
+  rp.field = m.dev;
+  rp.queue = q.queue;
+  rp.queue_ext = q.queue_ext;
+  rp.step_mode = o->step_mode;
+  rp.queue_count = q.queue_count;
+  rp.queue_head = queue_head;
+  rp.n_segments = L.n_seg;
+  rp.n_sub = L.n_sub;
+  rp.seg_cap = seg_cap;
+  rp.stat_evaluated = stat;
+  rp.out_f32 = q.out_f32;
+  rp.out_u8 = q.out_u8;
+  rp.min_T = o->min_transmittance;
+  rp.last_pass = o->spp == 1;
+  memcpy(rp.bg, o->background, sizeof(rp.bg));
+  render_policy(c, m, (size_t)o->width * o->height, o->step_mode == PRV_STEP_NGP, rp);
+  return rp;
+}
+
 // The render of one batch of views into out_f32 (+ optional out_u8).  Views are dealt to
 // the queue in batches so the queue stays within queue_budget bytes.
 int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views,
                  const prv_render_opts* o, float* out_f32, uint8_t* out_u8, bool zero_stats, bool private_output = false) {
   if (o->spp != 1 || out_u8) private_output = false; // sub-sample staging and byte images are written in full
   const Model& m = c->models[slot];
-  const int W = o->width, H = o->height;
+  const int W = o->width, H = o->height, spp = o->spp;
   const size_t npix = (size_t)W * H;
   int rc;
   // counters: 8 region heads (one 64-byte line each) | 8 region counts (same) | stats {evaluated, wave rounds} | dev histogram
@@ -642,38 +806,12 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
     if (zero_stats) HIPCHK(c, hipMemsetAsync(stat, 0, kCountersBytes - kStatOffset, c->stream));
     return PRV_OK;
   }
-
-  // cameras at this resolution, uploaded per call (tiny): built in pinned memory and sent with one asynchronous copy
-  const size_t up_bytes = (size_t)n_views * (sizeof(CamDev) + sizeof(int));
-  if (c->pin_cap < up_bytes) {
-    if (c->pin_ev) HIPCHK(c, hipEventSynchronize(c->pin_ev));
-    if (c->pin) (void)hipHostFree(c->pin);
-    c->pin = nullptr;
-    c->pin_cap = 0;
-    HIPCHK(c, hipHostMalloc(&c->pin, std::max<size_t>(up_bytes, 8192), hipHostMallocDefault));
-    c->pin_cap = std::max<size_t>(up_bytes, 8192);
-  }
-  if (!c->pin_ev) HIPCHK(c, hipEventCreateWithFlags(&c->pin_ev, hipEventDisableTiming));
-  else HIPCHK(c, hipEventSynchronize(c->pin_ev));
-  CamDev* cams = (CamDev*)c->pin;
-  int* ids = (int*)((char*)c->pin + (size_t)n_views * sizeof(CamDev));
-  for (int i = 0; i < n_views; i++) {
-    const int v = view_ids ? view_ids[i] : i;
-    if (v < 0 || v >= (int)cs->cams.size()) return fail(c, PRV_E_INVALID, "view id %d out of range", v);
-    cams[i] = cam_at(cs, v, W, H);
-    set_cull_rect(cams[i], m, W, H);
-    ids[i] = i;
-  }
-  if ((rc = ensure(c, c->view_ids, up_bytes)) != PRV_OK) return rc;
-  CamDev* cams_dev = (CamDev*)c->view_ids.p;
-  int* ids_dev = (int*)((char*)c->view_ids.p + (size_t)n_views * sizeof(CamDev));
-  HIPCHK(c, hipMemcpyAsync(c->view_ids.p, c->pin, up_bytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipEventRecord(c->pin_ev, c->stream));
+  Upload up;
+  if ((rc = upload_views(c, cs, view_ids, n_views, W, H, box_of(m), up)) != PRV_OK) return rc;
 
   // all spp sub-samples of a batch of views go through ONE march + ONE render launch: sub-sample k of
   // view v is image (k*nb + v) of a staging buffer, reduced over k in order afterwards (spp = 1 renders
   // straight into the output).  Batches keep queue and staging within their budgets.
-  const int spp = o->spp;
   const bool ngp = o->step_mode == PRV_STEP_NGP;
   const size_t slot_bytes = kRecordBytes + (ngp ? kExtBytes : 0); // NGP: every queue slot has its mask-extension slot
   size_t batch = std::max<size_t>(1, c->queue_budget / (npix * slot_bytes * (size_t)spp));
@@ -681,34 +819,14 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
   if (spp > 1) batch = std::min<size_t>(batch, std::max<size_t>(1, c->stage_budget / (npix * 16 * (size_t)spp)));
   if (batch * npix * (size_t)spp >= (1ull << 32)) batch = ((1ull << 32) - 1) / (npix * (size_t)spp); // 32-bit pixel ids
   if (batch == 0) return fail(c, PRV_E_INVALID, "image x spp too large");
-  // the queue is n_seg regions: a march block appends to region (linear block id % n_seg), so a region holds at most
-  // ceil(blocks / n_seg) * 256 records -- the same total as one flat queue plus less than one block per region
-  // spatial regions: every octant's region is cut into kSubRegions sub-regions with a counter each (a march block appends to
-  // sub-region `linear block id % kSubRegions` of its octant's region): the waves running at any one time are neighbours in
-  // the image, i.e. in ONE octant, and one returning-atomic word serves ~90 of them per microsecond
-  const int n_sub = c->spatial_regions ? kSubRegions : 1;
-  const int n_seg = c->queue_segments * n_sub;
-  auto march_blocks = [&](int nb) {
-    const int inner = (spp > 1 && spp <= 64 && (spp & (spp - 1)) == 0) ? spp : 1;
-    int pl = 8;
-    for (int v = inner; v > 1; v >>= 1) pl--;
-    const size_t tw = (size_t)1 << ((pl + 1) / 2), th = (size_t)1 << (pl / 2);
-    return ((W + tw - 1) / tw) * ((H + th - 1) / th) * (size_t)nb * (size_t)(inner > 1 ? 1 : spp);
-  };
-  const size_t seg_cap_max = ((march_blocks((int)batch) + n_seg - 1) / n_seg) * 256 + 64; // (+ 64: a wave moves to the next region when its own is full, region_reserve)
-  if (seg_cap_max * (size_t)n_seg >= (1ull << 32)) return fail(c, PRV_E_INVALID, "image x spp too large");
-  if ((rc = ensure(c, c->queue, seg_cap_max * (size_t)n_seg * kRecordBytes)) != PRV_OK) return rc;
-  if (ngp && (rc = ensure(c, c->queue_ext, seg_cap_max * (size_t)n_seg * kExtBytes)) != PRV_OK) return rc;
+  const MarchLayout L(c, W, H, spp);
+  const size_t seg_cap_max = L.seg_cap(batch);
+  if (seg_cap_max * (size_t)L.n_seg >= (1ull << 32)) return fail(c, PRV_E_INVALID, "image x spp too large");
+  if ((rc = ensure(c, c->queue, seg_cap_max * (size_t)L.n_seg * kRecordBytes)) != PRV_OK) return rc;
+  if (ngp && (rc = ensure(c, c->queue_ext, seg_cap_max * (size_t)L.n_seg * kExtBytes)) != PRV_OK) return rc;
   if (spp > 1 && (rc = ensure(c, c->stage, batch * npix * (size_t)spp * 16)) != PRV_OK) return rc;
 
-  // Persistent render blocks per CU.  More resident waves hide more gather latency but also put more random requests in
-  // flight and draw more power: measured per workload (64-slot kernel, profiles/archive/r02_bm_blocks_per_cu.txt) -- the
-  // cache-resident table at large images is flat from 3 up (3 waves per SIMD is what its registers allow), small images
-  // (incoherent gathers: the reference's 80x45 candidates, 320x320) are 6 % faster with 2, and the HBM-bound 512^3 table
-  // is 10 % faster with ONE wave per SIMD: fewer requests in flight, a better L2 hit rate.
-  int bpc = c->blocks_per_cu;
-  if (bpc <= 0) bpc = m.table_halfs * 2 > ((size_t)32 << 20) ? 1 : npix < ((size_t)1 << 17) ? 2 : 4;
-  const int n_blocks = c->n_cu * bpc;
+  const int n_blocks = render_blocks(c, m, npix);
   for (size_t b0 = 0; b0 < (size_t)n_views; b0 += batch) {
     const int nb = (int)std::min(batch, (size_t)n_views - b0);
     float* dst_f32 = out_f32 + b0 * npix * 4;
@@ -716,38 +834,15 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
     // one fill per batch: heads and counts, and with them the statistics when this call starts a new window
     HIPCHK(c, hipMemsetAsync(c->counters.p, 0, b0 == 0 && zero_stats ? kCountersBytes : kStatOffset, c->stream));
     MarchParams mp;
-    memset(&mp, 0, sizeof(mp));
+    march_common(mp, c, L, o, up, b0, (size_t)nb, stat);
     mp.field = m.dev;
-    mp.cams = cams_dev;
-    mp.view_ids = ids_dev + b0;
-    mp.W = W;
-    mp.H = H;
     mp.S = o->samples_per_ray;
-    mp.spp_k = 0;
-    // 256 threads = (256 / spp) pixels x spp sub-samples when spp is a power of two <= 64
-    int inner = 0;
-    if (spp > 1 && spp <= 64 && (spp & (spp - 1)) == 0)
-      while ((1 << inner) < spp) inner++;
-    const int pix_log2 = 8 - inner; // pixels per block, Morton-ordered: x gets the extra bit
-    mp.spp_inner_log2 = inner;
-    mp.tile_w_log2 = (pix_log2 + 1) / 2;
-    mp.tile_h_log2 = pix_log2 / 2;
-    mp.tiles_x = (uint32_t)((W + (1 << mp.tile_w_log2) - 1) >> mp.tile_w_log2);
-    mp.tiles_y = (uint32_t)((H + (1 << mp.tile_h_log2) - 1) >> mp.tile_h_log2);
     mp.step_mode = o->step_mode;
     mp.queue = c->queue.p;
     mp.queue_ext = (uint4*)c->queue_ext.p;
-    mp.stat = stat;
     mp.queue_count = q_count;
-    mp.n_seg = n_seg;
-    mp.n_sub = n_sub;
-    mp.seg_cap = (uint32_t)(((march_blocks(nb) + n_seg - 1) / n_seg) * 256 + 64);
-    mp.spatial_regions = c->spatial_regions;
     mp.out_f32 = spp > 1 ? (float*)c->stage.p : dst_f32;
     mp.out_u8 = spp > 1 ? nullptr : dst_u8;
-    mp.inv_spp = 1.0f;
-    mp.last_pass = spp == 1; // staged sub-samples are written raw; scaling / bytes happen in the reduce
-    memcpy(mp.bg, o->background, sizeof(mp.bg));
     // A caller that consumes the image through the views' cull rectangles (prv_score_views, method 5: the image is a private
     // temporary of the round) gets only the tiles inside them launched and nothing written outside: most of an 800x800
     // view of the bench scene is dead, and 16 B per dead pixel were a 0.4 ms stream of zeros per 64-view step.
@@ -755,7 +850,7 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
       const uint64_t tw = 1ull << mp.tile_w_log2, th = 1ull << mp.tile_h_log2;
       uint64_t live_max = 0;
       for (int i = 0; i < nb; i++) {
-        const CamDev& cv = cams[b0 + i];
+        const CamDev& cv = up.cams[b0 + i];
         uint64_t w = mp.tiles_x, h = mp.tiles_y;
         if (cv.cull[2] > 0) {
           const uint64_t x0 = (uint64_t)cv.cull[0] / tw, y0 = (uint64_t)cv.cull[1] / th;
@@ -769,46 +864,9 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
       mp.live_grid = 1;
       mp.live_tiles_max = (uint32_t)live_max;
     }
-    if (c->profiling) {
-      hipEvent_t a, b;
-      HIPCHK(c, take_event(c, &a));
-      HIPCHK(c, take_event(c, &b));
-      c->ev_march.push_back(a);
-      c->ev_march.push_back(b);
-      HIPCHK(c, hipEventRecord(a, c->stream));
-    }
-    HIPCHK(c, launch_march(mp, nb, spp, c->stream));
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->ev_march.back(), c->stream));
-    RenderParams rp;
-    memset(&rp, 0, sizeof(rp));
-    rp.field = m.dev;
-    rp.queue = c->queue.p;
-    rp.queue_ext = (const uint4*)c->queue_ext.p;
-    rp.step_mode = o->step_mode;
-    rp.queue_count = q_count;
-    rp.queue_head = q_head;
-    rp.n_segments = n_seg;
-    rp.n_sub = n_sub;
-    rp.seg_cap = mp.seg_cap;
-    rp.stat_evaluated = stat;
-    rp.out_f32 = mp.out_f32;
-    rp.out_u8 = mp.out_u8;
-    rp.min_T = o->min_transmittance;
-    rp.inv_spp = 1.0f;
-    rp.spp_k = 0;
-    rp.last_pass = mp.last_pass;
-    render_policy(c, m, npix, ngp, rp);
-    memcpy(rp.bg, o->background, sizeof(rp.bg));
-    if (c->profiling) {
-      hipEvent_t a, b;
-      HIPCHK(c, take_event(c, &a));
-      HIPCHK(c, take_event(c, &b));
-      c->ev_render.push_back(a);
-      c->ev_render.push_back(b);
-      HIPCHK(c, hipEventRecord(a, c->stream));
-    }
-    HIPCHK(c, launch_render(rp, n_blocks, c->stream));
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->ev_render.back(), c->stream));
+    if ((rc = timed(c, c->ev_march, [&] { HIPCHK(c, launch_march(mp, nb, spp, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
+    const RenderParams rp = render_params(c, m, o, L, mp.seg_cap, {mp.queue, mp.queue_ext, mp.queue_count, mp.out_f32, mp.out_u8}, q_head, stat);
+    if ((rc = timed(c, c->ev_render, [&] { HIPCHK(c, launch_render(rp, n_blocks, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
     if (spp > 1) HIPCHK(c, launch_spp_reduce((const float*)c->stage.p, (size_t)nb * npix, spp, o->background, dst_f32, dst_u8, c->stream));
   }
   return PRV_OK;
@@ -842,60 +900,34 @@ int render_ensemble_ngp(prv_ctx* c, const int* slots, int E, const prv_camset* c
   if ((size_t)n_views * npix * (size_t)spp >= (1ull << 32)) return PRV_OK;
   if ((size_t)n_views * npix * (size_t)spp * slot_bytes > c->queue_budget) return PRV_OK; // per member, as render_views batches
   if (spp > 1 && (size_t)n_views * npix * (size_t)spp * 16 > c->stage_budget) return PRV_OK;
+  const MarchLayout L(c, W, H, spp);
+  const size_t seg_cap = L.seg_cap((size_t)n_views);
+  if (seg_cap * (size_t)L.n_seg >= (1ull << 32)) return PRV_OK;
   int rc;
   if ((rc = ensure(c, c->counters, kCountersBytes)) != PRV_OK) return rc;
   if ((rc = ensure(c, c->counters_multi, (size_t)E * kStatOffset)) != PRV_OK) return rc;
   unsigned long long* stat = (unsigned long long*)((char*)c->counters.p + kStatOffset);
+  const size_t R = (size_t)m0.desc.occ_res, n_fine = R * R * R, Rc = R / 4, n_coarse = Rc * Rc * Rc;
+  if ((rc = ensure(c, c->occ_multi, n_fine + n_coarse + 64)) != PRV_OK) return rc;
+  const size_t q_stride = seg_cap * (size_t)L.n_seg * kRecordBytes, x_stride = seg_cap * (size_t)L.n_seg * kExtBytes,
+               s_stride = spp > 1 ? (size_t)n_views * npix * (size_t)spp * 16 : 0;
+  { // E queues, E extension buffers, E staging images at once: only where the device has the room (else member by member,
+    // whose buffers are a fifth of these)
+    const size_t grow = (q_stride * (size_t)E > c->queue.bytes ? q_stride * (size_t)E - c->queue.bytes : 0) +
+                        (x_stride * (size_t)E > c->queue_ext.bytes ? x_stride * (size_t)E - c->queue_ext.bytes : 0) +
+                        (s_stride * (size_t)E > c->stage.bytes ? s_stride * (size_t)E - c->stage.bytes : 0);
+    size_t free_b = 0, total_b = 0;
+    // (the context's parked trainer buffers count as free: ensure() releases them before an allocation fails)
+    if (grow && (hipMemGetInfo(&free_b, &total_b) != hipSuccess || grow + ((size_t)2 << 30) > free_b + c->idle_bytes)) return PRV_OK;
+  }
 
   // the members' union box: clip range and cull rectangles (conservative for every member)
-  OccBox box;
-  for (int a = 0; a < 3; a++) {
-    box.occ_lo[a] = 1e30f;
-    box.occ_hi[a] = -1e30f;
-  }
-  bool any = false;
-  for (int e = 0; e < E; e++) {
-    const Model& m = c->models[slots[e]];
-    if (!(m.occ_hi[0] > m.occ_lo[0])) continue; // an empty grid adds nothing
-    any = true;
-    for (int a = 0; a < 3; a++) {
-      box.occ_lo[a] = std::min(box.occ_lo[a], m.occ_lo[a]);
-      box.occ_hi[a] = std::max(box.occ_hi[a], m.occ_hi[a]);
-    }
-  }
-  if (!any)
-    for (int a = 0; a < 3; a++) box.occ_lo[a] = box.occ_hi[a] = 0.f;
-
-  const size_t up_bytes = (size_t)n_views * (sizeof(CamDev) + sizeof(int));
-  if (c->pin_cap < up_bytes) {
-    if (c->pin_ev) HIPCHK(c, hipEventSynchronize(c->pin_ev));
-    if (c->pin) (void)hipHostFree(c->pin);
-    c->pin = nullptr;
-    c->pin_cap = 0;
-    HIPCHK(c, hipHostMalloc(&c->pin, std::max<size_t>(up_bytes, 8192), hipHostMallocDefault));
-    c->pin_cap = std::max<size_t>(up_bytes, 8192);
-  }
-  if (!c->pin_ev) HIPCHK(c, hipEventCreateWithFlags(&c->pin_ev, hipEventDisableTiming));
-  else HIPCHK(c, hipEventSynchronize(c->pin_ev));
-  CamDev* cams = (CamDev*)c->pin;
-  int* ids = (int*)((char*)c->pin + (size_t)n_views * sizeof(CamDev));
-  for (int i = 0; i < n_views; i++) {
-    const int v = view_ids ? view_ids[i] : i;
-    if (v < 0 || v >= (int)cs->cams.size()) return fail(c, PRV_E_INVALID, "view id %d out of range", v);
-    cams[i] = cam_at(cs, v, W, H);
-    set_cull_rect(cams[i], box, W, H);
-    ids[i] = i;
-  }
-  if ((rc = ensure(c, c->view_ids, up_bytes)) != PRV_OK) return rc;
-  CamDev* cams_dev = (CamDev*)c->view_ids.p;
-  int* ids_dev = (int*)((char*)c->view_ids.p + (size_t)n_views * sizeof(CamDev));
-  HIPCHK(c, hipMemcpyAsync(c->view_ids.p, c->pin, up_bytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipEventRecord(c->pin_ev, c->stream));
+  const OccBox box = union_box(c, slots, E);
+  Upload up;
+  if ((rc = upload_views(c, cs, view_ids, n_views, W, H, box, up)) != PRV_OK) return rc;
 
   // the members' occupancy, interleaved: byte c = bit c of every member's bitfield (fine grid, then the dilated coarse one)
-  const size_t R = (size_t)m0.desc.occ_res, n_fine = R * R * R, Rc = R / 4, n_coarse = Rc * Rc * Rc;
   const bool have_coarse = m0.dev.occ_coarse != nullptr;
-  if ((rc = ensure(c, c->occ_multi, n_fine + n_coarse + 64)) != PRV_OK) return rc;
   {
     OccInterleaveParams ip{};
     ip.n_members = E;
@@ -911,31 +943,6 @@ int render_ensemble_ngp(prv_ctx* c, const int* slots, int E, const prv_camset* c
     }
   }
 
-  // spatial regions: every octant's region is cut into kSubRegions sub-regions with a counter each (a march block appends to
-  // sub-region `linear block id % kSubRegions` of its octant's region): the waves running at any one time are neighbours in
-  // the image, i.e. in ONE octant, and one returning-atomic word serves ~90 of them per microsecond
-  const int n_sub = c->spatial_regions ? kSubRegions : 1;
-  const int n_seg = c->queue_segments * n_sub;
-  int inner = 0;
-  if (spp > 1 && spp <= 64 && (spp & (spp - 1)) == 0)
-    while ((1 << inner) < spp) inner++;
-  const int pix_log2 = 8 - inner;
-  const int tile_w_log2 = (pix_log2 + 1) / 2, tile_h_log2 = pix_log2 / 2;
-  const uint32_t tiles_x = (uint32_t)((W + (1 << tile_w_log2) - 1) >> tile_w_log2), tiles_y = (uint32_t)((H + (1 << tile_h_log2) - 1) >> tile_h_log2);
-  const size_t blocks = (size_t)tiles_x * tiles_y * (size_t)n_views * (size_t)(inner > 0 ? 1 : spp);
-  const size_t seg_cap = ((blocks + n_seg - 1) / n_seg) * 256 + 64;
-  if (seg_cap * (size_t)n_seg >= (1ull << 32)) return PRV_OK;
-  const size_t q_stride = seg_cap * (size_t)n_seg * kRecordBytes, x_stride = seg_cap * (size_t)n_seg * kExtBytes,
-               s_stride = spp > 1 ? (size_t)n_views * npix * (size_t)spp * 16 : 0;
-  { // E queues, E extension buffers, E staging images at once: only where the device has the room (else member by member,
-    // whose buffers are a fifth of these)
-    const size_t grow = (q_stride * (size_t)E > c->queue.bytes ? q_stride * (size_t)E - c->queue.bytes : 0) +
-                        (x_stride * (size_t)E > c->queue_ext.bytes ? x_stride * (size_t)E - c->queue_ext.bytes : 0) +
-                        (s_stride * (size_t)E > c->stage.bytes ? s_stride * (size_t)E - c->stage.bytes : 0);
-    size_t free_b = 0, total_b = 0;
-    // (the context's parked trainer buffers count as free: ensure() releases them before an allocation fails)
-    if (grow && (hipMemGetInfo(&free_b, &total_b) != hipSuccess || grow + ((size_t)2 << 30) > free_b + c->idle_bytes)) return PRV_OK;
-  }
   if ((rc = ensure(c, c->queue, q_stride * (size_t)E)) != PRV_OK) return rc;
   if ((rc = ensure(c, c->queue_ext, x_stride * (size_t)E)) != PRV_OK) return rc;
   if (spp > 1 && (rc = ensure(c, c->stage, s_stride * (size_t)E)) != PRV_OK) return rc;
@@ -943,7 +950,7 @@ int render_ensemble_ngp(prv_ctx* c, const int* slots, int E, const prv_camset* c
   HIPCHK(c, hipMemsetAsync(c->counters_multi.p, 0, (size_t)E * kStatOffset, c->stream));
 
   MarchMultiParams mp;
-  memset(&mp, 0, sizeof(mp));
+  march_common(mp, c, L, o, up, 0, (size_t)n_views, stat);
   mp.occ_bytes = (const uint8_t*)c->occ_multi.p;
   mp.occ_coarse_bytes = have_coarse ? (const uint8_t*)c->occ_multi.p + n_fine : nullptr;
   mp.occ_res = (int)R;
@@ -951,24 +958,6 @@ int render_ensemble_ngp(prv_ctx* c, const int* slots, int E, const prv_camset* c
     mp.occ_lo[a] = box.occ_lo[a];
     mp.occ_hi[a] = box.occ_hi[a];
   }
-  mp.cams = cams_dev;
-  mp.view_ids = ids_dev;
-  mp.W = W;
-  mp.H = H;
-  mp.spp_k = 0;
-  mp.tiles_x = tiles_x;
-  mp.tiles_y = tiles_y;
-  mp.tile_w_log2 = tile_w_log2;
-  mp.tile_h_log2 = tile_h_log2;
-  mp.spp_inner_log2 = inner;
-  mp.stat = stat;
-  mp.n_seg = n_seg;
-  mp.n_sub = n_sub;
-  mp.seg_cap = (uint32_t)seg_cap;
-  mp.spatial_regions = c->spatial_regions;
-  mp.inv_spp = 1.0f;
-  mp.last_pass = spp == 1;
-  memcpy(mp.bg, o->background, sizeof(mp.bg));
   mp.n_members = E;
   for (int e = 0; e < E; e++) {
     MarchMember& mm = mp.mem[e];
@@ -979,51 +968,14 @@ int render_ensemble_ngp(prv_ctx* c, const int* slots, int E, const prv_camset* c
     mm.out_f32 = spp > 1 ? (float*)((char*)c->stage.p + s_stride * (size_t)e) : scratch_f32;
     mm.out_u8 = spp > 1 ? nullptr : (uint32_t*)out_u8[e];
   }
-  if (c->profiling) {
-    hipEvent_t a, b;
-    HIPCHK(c, take_event(c, &a));
-    HIPCHK(c, take_event(c, &b));
-    c->ev_march.push_back(a);
-    c->ev_march.push_back(b);
-    HIPCHK(c, hipEventRecord(a, c->stream));
-  }
-  HIPCHK(c, launch_march_multi(mp, n_views, spp, c->stream));
-  if (c->profiling) HIPCHK(c, hipEventRecord(c->ev_march.back(), c->stream));
+  if ((rc = timed(c, c->ev_march, [&] { HIPCHK(c, launch_march_multi(mp, n_views, spp, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
 
   for (int e = 0; e < E; e++) {
     const Model& m = c->models[slots[e]];
-    int bpc = c->blocks_per_cu;
-    if (bpc <= 0) bpc = m.table_halfs * 2 > ((size_t)32 << 20) ? 1 : npix < ((size_t)1 << 17) ? 2 : 4;
-    RenderParams rp;
-    memset(&rp, 0, sizeof(rp));
-    rp.field = m.dev;
-    rp.queue = mp.mem[e].queue;
-    rp.queue_ext = mp.mem[e].queue_ext;
-    rp.step_mode = o->step_mode;
-    rp.queue_count = mp.mem[e].queue_count;
-    rp.queue_head = (uint32_t*)((char*)c->counters_multi.p + (size_t)e * kStatOffset);
-    rp.n_segments = n_seg;
-    rp.n_sub = n_sub;
-    rp.seg_cap = mp.seg_cap;
-    rp.stat_evaluated = stat;
-    rp.out_f32 = mp.mem[e].out_f32;
-    rp.out_u8 = mp.mem[e].out_u8;
-    rp.min_T = o->min_transmittance;
-    rp.inv_spp = 1.0f;
-    rp.spp_k = 0;
-    rp.last_pass = mp.last_pass;
-    render_policy(c, m, npix, true, rp);
-    memcpy(rp.bg, o->background, sizeof(rp.bg));
-    if (c->profiling) {
-      hipEvent_t a, b;
-      HIPCHK(c, take_event(c, &a));
-      HIPCHK(c, take_event(c, &b));
-      c->ev_render.push_back(a);
-      c->ev_render.push_back(b);
-      HIPCHK(c, hipEventRecord(a, c->stream));
-    }
-    HIPCHK(c, launch_render(rp, c->n_cu * bpc, c->stream));
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->ev_render.back(), c->stream));
+    const int n_blocks = render_blocks(c, m, npix);
+    uint32_t* q_head = (uint32_t*)((char*)c->counters_multi.p + (size_t)e * kStatOffset);
+    const RenderParams rp = render_params(c, m, o, L, mp.seg_cap, mp.mem[e], q_head, stat);
+    if ((rc = timed(c, c->ev_render, [&] { HIPCHK(c, launch_render(rp, n_blocks, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
     if (spp > 1)
       HIPCHK(c, launch_spp_reduce((const float*)mp.mem[e].out_f32, (size_t)n_views * npix, spp, o->background, scratch_f32, (uint32_t*)out_u8[e], c->stream));
   }
@@ -1622,11 +1574,7 @@ int prv_first_hit(prv_ctx* c, int slot, const prv_camset* cs, const int* view_id
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = check_device_ptr(c, out, "out_voxel_dev")) != PRV_OK) return rc;
   std::vector<CamDev> cams(n_views);
-  for (int i = 0; i < n_views; i++) {
-    const int v = view_ids ? view_ids[i] : i;
-    if (v < 0 || v >= (int)cs->cams.size()) return fail(c, PRV_E_INVALID, "view id %d out of range", v);
-    cams[i] = cam_at(cs, v, W, H);
-  }
+  if ((rc = gather_cams(c, cs, view_ids, n_views, W, H, cams.data())) != PRV_OK) return rc;
   if ((rc = ensure(c, c->view_ids, (size_t)n_views * (sizeof(CamDev) + sizeof(int)))) != PRV_OK) return rc;
   HIPCHK(c, hipMemcpyAsync(c->view_ids.p, cams.data(), (size_t)n_views * sizeof(CamDev), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1648,11 +1596,7 @@ int prv_splat_points(prv_ctx* c, const float* xyz, const uint8_t* rgb, size_t n,
       (rc = check_device_ptr(c, out, "out_rgba8_dev")) != PRV_OK)
     return rc;
   std::vector<CamDev> cams(n_views);
-  for (int i = 0; i < n_views; i++) {
-    const int v = view_ids ? view_ids[i] : i;
-    if (v < 0 || v >= (int)cs->cams.size()) return fail(c, PRV_E_INVALID, "view id %d out of range", v);
-    cams[i] = cam_at(cs, v, W, H);
-  }
+  if ((rc = gather_cams(c, cs, view_ids, n_views, W, H, cams.data())) != PRV_OK) return rc;
   if ((rc = ensure(c, c->view_ids, (size_t)n_views * (sizeof(CamDev) + sizeof(int)))) != PRV_OK) return rc;
   if ((rc = ensure(c, c->stage, (size_t)n_views * W * H * 8)) != PRV_OK) return rc;
   HIPCHK(c, hipMemcpyAsync(c->view_ids.p, cams.data(), (size_t)n_views * sizeof(CamDev), hipMemcpyHostToDevice, c->stream));

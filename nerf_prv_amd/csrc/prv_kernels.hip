@@ -125,7 +125,6 @@ __device__ __forceinline__ void march_ray_setup(const PT& P, const float occ_lo[
     kk = blockIdx.z;
     morton16(threadIdx.x, ix, iy);
   }
-  const int spp_k = P.spp_k + (int)kk;
   const int px = (int)((tx << P.tile_w_log2) + ix), py = (int)((ty << P.tile_h_log2) + iy);
   r.valid = px < P.W && py < P.H;
   r.pix = ((kk * gridDim.y + (uint32_t)vi) * (uint32_t)P.H + (uint32_t)py) * (uint32_t)P.W + (uint32_t)px;
@@ -137,7 +136,7 @@ __device__ __forceinline__ void march_ray_setup(const PT& P, const float occ_lo[
   bool maybe = r.valid;
   const CamDev& cam = P.cams[P.view_ids[vi]];
   float ox, oy;
-  spp_offset(spp_k, ox, oy);
+  spp_offset((int)kk, ox, oy);
   // whole-tile rejection (block-uniform, before any per-ray work): the tile's pixels against the rectangle outside which no
   // ray of this view can meet the occupied box (CamDev::cull, computed on the host in double per render call)
   if (cam.cull[2] > 0) {
@@ -232,13 +231,8 @@ __device__ __forceinline__ void march_write(const PT& P, const MarchSink& Q, uin
   }
   if (!live && r.valid && !(PRV_ABLATE & 64)) {
     // dead ray: contributes exactly zero to its pixel
-    float4* out = reinterpret_cast<float4*>(Q.out_f32) + r.pix;
-    float4 v = P.spp_k == 0 ? make_float4(0.f, 0.f, 0.f, 0.f) : *out;
-    if (P.last_pass) {
-      v.x *= P.inv_spp; v.y *= P.inv_spp; v.z *= P.inv_spp; v.w *= P.inv_spp;
-      if (Q.out_u8) Q.out_u8[r.pix] = quantize_rgba8(v.x, v.y, v.z, v.w, P.bg);
-    }
-    if (P.spp_k == 0 || P.last_pass) *out = v;
+    reinterpret_cast<float4*>(Q.out_f32)[r.pix] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (P.last_pass && Q.out_u8) Q.out_u8[r.pix] = quantize_rgba8(0.f, 0.f, 0.f, 0.f, P.bg);
   }
 }
 
@@ -1020,17 +1014,9 @@ void render_queue64_kernel(RenderParams P) {
       done = last || T < P.min_T;
     }
     if (done) {
-      float4* out = reinterpret_cast<float4*>(P.out_f32) + pix;
-      float4 v = make_float4(cr, cg, cb, 1.0f - T);
-      if (P.spp_k != 0) {
-        const float4 prev = *out;
-        v.x = prev.x + v.x; v.y = prev.y + v.y; v.z = prev.z + v.z; v.w = prev.w + v.w;
-      }
-      if (P.last_pass) {
-        v.x *= P.inv_spp; v.y *= P.inv_spp; v.z *= P.inv_spp; v.w *= P.inv_spp;
-        if (P.out_u8) P.out_u8[pix] = quantize_rgba8(v.x, v.y, v.z, v.w, P.bg);
-      }
-      *out = v;
+      const float4 v = make_float4(cr, cg, cb, 1.0f - T);
+      reinterpret_cast<float4*>(P.out_f32)[pix] = v;
+      if (P.last_pass && P.out_u8) P.out_u8[pix] = quantize_rgba8(v.x, v.y, v.z, v.w, P.bg);
       active = false;
     }
   }
@@ -1696,7 +1682,7 @@ int render_instance_dense_levels(const FieldDev& fd) {
 template <bool NGP>
 static void launch_render_mode(const RenderParams& P, int n_blocks, hipStream_t s) {
   const int nd = render_instance_dense_levels(P.field);
-  if (P.cell_cache && nd > 0) { // the caller asked for the per-lane corner cache (prv_api.cpp: render_views says when)
+  if (P.cell_cache && nd > 0) { // the caller asked for the per-lane corner cache (prv_api.cpp: render_policy says when)
     if (P.field.n_features == 4 && nd == 5) {
       hipLaunchKernelGGL((render_queue64_kernel<4, 5, NGP, true>), dim3(n_blocks), dim3(256), 0, s, P);
       return;

@@ -24,7 +24,7 @@ struct MarchParams {
   FieldDev field;
   const CamDev* cams;
   const int* view_ids; // n_views indices into cams
-  int W, H, S, spp_k;
+  int W, H, S;
   uint32_t tiles_x, tiles_y;
   int tile_w_log2, tile_h_log2; // pixel tile of one 256-thread block
   int spp_inner_log2;           // > 0: sub-samples on adjacent lanes (spp = 2^n), 0: on grid.z
@@ -42,12 +42,12 @@ struct MarchParams {
   int n_sub;             // spatial_regions: the n_seg regions are n_seg / n_sub octant regions of n_sub sub-regions each (a counter per sub-region)
   float* out_f32; // n_views*H*W*4
   uint32_t* out_u8; // optional, n_views*H*W
-  float inv_spp;
   int last_pass;
   float bg[4];
 };
 
 // the ensemble's march in one launch (march_multi_kernel): the common fields carry MarchParams' names
+// (the host fills them in one place, prv_api.cpp: march_common)
 struct MarchMember {
   void* queue;
   uint4* queue_ext;
@@ -62,14 +62,13 @@ struct MarchMultiParams {
   float occ_lo[3], occ_hi[3]; // the union of the members' occupied boxes
   const CamDev* cams;         // cull rectangles against the union box
   const int* view_ids;
-  int W, H, spp_k;
+  int W, H;
   uint32_t tiles_x, tiles_y;
   int tile_w_log2, tile_h_log2, spp_inner_log2;
   unsigned long long* stat;
   int n_seg;
   uint32_t seg_cap;
   int spatial_regions, n_sub; // MarchParams::spatial_regions, n_sub
-  float inv_spp;
   int last_pass;
   float bg[4];
   int n_members;
@@ -99,8 +98,6 @@ struct RenderParams {
   float* out_f32;
   uint32_t* out_u8;
   float min_T;
-  float inv_spp;
-  int spp_k;
   int last_pass;
   int merge_max; // render_queue64: a group down to <= this many rays hands them to the other group's idle slots (0 = never)
   int pool_on;   // render_queue64: ... or, failing that, to the block's LDS tail pool (any wave's idle slots adopt them)
