@@ -236,6 +236,19 @@ int prv_render(prv_ctx* ctx, int model_slot, const prv_camset* cs, const int* vi
 int prv_render_rgba8(prv_ctx* ctx, int model_slot, const prv_camset* cs, const int* view_ids,
                      int n_views, const prv_render_opts* opts, uint8_t* out_rgba8_dev,
                      prv_stats* stats);
+/* replaces: testbed.render_mode = ngp.Depth; testbed.render(w, h, spp, True) (run.py:287-288, 304).
+ * out_depth_dev: n_views*h*w float32, premultiplied z-depth in engine units:
+ *   per ray (every spp sub-sample), over exactly the samples, weights and early termination prv_render composites,
+ *   D = sum_i w_i t_i (w_i = alpha_i T_i, the sample's colour weight; t_i = fmaf(i + 0.5, dt, t0), its ray parameter:
+ *   directions are unit length from the camera centre, so t_i is a distance), and z = D * dot(d, f), f = the view's
+ *   forward axis (column 2 of its engine-frame c2w, normalised; lens cameras too): depth along the optical axis,
+ *   premultiplied by opacity like the colour channels.  The pixel is the mean of its sub-samples (summed in order, then
+ *   scaled by 1/spp); rays that miss the box or have no live sample give exactly 0.  Engine units (the unit cube):
+ *   dataset units = engine / scale.  ASSUMED (the engine is not in the reference tree): upstream's Depth mode outputs
+ *   camera-axis depth composited like colour.
+ * out_rgba_dev: as prv_render (bit-identical to it), or NULL (rendered into a context scratch buffer). */
+int prv_render_depth(prv_ctx* ctx, int model_slot, const prv_camset* cs, const int* view_ids, int n_views,
+                     const prv_render_opts* opts, float* out_rgba_dev, float* out_depth_dev, prv_stats* stats);
 int prv_quantize_rgba8(prv_ctx* ctx, const float* rgba_dev, size_t n_pixels, const float bg[4],
                        uint8_t* out_rgba8_dev);
 

@@ -11,6 +11,7 @@ Two layers:
 No CPU fallback: every call goes to libprv_hip.so; errors raise `PrvError`.
 """
 import ctypes as C
+import enum
 import json
 import math
 
@@ -30,6 +31,16 @@ FIELD_512 = dict(n_levels=16, n_features=2, log2_hashmap=21, base_res=16, finest
 # offsets (prv_api.cpp: FieldDev::wide_offsets)
 FIELD_HBM = dict(n_levels=16, n_features=2, log2_hashmap=24, base_res=16, finest_res=2048, occ_res=128,
                  density_bias=3.0, table_amp=4.0)
+
+
+class RenderMode(enum.IntEnum):
+    """testbed.render_mode (run.py:287: `testbed.render_mode = ngp.Depth` for --screenshot_depth)"""
+
+    Shade = 0
+    Depth = 1
+
+
+Shade, Depth = RenderMode.Shade, RenderMode.Depth  # as pyngp exports them (ngp.Depth)
 
 
 class PrvError(RuntimeError):
@@ -286,6 +297,19 @@ class Context:
                                             _ptr(out), C.byref(st) if want_stats else None))
         return out, st
 
+    def render_depth(self, slot, camset, view_ids, opts, out=None, out_depth=None, want_stats=True):
+        """prv_render_depth -> (rgba [n, h, w, 4] as `render`, depth [n, h, w] float32, stats).  depth: z-depth along each
+        view's optical axis in engine units, premultiplied by opacity like the colour (include/prv.h)"""
+        ids = self._ids(camset, view_ids)
+        if out is None:
+            out = self.torch.empty((len(ids), opts.height, opts.width, 4), dtype=self.torch.float32, device=self.device)
+        if out_depth is None:
+            out_depth = self.torch.empty((len(ids), opts.height, opts.width), dtype=self.torch.float32, device=self.device)
+        st = L.Stats()
+        self._chk(self.lib.prv_render_depth(self.handle, slot, camset.handle, _ptr(ids), len(ids), C.byref(opts), _ptr(out),
+                                            _ptr(out_depth), C.byref(st) if want_stats else None))
+        return out, out_depth, st
+
     def first_hit(self, slot, camset, view_ids, width, height, max_range=1e30):
         ids = self._ids(camset, view_ids)
         out = self.torch.empty((len(ids), height, width), dtype=self.torch.int32, device=self.device)
@@ -510,6 +534,22 @@ class Mesh:
             pass
 
 
+def write_image_depth(path, image, scale):
+    """run.py:307 `write_image_depth(outname, image, ref_transforms["scale"])`: a single-channel 16-bit PNG of channel 0 of
+    `image` (a Depth-mode Testbed.render; a 2-D array is taken as it is), uint16(clip(round(z / scale * 1000), 0, 65535)):
+    millimetres of the dataset unit, which a reader with depth_scale 0.001 (the reference's DefaultConfiguration.yaml:50)
+    takes back to dataset units.  round is numpy's (halves to even).  The depth is written as rendered: premultiplied by
+    opacity, with no un-premultiply and no opacity threshold, so partially transparent pixels read nearer than the surface.
+    ASSUMED: upstream's write_image_depth lives in the unvendored scripts/common.py."""
+    from PIL import Image
+
+    z = np.asarray(image, np.float64)
+    if z.ndim == 3:
+        z = z[..., 0]
+    mm = np.clip(np.round(np.nan_to_num(z) / float(scale) * 1000.0), 0, 65535).astype(np.uint16)
+    Image.fromarray(mm).save(path)  # uint16 -> mode I;16
+
+
 def engine_to_dataset(xyz, scale, offset):
     """engine-frame positions -> the dataset (transforms.json) frame: q = (e2, e0, e1), (q - offset) / scale"""
     e = np.asarray(xyz, np.float64).reshape(-1, 3)
@@ -726,6 +766,7 @@ class Testbed:
     run.py:285  testbed.fov_axis = 0 ; testbed.fov = camera_angle_x * 180 / pi
     run.py:296  testbed.set_nerf_camera_matrix(M[:-1,:])
     run.py:304  image = testbed.render(w, h, spp, True)  -> float32 HxWx4, linear
+    run.py:287  testbed.render_mode = ngp.Depth         -> render() returns (z, z, z, alpha) (prv_render_depth)
     """
 
     def __init__(self, device=0):
@@ -743,6 +784,7 @@ class Testbed:
         self._slot = 0
         self._have_model = False
         self.render_ground_truth = False
+        self.render_mode = RenderMode.Shade
         self.steps_per_frame = 16  # ASSUMED: upstream trains a batch of steps per frame() call
         self.train_options = None  # TrainOpts override
         self._trainer = None
@@ -851,6 +893,8 @@ class Testbed:
             raise NotImplementedError("fov_axis must be 0 (run.py:285)")
         eff_spp = 1 if self.snap_to_pixel_centers else int(spp)
         opts = engine_render_opts(width, height, self.nerf.samples_per_ray, eff_spp, self.nerf.render_min_transmittance)
+        if self.render_mode == RenderMode.Depth:
+            return self._render_depth(width, height, opts)
         if self._training_view is not None:  # dataset camera: own intrinsics + lens (run.py:242-247)
             if self.render_ground_truth:
                 img = self._ground_truth(self._training_view, width, height)
@@ -866,6 +910,21 @@ class Testbed:
         bg = self.ctx.torch.tensor(self.background_color, dtype=img.dtype, device=img.device)
         img = img + (1.0 - img[..., 3:4]) * bg  # composite over the background colour
         return img.cpu().numpy()
+
+    def _render_depth(self, width, height, opts):
+        """Depth mode: (h, w, 4) float32, r = g = b = z (premultiplied z-depth, engine units; prv_render_depth), a = opacity;
+        the background colour is not composited"""
+        if self._training_view is not None:
+            if self.render_ground_truth:
+                raise NotImplementedError("render_ground_truth has no depth image")
+            rgba, depth, _ = self.ctx.render_depth(self._slot, self._dataset_cams, [self._training_view], opts, want_stats=False)
+        else:
+            tm = np.vstack([self._matrix, [0, 0, 0, 1]])
+            cams = self.ctx.cameras_from_matrices(tm, self.fov * math.pi / 180.0, width, height, self.scale, self.offset)
+            rgba, depth, _ = self.ctx.render_depth(self._slot, cams, None, opts, want_stats=False)
+            cams.close()
+        z = depth[0]
+        return self.ctx.torch.stack([z, z, z, rgba[0][..., 3]], dim=-1).cpu().numpy()
 
     # ASSUMED: pyngp's signatures (upstream testbed.compute_marching_cubes_mesh / compute_and_save_marching_cubes_mesh are
     # not in the reference tree; run.py:282 passes (filename, [res, res, res])).  resolution = (x, y, z) grid points; aabb =

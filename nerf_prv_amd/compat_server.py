@@ -10,6 +10,9 @@ This server honours the same files but never spawns anything: it parses the run.
 out of the script and answers it in-process through the C ABI:
   --screenshot_transforms J --screenshot_dir D   -> render every frame of J, write D/<basename>.png
                                                     (run.py:284-309)
+    ... --screenshot_depth                        -> the frames' depth images instead (prv_render_depth), written under
+                                                    the same names as 16-bit PNGs by api.write_image_depth with J's
+                                                    "scale" (run.py:49, 287-288, 306-307); no colour PNG
   --test_transforms J --save_metrics M           -> evaluate against reference images, write M
                                                     (run.py:213-277)
   --save_mesh P [--marching_cubes_res N]         -> marching-cubes mesh of the field at N^3 (default 256), written to
@@ -18,7 +21,8 @@ out of the script and answers it in-process through the C ABI:
                                                     (run.py:109, 185-208; `train_desc=` names the field),
                                                     unless a `load_model(scene, ctx) -> slot` callable supplies
                                                     weights from elsewhere (e.g. `.prvf` files)
-PNG encoding uses PIL (present in the image); the byte rule is the library's (prv_render_rgba8).
+PNG encoding uses PIL (present in the image); the byte rule is the library's (prv_render_rgba8), the depth rule
+api.write_image_depth's.
 """
 import json
 import os
@@ -138,14 +142,22 @@ class CompatServer:
             cams = self.ctx.cameras_from_json(args["screenshot_transforms"])
             w, h = int(ref_transforms["w"]), int(ref_transforms["h"])  # run.py:304
             opts = api.engine_render_opts(w, h, self.samples_per_ray, self.spp, 0.01, background=(0.0, 0.0, 0.0, 1.0))
-            u8, _ = self.ctx.render_rgba8(slot, cams, None, opts)
-            u8 = u8.cpu().numpy()
+            depth = "screenshot_depth" in args["flags"]  # run.py:287-288: testbed.render_mode = ngp.Depth
+            if depth:
+                _, imgs, _ = self.ctx.render_depth(slot, cams, None, opts, want_stats=False)
+                scale = float(ref_transforms.get("scale", 0.33))  # run.py:307 (upstream's default scale without one)
+            else:
+                imgs, _ = self.ctx.render_rgba8(slot, cams, None, opts)
+            imgs = imgs.cpu().numpy()
             os.makedirs(args["screenshot_dir"], exist_ok=True)
-            for frame, img in zip(ref_transforms["frames"], u8):
+            for frame, img in zip(ref_transforms["frames"], imgs):
                 name = os.path.basename(frame["file_path"])  # run.py:297
                 if not os.path.splitext(name)[1]:
                     name += ".png"
-                Image.fromarray(img, "RGBA").save(os.path.join(args["screenshot_dir"], name))
+                if depth:
+                    api.write_image_depth(os.path.join(args["screenshot_dir"], name), img, scale)  # run.py:307
+                else:
+                    Image.fromarray(img, "RGBA").save(os.path.join(args["screenshot_dir"], name))
             cams.close()
 
     def _evaluate(self, slot, args):

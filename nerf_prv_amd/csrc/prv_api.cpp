@@ -78,6 +78,7 @@ struct prv_ctx {
   Model models[PRV_MAX_SLOTS];
   // grow-only workspaces
   Buffer queue, queue_ext, stage, counters, view_ids, img_f32, partial, records, dbg[6];
+  Buffer stage_depth; // prv_render_depth with spp > 1: the sub-samples' depth images (spp x batch x image floats)
   Buffer counters_multi, occ_multi; // the ensemble's one-launch march: queue heads + counts per member, the interleaved occupancy bytes
   int march_multi = -1;             // PRV_MARCH_MULTI=0/1 (-1: on where an instance exists, render_ensemble_ngp)
   Buffer img_u8[PRV_MAX_MODELS];
@@ -789,10 +790,12 @@ RenderParams render_params(prv_ctx* c, const Model& m, const prv_render_opts* o,
 }
 
 // The render of one batch of views into out_f32 (+ optional out_u8).  Views are dealt to
-// the queue in batches so the queue stays within queue_budget bytes.
+// the queue in batches so the queue stays within queue_budget bytes.  out_depth (prv_render_depth): the views' depth images
+// as well, n_views * H * W floats, through the depth instances of the render kernel; null: the colour render alone.
 int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views,
-                 const prv_render_opts* o, float* out_f32, uint8_t* out_u8, bool zero_stats, bool private_output = false) {
-  if (o->spp != 1 || out_u8) private_output = false; // sub-sample staging and byte images are written in full
+                 const prv_render_opts* o, float* out_f32, uint8_t* out_u8, bool zero_stats, bool private_output = false,
+                 float* out_depth = nullptr) {
+  if (o->spp != 1 || out_u8 || out_depth) private_output = false; // sub-sample staging, byte and depth images are written in full
   const Model& m = c->models[slot];
   const int W = o->width, H = o->height, spp = o->spp;
   const size_t npix = (size_t)W * H;
@@ -816,7 +819,8 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
   const size_t slot_bytes = kRecordBytes + (ngp ? kExtBytes : 0); // NGP: every queue slot has its mask-extension slot
   size_t batch = std::max<size_t>(1, c->queue_budget / (npix * slot_bytes * (size_t)spp));
   batch = std::min<size_t>(batch, (size_t)n_views);
-  if (spp > 1) batch = std::min<size_t>(batch, std::max<size_t>(1, c->stage_budget / (npix * 16 * (size_t)spp)));
+  const size_t stage_px = out_depth ? 16 + 4 : 16; // staging bytes per sub-sample pixel: RGBA (+ depth)
+  if (spp > 1) batch = std::min<size_t>(batch, std::max<size_t>(1, c->stage_budget / (npix * stage_px * (size_t)spp)));
   if (batch * npix * (size_t)spp >= (1ull << 32)) batch = ((1ull << 32) - 1) / (npix * (size_t)spp); // 32-bit pixel ids
   if (batch == 0) return fail(c, PRV_E_INVALID, "image x spp too large");
   const MarchLayout L(c, W, H, spp);
@@ -825,12 +829,17 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
   if ((rc = ensure(c, c->queue, seg_cap_max * (size_t)L.n_seg * kRecordBytes)) != PRV_OK) return rc;
   if (ngp && (rc = ensure(c, c->queue_ext, seg_cap_max * (size_t)L.n_seg * kExtBytes)) != PRV_OK) return rc;
   if (spp > 1 && (rc = ensure(c, c->stage, batch * npix * (size_t)spp * 16)) != PRV_OK) return rc;
+  if (spp > 1 && out_depth && (rc = ensure(c, c->stage_depth, batch * npix * (size_t)spp * 4)) != PRV_OK) return rc;
 
   const int n_blocks = render_blocks(c, m, npix);
   for (size_t b0 = 0; b0 < (size_t)n_views; b0 += batch) {
     const int nb = (int)std::min(batch, (size_t)n_views - b0);
     float* dst_f32 = out_f32 + b0 * npix * 4;
     uint32_t* dst_u8 = out_u8 ? (uint32_t*)out_u8 + b0 * npix : nullptr;
+    float* dst_depth = out_depth ? out_depth + b0 * npix : nullptr;
+    float* depth_target = spp > 1 ? (float*)c->stage_depth.p : dst_depth;
+    // the march writes no depth: every pixel starts at 0, which is what a dead ray contributes
+    if (out_depth) HIPCHK(c, hipMemsetAsync(depth_target, 0, (size_t)nb * npix * (size_t)spp * 4, c->stream));
     // one fill per batch: heads and counts, and with them the statistics when this call starts a new window
     HIPCHK(c, hipMemsetAsync(c->counters.p, 0, b0 == 0 && zero_stats ? kCountersBytes : kStatOffset, c->stream));
     MarchParams mp;
@@ -866,8 +875,21 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
     }
     if ((rc = timed(c, c->ev_march, [&] { HIPCHK(c, launch_march(mp, nb, spp, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
     const RenderParams rp = render_params(c, m, o, L, mp.seg_cap, {mp.queue, mp.queue_ext, mp.queue_count, mp.out_f32, mp.out_u8}, q_head, stat);
-    if ((rc = timed(c, c->ev_render, [&] { HIPCHK(c, launch_render(rp, n_blocks, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
+    if (out_depth) {
+      RenderDepthParams dp;
+      memset(&dp, 0, sizeof(dp));
+      dp.r = rp;
+      dp.out_depth = depth_target;
+      dp.cams = mp.cams;
+      dp.view_ids = mp.view_ids;
+      dp.npix = (uint32_t)npix;
+      dp.nb = (uint32_t)nb;
+      if ((rc = timed(c, c->ev_render, [&] { HIPCHK(c, launch_render_depth(dp, n_blocks, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
+    } else {
+      if ((rc = timed(c, c->ev_render, [&] { HIPCHK(c, launch_render(rp, n_blocks, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
+    }
     if (spp > 1) HIPCHK(c, launch_spp_reduce((const float*)c->stage.p, (size_t)nb * npix, spp, o->background, dst_f32, dst_u8, c->stream));
+    if (spp > 1 && out_depth) HIPCHK(c, launch_spp_reduce_depth((const float*)c->stage_depth.p, (size_t)nb * npix, spp, dst_depth, c->stream));
   }
   return PRV_OK;
 }
@@ -1073,6 +1095,7 @@ void prv_destroy(prv_ctx* c) {
   release(c->queue);
   release(c->queue_ext);
   release(c->stage);
+  release(c->stage_depth);
   release(c->counters);
   if (c->pin) (void)hipHostFree(c->pin);
   if (c->pin_ev) (void)hipEventDestroy(c->pin_ev);
@@ -1560,6 +1583,23 @@ int prv_render_rgba8(prv_ctx* c, int slot, const prv_camset* cs, const int* view
   const size_t npix = (size_t)o->width * o->height;
   if ((rc = ensure(c, c->img_f32, std::max<size_t>(16, (size_t)n_views * npix * 16))) != PRV_OK) return rc;
   if ((rc = render_views(c, slot, cs, view_ids, n_views, o, (float*)c->img_f32.p, out, true)) != PRV_OK) return rc;
+  return fetch_stats(c, o, n_views, 1, st);
+} catch (...) { return caught(c); }
+
+int prv_render_depth(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, const prv_render_opts* o,
+                     float* out_rgba, float* out_depth, prv_stats* st) try {
+  if (!c) return PRV_E_INVALID;
+  int rc;
+  if ((rc = check_model(c, slot)) != PRV_OK || (rc = check_opts(c, o)) != PRV_OK) return rc;
+  if (!cs || n_views < 0 || (!out_depth && n_views > 0)) return fail(c, PRV_E_INVALID, "bad camset / view count / depth output");
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = check_device_ptr(c, out_depth, "out_depth_dev")) != PRV_OK) return rc;
+  if ((rc = check_device_ptr(c, out_rgba, "out_rgba_dev")) != PRV_OK) return rc;
+  if (!out_rgba && n_views > 0) { // the colour is rendered anyway (the opacity terminates the rays): into the context's scratch
+    if ((rc = ensure(c, c->img_f32, (size_t)n_views * o->width * o->height * 16)) != PRV_OK) return rc;
+    out_rgba = (float*)c->img_f32.p;
+  }
+  if ((rc = render_views(c, slot, cs, view_ids, n_views, o, out_rgba, nullptr, true, false, out_depth)) != PRV_OK) return rc;
   return fetch_stats(c, o, n_views, 1, st);
 } catch (...) { return caught(c); }
 

@@ -10,6 +10,7 @@
 //       the column, weights staged once per block in LDS as prepacked A fragments, activations never leaving
 //       registers.  Front-to-back compositing is sequential per ray inside one lane (deterministic).  A group of 32
 //       slots refills as a whole cohort from the queue; thinned-out tails merge / pool (see the kernel).
+//       render_depth: the same kernel body with one more per-ray sum, the depth (prv_render_depth).
 //  K_S* score kernels : per-view reductions in fp64, fixed reduction order (no float
 //       atomics), so rankings are reproducible bit for bit.
 //
@@ -702,16 +703,17 @@ __device__ __forceinline__ void clock_stamp_end(unsigned long long* stat) {
 // every weight fragment.  A group refills when all its 32 slots are idle (whole-group lockstep).
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
 
-template <int F, int NDENSE, bool NGP, bool CACHE = false>
-__global__ __launch_bounds__(256)
-// the cached instances must keep TWO waves per SIMD (<= 256 registers); the plain ones with dense levels are asked for THREE (<= 168): left alone
-// they took 172 since the octant regions of round 6 -- two waves -- and three are 1.7-2.5 % faster (r06ay); the all-hashed ones would spill 50-80
-__attribute__((amdgpu_waves_per_eu(CACHE ? 2 : NDENSE == 0 ? 1 : 3)))
-void render_queue64_kernel(RenderParams P) {
+// The body of render_queue64_kernel and render_depth_kernel.  DEPTH: the ray also sums D = sum_i w_i t_i (w_i = the
+// sample's compositing weight, t_i its ray parameter) and writes z = D * dot(d, f) to PD->out_depth[pix] when it ends
+// (f = the view's normalised forward axis, column 2 of its c2w: z-depth along the optical axis, premultiplied by opacity);
+// the ray's dynamic state that tail merge and pool move between lanes gains a 7th word, D.  PD is unused without DEPTH.
+template <int F, int NDENSE, bool NGP, bool CACHE, bool DEPTH>
+__device__ __forceinline__ void render_queue64_body(RenderParams P, const RenderDepthParams* PD) {
+  constexpr int kMoveWords = DEPTH ? 7 : 6; // {record, next sample, T, r, g, b (, D)}
   __shared__ half8 wl[kNumFrags * 64];
-  __shared__ uint32_t mv[4][32][6]; // tail merges: {record, next sample, T, r, g, b} of the rays that change slots, per wave
+  __shared__ uint32_t mv[4][32][kMoveWords]; // tail merges: {record, next sample, T, r, g, b (, D)} of the rays that change slots, per wave
   constexpr uint32_t kPoolCap = 192;
-  __shared__ uint32_t pool[kPoolCap][6]; // the block's tail pool: rays a group gave up, waiting for an idle slot of ANY of the block's waves
+  __shared__ uint32_t pool[kPoolCap][kMoveWords]; // the block's tail pool: rays a group gave up, waiting for an idle slot of ANY of the block's waves
   __shared__ uint32_t pool_n, pool_lock;
   for (int i = threadIdx.x; i < kNumFrags * 64; i += 256) wl[i] = P.field.frags64[i];
   if (threadIdx.x == 0) {
@@ -745,6 +747,7 @@ void render_queue64_kernel(RenderParams P) {
   // when this one is spent (next_chunk below); nothing about them lives in registers.
   uint32_t cur = 0, m1 = 0, m2 = 0, m3 = 0, base = 0;
   float T = 1.f, cr = 0.f, cg = 0.f, cb = 0.f;
+  float D = 0.f; // DEPTH: sum of w_i t_i so far
   half8 shA = {0, 0, 0, 0, 0, 0, 0, 0}, shB = {0, 0, 0, 0, 0, 0, 0, 0}; // SH rows [8g, 8g+8) of the rays in slots (r, A) and (r, B)
   bool drained = false;
   unsigned long long n_eval = 0ull, n_rounds = 0ull;
@@ -836,7 +839,7 @@ void render_queue64_kernel(RenderParams P) {
       if (src >= 0) { // wave-uniform
         const uint32_t a_src = src == 0 ? aA : aB, a_dst = src == 0 ? aB : aA, n_src = src == 0 ? nA : nB;
         const uint32_t below = (1u << r) - 1u;
-        uint32_t(*slot)[6] = mv[threadIdx.x >> 6];
+        uint32_t(*slot)[kMoveWords] = mv[threadIdx.x >> 6];
         if (g == src && active) {
           uint32_t* e = slot[__popc(a_src & below)];
           e[0] = rec_i;
@@ -845,6 +848,7 @@ void render_queue64_kernel(RenderParams P) {
           e[3] = __float_as_uint(cr);
           e[4] = __float_as_uint(cg);
           e[5] = __float_as_uint(cb);
+          if constexpr (DEPTH) e[6] = __float_as_uint(D);
           active = false;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -859,6 +863,7 @@ void render_queue64_kernel(RenderParams P) {
           else shA = sh;
           if (g != src) { // the destination lane itself takes the ray over
             T = __uint_as_float(e[2]); cr = __uint_as_float(e[3]); cg = __uint_as_float(e[4]); cb = __uint_as_float(e[5]);
+            if constexpr (DEPTH) D = __uint_as_float(e[6]);
             take_ray(ri, e[1]);
           }
         }
@@ -888,6 +893,7 @@ void render_queue64_kernel(RenderParams P) {
             e[3] = __float_as_uint(cr);
             e[4] = __float_as_uint(cg);
             e[5] = __float_as_uint(cb);
+            if constexpr (DEPTH) e[6] = __float_as_uint(D);
             active = false;
           }
           if (fits && lane == 0) *(volatile uint32_t*)&pool_n = at + n_g;
@@ -905,11 +911,11 @@ void render_queue64_kernel(RenderParams P) {
         const uint32_t have = *(volatile uint32_t*)&pool_n;
         const uint32_t take = min(have, n_idle), from = have - take;
         const uint32_t kth = (uint32_t)__popc(~a_g & below);
-        uint32_t ent[6] = {0, 0, 0, 0, 0, 0};
+        uint32_t ent[kMoveWords] = {};
         const bool mine = !((a_g >> r) & 1u) && kth < take; // both lanes of the slot
         if (mine) {
 #pragma unroll
-          for (int q = 0; q < 6; q++) ent[q] = pool[from + kth][q];
+          for (int q = 0; q < kMoveWords; q++) ent[q] = pool[from + kth][q];
         }
         if (lane == 0) *(volatile uint32_t*)&pool_n = from;
         pool_release();
@@ -919,6 +925,7 @@ void render_queue64_kernel(RenderParams P) {
           else shB = sh;
           if (g == grp) {
             T = __uint_as_float(ent[2]); cr = __uint_as_float(ent[3]); cg = __uint_as_float(ent[4]); cb = __uint_as_float(ent[5]);
+            if constexpr (DEPTH) D = __uint_as_float(ent[6]);
             take_ray(ent[0], ent[1]);
           }
         }
@@ -953,6 +960,7 @@ void render_queue64_kernel(RenderParams P) {
           else shB = sh;
           if (g == grp) {
             T = 1.f; cr = 0.f; cg = 0.f; cb = 0.f;
+            if constexpr (DEPTH) D = 0.f;
             take_ray(q_cur + (uint32_t)r, 0u);
           }
         }
@@ -976,6 +984,7 @@ void render_queue64_kernel(RenderParams P) {
 #pragma unroll
     for (int s = 0; s < 4; s++) asm volatile("" : "=v"(f[s]));
     bool last = false;
+    float ts = 0.f; // DEPTH: the sample's ray parameter, kept across the MLP
     if (active) {
       const uint32_t i = base + (uint32_t)__builtin_ctz(cur);
       cur &= cur - 1u;
@@ -990,6 +999,7 @@ void render_queue64_kernel(RenderParams P) {
         }
       }
       const float t = fmaf((float)i + 0.5f, dt, t0);
+      if constexpr (DEPTH) ts = t;
       encode_sample<F, NDENSE, CACHE>(P.field.table, lvl, hc, fmaf(t, d[0], o[0]), fmaf(t, d[1], o[1]), fmaf(t, d[2], o[2]), f, cc);
     }
     // f[2s] | f[2s+1] = k rows [16s, 16s+8) | [16s+8, 16s+16) of the lane's own sample -> B operands of the two groups
@@ -1010,6 +1020,7 @@ void render_queue64_kernel(RenderParams P) {
       cr = fmaf(wgt, fast_sigmoid(lr), cr);
       cg = fmaf(wgt, fast_sigmoid(lg), cg);
       cb = fmaf(wgt, fast_sigmoid(lb), cb);
+      if constexpr (DEPTH) D = fmaf(wgt, ts, D);
       T = T * (1.0f - alpha);
       done = last || T < P.min_T;
     }
@@ -1017,6 +1028,13 @@ void render_queue64_kernel(RenderParams P) {
       const float4 v = make_float4(cr, cg, cb, 1.0f - T);
       reinterpret_cast<float4*>(P.out_f32)[pix] = v;
       if (P.last_pass && P.out_u8) P.out_u8[pix] = quantize_rgba8(v.x, v.y, v.z, v.w, P.bg);
+      if constexpr (DEPTH) {
+        // image pix / npix of the launch is a sub-sample of view (pix / npix) % nb
+        const CamDev& cam = PD->cams[PD->view_ids[(pix / PD->npix) % PD->nb]];
+        const float fx = cam.c2w[2], fy = cam.c2w[6], fz = cam.c2w[10];
+        const float inv = 1.0f / sqrtf(fmaf(fx, fx, fmaf(fy, fy, fz * fz)));
+        PD->out_depth[pix] = D * (fmaf(d[0], fx, fmaf(d[1], fy, d[2] * fz)) * inv);
+      }
       active = false;
     }
   }
@@ -1025,6 +1043,24 @@ void render_queue64_kernel(RenderParams P) {
     atomicAdd(P.stat_evaluated + 1, n_rounds);
   }
   clock_stamp_end(P.stat_evaluated);
+}
+
+template <int F, int NDENSE, bool NGP, bool CACHE = false>
+__global__ __launch_bounds__(256)
+// the cached instances must keep TWO waves per SIMD (<= 256 registers); the plain ones with dense levels are asked for THREE (<= 168): left alone
+// they took 172 since the octant regions of round 6 -- two waves -- and three are 1.7-2.5 % faster (r06ay); the all-hashed ones would spill 50-80
+__attribute__((amdgpu_waves_per_eu(CACHE ? 2 : NDENSE == 0 ? 1 : 3)))
+void render_queue64_kernel(RenderParams P) {
+  render_queue64_body<F, NDENSE, NGP, CACHE, false>(P, nullptr);
+}
+
+// prv_render_depth: the render with the depth sum (render_queue64_body, DEPTH), for the (F, NDENSE) set of the colour
+// instances; no corner-cache instance.  Waves per SIMD as the colour instances ask for: no spills at either
+// (scripts/kernel_resources.py prv_kernels.hip render_depth)
+template <int F, int NDENSE, bool NGP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NDENSE == 0 ? 1 : 3)))
+void render_depth_kernel(RenderDepthParams P) {
+  render_queue64_body<F, NDENSE, NGP, false, true>(P.r, &P);
 }
 
 
@@ -1146,6 +1182,16 @@ __global__ __launch_bounds__(256) void spp_reduce_kernel(const float4* __restric
     a.x *= inv_spp; a.y *= inv_spp; a.z *= inv_spp; a.w *= inv_spp;
     out[i] = a;
     if (out_u8) out_u8[i] = quantize_rgba8(a.x, a.y, a.z, a.w, bg);
+  }
+}
+
+// the depth image's reduce (prv_render_depth, spp > 1): out[pixel] = (((z0 + z1) + z2) + ...) * inv_spp, spp_reduce_kernel's order
+__global__ __launch_bounds__(256) void spp_reduce_depth_kernel(const float* __restrict__ stage, size_t n, int spp, float inv_spp,
+                                                               float* __restrict__ out) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    float a = stage[i];
+    for (int k = 1; k < spp; k++) a = a + stage[(size_t)k * n + i];
+    out[i] = a * inv_spp;
   }
 }
 
@@ -1644,6 +1690,13 @@ hipError_t launch_spp_reduce(const float* stage, size_t n_pixels, int spp, const
   return hipGetLastError();
 }
 
+hipError_t launch_spp_reduce_depth(const float* stage, size_t n_pixels, int spp, float* out, hipStream_t s) {
+  unsigned blocks = (unsigned)std::min<size_t>(4096, (n_pixels + 255) / 256);
+  if (blocks == 0) return hipSuccess;
+  hipLaunchKernelGGL(spp_reduce_depth_kernel, dim3(blocks), dim3(256), 0, s, stage, n_pixels, spp, 1.0f / (float)spp, out);
+  return hipGetLastError();
+}
+
 hipError_t launch_march(const MarchParams& P, int n_views, int n_spp, hipStream_t s) {
   dim3 grid((unsigned)(P.live_grid ? P.live_tiles_max : P.tiles_x * P.tiles_y), (unsigned)n_views, (unsigned)(P.spp_inner_log2 > 0 ? 1 : n_spp));
   if (grid.x == 0) return hipSuccess; // no view of the batch can see the object
@@ -1703,6 +1756,26 @@ static void launch_render_mode(const RenderParams& P, int n_blocks, hipStream_t 
 hipError_t launch_render(const RenderParams& P, int n_blocks, hipStream_t s) {
   if (P.step_mode == PRV_STEP_NGP) launch_render_mode<true>(P, n_blocks, s);
   else launch_render_mode<false>(P, n_blocks, s);
+  return hipGetLastError();
+}
+
+template <bool NGP>
+static void launch_render_depth_mode(const RenderDepthParams& P, int n_blocks, hipStream_t s) {
+  const int nd = render_instance_dense_levels(P.r.field); // (P.r.cell_cache is not looked at: no cached depth instance)
+  if (P.r.field.n_features == 4) {
+    if (nd == 5) hipLaunchKernelGGL((render_depth_kernel<4, 5, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
+    else if (nd == 3) hipLaunchKernelGGL((render_depth_kernel<4, 3, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
+    else hipLaunchKernelGGL((render_depth_kernel<4, 0, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
+  } else {
+    if (nd == 10) hipLaunchKernelGGL((render_depth_kernel<2, 10, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
+    else if (nd == 6) hipLaunchKernelGGL((render_depth_kernel<2, 6, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
+    else hipLaunchKernelGGL((render_depth_kernel<2, 0, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
+  }
+}
+
+hipError_t launch_render_depth(const RenderDepthParams& P, int n_blocks, hipStream_t s) {
+  if (P.r.step_mode == PRV_STEP_NGP) launch_render_depth_mode<true>(P, n_blocks, s);
+  else launch_render_depth_mode<false>(P, n_blocks, s);
   return hipGetLastError();
 }
 

@@ -105,6 +105,17 @@ struct RenderParams {
   float bg[4];
 };
 
+// the depth render (prv_render_depth, render_depth_kernel): the colour launch's parameters, untouched, plus where the depth
+// goes and how a ray finds its view's camera
+struct RenderDepthParams {
+  RenderParams r;
+  float* out_depth;     // one float per pixel of the launch's images (r.out_f32 / 4): premultiplied z-depth, engine units
+  const CamDev* cams;   // image i of the launch (i = pix / npix; sub-sample i / nb of view i % nb) is seen by cams[view_ids[i % nb]]
+  const int* view_ids;
+  uint32_t npix;        // W * H
+  uint32_t nb;          // views in the launch
+};
+
 struct EnsembleParams {
   const uint32_t* imgs[PRV_MAX_MODELS];
   int E;
@@ -132,6 +143,8 @@ hipError_t launch_march(const MarchParams& P, int n_views, int n_spp, hipStream_
 hipError_t launch_spp_reduce(const float* stage, size_t n_pixels, int spp, const float bg[4], float* out, uint32_t* out_u8,
                              hipStream_t s);
 hipError_t launch_render(const RenderParams& P, int n_blocks, hipStream_t s);
+hipError_t launch_render_depth(const RenderDepthParams& P, int n_blocks, hipStream_t s);
+hipError_t launch_spp_reduce_depth(const float* stage, size_t n_pixels, int spp, float* out, hipStream_t s);
 int render_instance_dense_levels(const FieldDev& fd); // NDENSE of the render_queue64_kernel<F, NDENSE> instance launch_render picks
 struct PreceptPose {
   double w2c[16], c2w[16];
