@@ -47,6 +47,7 @@ struct Model {
   prv_field_desc desc{};
   FieldDev dev{};
   uint64_t table_halfs = 0, occ_words = 0;
+  uint64_t phys_bytes = 0; // the kernel layout of THIS field (phys may be a larger allocation left by an earlier one)
   float occ_lo[3] = {0, 0, 0}, occ_hi[3] = {1, 1, 1};
   Buffer table, phys, occ, occ_coarse, frags, frags64, mlp; // table/mlp = canonical (ABI) copies kept for export; phys = kernel layout
 };
@@ -371,6 +372,7 @@ int install_model(prv_ctx* c, int slot, const prv_field_desc& d, const uint16_t*
   }
   if (ptotal * ebytes >= (1ull << 32)) return fail(c, PRV_E_INVALID, "field too large for 32-bit gather offsets");
   if ((rc = ensure(c, m.phys, ptotal * ebytes)) != PRV_OK) return rc;
+  m.phys_bytes = ptotal * ebytes;
   HIPCHK(c, hipMemsetAsync(m.phys.p, 0, ptotal * ebytes, c->stream));
   for (int l = 0; l < d.n_levels; l++) {
     RepackLevel R{lv[l].offset, poff[l], lv[l].size, lv[l].res, sx[l], lv[l].hashed};
@@ -1936,7 +1938,7 @@ int prv_debug_model_layout(prv_ctx* c, int slot, prv_model_layout* out) try {
   uint64_t total = 0;
   compute_levels(m.desc, lv, &total);
   out->table_bytes_canonical = m.table_halfs * 2;
-  out->table_bytes_physical = m.phys.bytes;
+  out->table_bytes_physical = m.phys_bytes;
   out->kernel_features = m.dev.n_features;
   out->kernel_dense_levels = render_instance_dense_levels(m.dev);
   out->kernel_slots = 64;

@@ -1722,9 +1722,9 @@ hipError_t launch_march_multi(const MarchMultiParams& P, int n_views, int n_spp,
   return hipGetLastError();
 }
 
-// compiled instances of the render kernel: NDENSE = the field's count of leading dense levels when an instance for
-// exactly that count exists (5 / 3 for F = 4, 10 / 6 for F = 2: the BASELINE fields, instant-ngp's base.json, the test
-// fields) and its hashed levels share their hash constants; any other field runs the generic instance <F, 0>
+// compiled instances of the field-evaluating kernels (render, depth, mesh, field hook): NDENSE = the field's count of leading dense levels when an
+// instance for exactly that count exists (5 / 3 for F = 4, 10 / 6 for F = 2: api.FIELD_256 / FIELD_512 run <4,5> / <2,10>) and its hashed levels share their hash
+// constants; any other field -- util.SMALL (4 dense), SMALL_F2 (9), instant-ngp's base.json (F = 2, 5 dense), levels > 16 MiB -- runs <F, 0> (tests/instances.py)
 int render_instance_dense_levels(const FieldDev& fd) {
   const int n = fd.n_dense_levels;
   if (!fd.hash_shared) return 0;

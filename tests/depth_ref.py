@@ -65,8 +65,10 @@ def march_ray(lib, field, o, d, step_mode, S, min_T):
     return np.array([r, g, b, f32(1) - T, D], np.float32)
 
 
-def render(lib, field, cam, w, h, S=128, spp=1, min_T=1e-4, step_mode=0):
-    """-> (h, w, 5) float32: r, g, b, alpha (as OracleField.render) and z (premultiplied z-depth, engine units)"""
+def render(lib, field, cam, w, h, S=128, spp=1, min_T=1e-4, step_mode=0, pixel_stride=1):
+    """-> (h, w, 5) float32: r, g, b, alpha (as OracleField.render) and z (premultiplied z-depth, engine units).
+    pixel_stride n > 1: only the pixels whose row-major index is a multiple of n are computed (`strided` picks the same
+    ones out of an image); the others stay 0."""
     out = np.zeros((h, w, 5), np.float32)
     min_T = f32(min_T)
     o, d = np.zeros(3, np.float32), np.zeros(3, np.float32)
@@ -78,6 +80,8 @@ def render(lib, field, cam, w, h, S=128, spp=1, min_T=1e-4, step_mode=0):
         offs.append((ox.value, oy.value))
     for y in range(h):
         for x in range(w):
+            if (y * w + x) % pixel_stride:
+                continue
             acc = np.zeros(5, np.float32)
             for k in range(spp):
                 lib.orc_raygen(C.byref(cam), x, y, C.c_float(offs[k][0]), C.c_float(offs[k][1]), _p(o), _p(d))
@@ -86,3 +90,31 @@ def render(lib, field, cam, w, h, S=128, spp=1, min_T=1e-4, step_mode=0):
                 acc = (acc + px).astype(np.float32)
             out[y, x] = (acc * inv_spp).astype(np.float32)
     return out
+
+
+def strided(img, pixel_stride):
+    """(h, w, c) -> (n, c): the pixels `render(..., pixel_stride=)` computes"""
+    img = np.asarray(img)
+    return img.reshape(img.shape[0] * img.shape[1], -1)[::pixel_stride]
+
+
+# ---- what the GPU depth tests share (tests/test_gpu_depth.py, tests/test_gpu_instances.py)
+def both(ctx, slot, cs, opts, ids=None):
+    """render_depth and render of the same views -> rgba, depth, stats, plain rgba, plain stats"""
+    rgba, depth, st = ctx.render_depth(slot, cs, ids, opts)
+    plain, st0 = ctx.render(slot, cs, ids, opts)
+    return rgba.cpu().numpy(), depth.cpu().numpy(), st, plain.cpu().numpy(), st0
+
+
+def check_identity(rgba, st, plain, st0):
+    assert np.array_equal(rgba.view(np.uint32), plain.view(np.uint32))  # bit for bit
+    for k in ("rays", "samples_nominal", "samples_evaluated", "samples_live"):
+        assert getattr(st, k) == getattr(st0, k), k
+
+
+def reference(oracle, f, ocam, w, h, S, spp, min_T, mode, pixel_stride=1):
+    want = render(oracle.lib(), f, ocam, w, h, S, spp, min_T, mode, pixel_stride)
+    # self-check: the restatement's colour is the oracle's own render
+    img, _ = f.render(ocam, w, h, S, spp, min_T, step_mode=mode)
+    assert np.abs(strided(want, pixel_stride)[:, :4] - strided(img, pixel_stride)).max() <= 1e-6
+    return want

@@ -35,24 +35,7 @@ def cams(ctx, oracle):
     return cs, oracle.cameras_from_transforms(tms, util.FOV_X, W, H, scale, offset)
 
 
-def _both(ctx, slot, cs, opts, ids=None):
-    rgba, depth, st = ctx.render_depth(slot, cs, ids, opts)
-    plain, st0 = ctx.render(slot, cs, ids, opts)
-    return rgba.cpu().numpy(), depth.cpu().numpy(), st, plain.cpu().numpy(), st0
-
-
-def _check_identity(rgba, st, plain, st0):
-    assert np.array_equal(rgba.view(np.uint32), plain.view(np.uint32))  # bit for bit
-    for k in ("rays", "samples_nominal", "samples_evaluated", "samples_live"):
-        assert getattr(st, k) == getattr(st0, k), k
-
-
-def _ref(oracle, f, ocam, w, h, S, spp, min_T, mode):
-    want = depth_ref.render(oracle.lib(), f, ocam, w, h, S, spp, min_T, mode)
-    # self-check: the restatement's colour is the oracle's own render
-    img, _ = f.render(ocam, w, h, S, spp, min_T, step_mode=mode)
-    assert np.abs(want[..., :4] - img).max() <= 1e-6
-    return want
+_both, _check_identity, _ref = depth_ref.both, depth_ref.check_identity, depth_ref.reference
 
 
 CONFIGS = [(128, 1, 1e-4, 0), (37, 1, 1e-4, 0), (64, 2, 1e-4, 0), (0, 1, 1e-4, 1)]
@@ -146,25 +129,30 @@ def test_depth_known_answer_slab(ctx, mode):
     cs.close()
 
 
-def _policy_scene(ctx, oracle, slot):
-    ctx.synthetic_model(slot, api.field_desc(**util.SMALL), util.SEED_B)
+def _policy_scene(ctx, oracle, slot, kw=util.SMALL):
+    ctx.synthetic_model(slot, api.field_desc(**kw), util.SEED_B)
     tms, scale, offset = util.hemisphere_transforms(oracle, util.fibonacci_hemisphere(6))
     return ctx.cameras_from_matrices(tms, util.FOV_X, 96, 80, scale, offset)
 
 
-@pytest.mark.parametrize("env", [{"PRV_MERGE_MAX": "0"}, {"PRV_MERGE_MAX": "6", "PRV_POOL": "1"}, {"PRV_MERGE_MAX": "31", "PRV_POOL": "0"},
-                                 {"PRV_MERGE_MAX": "31", "PRV_POOL": "1"}, {"PRV_CELL_CACHE": "1"}, {"PRV_BLOCKS_PER_CU": "1"},
-                                 {"PRV_QUEUE_MB": "1"}], ids=lambda e: ",".join(f"{k}={v}" for k, v in e.items()))
-def test_depth_policy_invariance(ctx, oracle, monkeypatch, env):
+POLICY_ENVS = [{"PRV_MERGE_MAX": "0"}, {"PRV_MERGE_MAX": "6", "PRV_POOL": "1"}, {"PRV_MERGE_MAX": "31", "PRV_POOL": "0"},
+               {"PRV_MERGE_MAX": "31", "PRV_POOL": "1"}, {"PRV_CELL_CACHE": "1"}, {"PRV_BLOCKS_PER_CU": "1"}, {"PRV_QUEUE_MB": "1"}]
+_env_id = lambda e: ",".join(f"{k}={v}" for k, v in e.items())
+
+
+def _check_policy_invariance(ctx, oracle, monkeypatch, env, kw, instance):
+    no_pair = "PRV_NO_PAIR" in env
     for mode in (1, 0):
         opts = api.render_opts(96, 80, 0 if mode else 128, 1, 1e-4, step_mode=mode)
-        cs = _policy_scene(ctx, oracle, SLOT + 3)
+        cs = _policy_scene(ctx, oracle, SLOT + 3, kw)
+        assert ctx.model_layout(SLOT + 3)["kernel_dense_levels"] == instance
         want_rgba, want_z, _ = ctx.render_depth(SLOT + 3, cs, None, opts)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         c2 = api.Context(0)
         try:
-            cs2 = _policy_scene(c2, oracle, 0)
+            cs2 = _policy_scene(c2, oracle, 0, kw)
+            assert c2.model_layout(0)["kernel_dense_levels"] == (0 if no_pair else instance)
             rgba, z, _ = c2.render_depth(0, cs2, None, opts)
             assert np.array_equal(rgba.cpu().numpy().view(np.uint32), want_rgba.cpu().numpy().view(np.uint32))
             assert np.array_equal(z.cpu().numpy().view(np.uint32), want_z.cpu().numpy().view(np.uint32))
@@ -179,6 +167,23 @@ def test_depth_policy_invariance(ctx, oracle, monkeypatch, env):
         assert np.array_equal(z.cpu().numpy(), want_z.cpu().numpy()[[4, 1]])
         assert np.array_equal(rgba.cpu().numpy(), want_rgba.cpu().numpy()[[4, 1]])
         cs.close()
+
+
+@pytest.mark.parametrize("env", POLICY_ENVS, ids=_env_id)
+def test_depth_policy_invariance(ctx, oracle, monkeypatch, env):
+    """util.SMALL: the generic instance <4,0>"""
+    _check_policy_invariance(ctx, oracle, monkeypatch, env, util.SMALL, 0)
+
+
+@pytest.mark.parametrize("env", POLICY_ENVS + [{"PRV_NO_PAIR": "1"}], ids=_env_id)
+@pytest.mark.parametrize("which", ["F4_5", "F2_10"])
+def test_depth_policy_invariance_on_the_fast_instances(ctx, oracle, monkeypatch, env, which):
+    """the same on <4,5> and <2,10> (tests/instances.py), the instances the product's fields run, and the generic gather
+    (PRV_NO_PAIR=1: <F,0>) against them: identical bits"""
+    from tests import instances
+
+    e = instances.MATRIX[which]
+    _check_policy_invariance(ctx, oracle, monkeypatch, env, e.kw, e.instance)
 
 
 def test_depth_spp_reduce_and_views(ctx, oracle, field, cams):

@@ -272,20 +272,25 @@ def test_view_batches_do_not_change_anything(ctx, oracle, monkeypatch):
                                  {"PRV_BLOCKS_PER_CU": "1"}, {"PRV_BLOCKS_PER_CU": "6"},
                                  {"PRV_MERGE_MAX": "0"}, {"PRV_MERGE_MAX": "6", "PRV_POOL": "0"}, {"PRV_MERGE_MAX": "31", "PRV_BLOCKS_PER_CU": "2"},
                                  {"PRV_MERGE_MAX": "12", "PRV_POOL": "1"}, {"PRV_MERGE_MAX": "31", "PRV_POOL": "1", "PRV_BLOCKS_PER_CU": "1"}])
-@pytest.mark.parametrize("which", ["F4", "F2"])
+@pytest.mark.parametrize("which", ["F4", "F2", "F4_5", "F2_10"])
 @pytest.mark.parametrize("step_mode", ["fixed", "ngp"])
 def test_placement_and_layout_switches_change_speed_only(ctx, oracle, monkeypatch, env, which, step_mode):
     """the tuning switches of the render path (queue segments per XCD, which region a wave's rays go to -- the octant of the
     middle of their live span, round 6's default, or the block index --, the generic gather for every level, resident
     blocks per CU, tail merge and tail pool: rays change lanes mid-flight) decide where and in which order rays are
-    rendered -- never the arithmetic: images and counts are bit-identical to the defaults, in both stepping modes"""
-    kw = util.SMALL if which == "F4" else util.SMALL_F2
+    rendered -- never the arithmetic: images and counts are bit-identical to the defaults, in both stepping modes.
+    F4 / F2 (util.SMALL, SMALL_F2) run the generic instances <4,0> / <2,0> by default; F4_5 / F2_10 (tests/instances.py) the
+    fast ones <4,5> / <2,10>, for which PRV_NO_PAIR=1 is a different kernel instance and table layout"""
+    from tests import instances
+
+    kw, inst = {"F4": (util.SMALL, 0), "F2": (util.SMALL_F2, 0)}.get(which) or (instances.MATRIX[which].kw, instances.MATRIX[which].instance)
     d_p = api.field_desc(**kw)
     pts = util.fibonacci_hemisphere(5)
     tms, scale, offset = util.hemisphere_transforms(oracle, pts)
     w, h = 56, 44
     opts = api.render_opts(w, h, 96, 1, 1e-4, step_mode=api.L.STEP_NGP if step_mode == "ngp" else api.L.STEP_FIXED_S)
     ctx.synthetic_model(2, d_p, util.SEED_A)
+    assert ctx.model_layout(2)["kernel_dense_levels"] == inst
     cs = ctx.cameras_from_matrices(tms, util.FOV_X, w, h, scale, offset)
     want, st0 = ctx.render(2, cs, None, opts)
     feat0 = ctx.debug_encode(2, np.random.default_rng(1).random((300, 3)).astype(np.float32))
@@ -293,10 +298,11 @@ def test_placement_and_layout_switches_change_speed_only(ctx, oracle, monkeypatc
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     other = api.Context(0)
-    for k in env:
-        monkeypatch.delenv(k)
     try:
-        other.synthetic_model(2, d_p, util.SEED_A)
+        other.synthetic_model(2, d_p, util.SEED_A)  # PRV_NO_PAIR is read when a model is installed, the others at creation
+        for k in env:
+            monkeypatch.delenv(k)
+        assert other.model_layout(2)["kernel_dense_levels"] == (0 if "PRV_NO_PAIR" in env else inst)
         cs = other.cameras_from_matrices(tms, util.FOV_X, w, h, scale, offset)
         got, st1 = other.render(2, cs, None, opts)
         assert np.array_equal(got.cpu().numpy(), want.cpu().numpy()), env
