@@ -45,6 +45,9 @@ extern "C" {
 #define PRV_SCORE_ENSEMBLE_RGB_DENSITY 3 /* main.cpp:2099-2161 */
 #define PRV_SCORE_PSNR_COVERAGE 5        /* -PSNR (run.py:257-263, vs supplied images) + w * mean((1 - alpha)^2), the
                                             density term of main.cpp:2148; w = prv_set_coverage_weight */
+#define PRV_SCORE_RAY_ENTROPY 7          /* mean over the view's pixels of prv_render_entropy's H: one model, no reference
+                                            images.  This build's own (not in the reference), like 5; the ids mirror the
+                                            planner's method_of_IG values, where 6 stays unassigned */
 #define PRV_COVERAGE_WEIGHT_DEFAULT 1.0  /* the reference adds its density term with unit weight too (main.cpp:2147-2148) */
 
 #define PRV_MAX_MODELS 8  /* members of one ensemble (one scoring call) */
@@ -103,7 +106,7 @@ typedef struct prv_render_opts {
 typedef struct prv_score_record { /* 16 bytes: the unit of the multi-GPU all-gather */
   double score;                   /* ranking key: larger = chosen first; NaN ranks last */
   float psnr;                     /* dB (method 5), else 0 */
-  float coverage;                 /* mean opacity of the render (method 5), else 0 */
+  float coverage;                 /* mean opacity of the render (methods 5 and 7), else 0 */
 } prv_score_record;
 
 typedef struct prv_stats {
@@ -249,6 +252,22 @@ int prv_render_rgba8(prv_ctx* ctx, int model_slot, const prv_camset* cs, const i
  * out_rgba_dev: as prv_render (bit-identical to it), or NULL (rendered into a context scratch buffer). */
 int prv_render_depth(prv_ctx* ctx, int model_slot, const prv_camset* cs, const int* view_ids, int n_views,
                      const prv_render_opts* opts, float* out_rgba_dev, float* out_depth_dev, prv_stats* stats);
+/* The ray entropy of a view (this build's own: the engine has no such mode), from one model and no reference image.
+ * out_entropy_dev: n_views*h*w float32, bits.  Per ray (every spp sub-sample), over exactly the samples, weights and early
+ *   termination prv_render composites, under either stepping rule:
+ *     w_i = alpha_i T_i, the sample's colour weight (the colour kernel's bits);
+ *     T_end = the transmittance when the ray stops: after its last sample, or at the min_transmittance cut;
+ *     H = sum_i h(w_i) + h(T_end),  h(p) = p >= 2^-126 ? -p log2(p) : 0  (denormal p count as 0),
+ *   accumulated in depth order as H = fmaf(p, -log2 p, H), the escape term last.  The w_i and T_end sum to 1: H is the
+ *   entropy of "where does this ray end" over its samples plus "it escapes"; 0 for a ray that surely escapes or surely
+ *   stops at one sample, large where the field spreads the stop over many samples.  A ray that misses the box or has no
+ *   live sample gives exactly 0 (T_end = 1).  The pixel is the sum of its sub-samples in order, times 1/spp, as for depth.
+ *   H depends on the stepping rule's dt like any discretised entropy (halving dt splits every weight in two: up to one bit
+ *   more): values compare between the views of one call, not between stepping rules or sample counts.
+ * out_alpha_dev: n_views*h*w float32, the pixel's opacity 1 - T_end, bit-identical to prv_render's alpha channel; may be
+ *   NULL.  stats: as prv_render's for the same views.  No colour is evaluated: the density layers alone run. */
+int prv_render_entropy(prv_ctx* ctx, int model_slot, const prv_camset* cs, const int* view_ids, int n_views,
+                       const prv_render_opts* opts, float* out_entropy_dev, float* out_alpha_dev, prv_stats* stats);
 int prv_quantize_rgba8(prv_ctx* ctx, const float* rgba_dev, size_t n_pixels, const float bg[4],
                        uint8_t* out_rgba8_dev);
 
@@ -302,7 +321,10 @@ int prv_evaluate(prv_ctx* ctx, int model_slot, const prv_camset* cs, const int* 
 /* The whole scoring round of nbv_loop for one shard of views, on the device end to end:
  * render every view with every model slot listed, reduce to one record per view.
  *   methods 2,3: model_slots = the ensemble (main.cpp:2041-2043 + 2045-2094);
- *   method 5   : model_slots[0] vs gt_rgba_dev (n_views*h*w*4 float, same view order).
+ *   method 5   : model_slots[0] vs gt_rgba_dev (n_views*h*w*4 float, same view order);
+ *   method 7   : model_slots[0] alone (n_models == 1, gt_rgba_dev NULL): score = the mean over the view's pixels of
+ *                prv_render_entropy's H in fp64 (block partials summed in block order: deterministic), coverage = the mean
+ *                opacity, psnr = 0.  The march and the entropy kernel are the round's only render launches; no colour image.
  * records_host and/or records_dev (n_views records) receive the result; records_dev is
  * what a caller hands to its all-gather. */
 int prv_score_views(prv_ctx* ctx, int method, const int* model_slots, int n_models,
@@ -391,7 +413,7 @@ int prv_comm_barrier(prv_comm* comm);
 int prv_shard_views(int n_views, int rank, int world, int interleaved, int* ids_out, int* n_mine);
 /* the sharded scoring round: prv_score_views on this rank's shard of views [0, n_views_total) of `cs`, one all-gather,
  * records_host = all n_views_total records in view order on every rank.  gt_shard_dev (method 5): the reference images
- * of THIS rank's views, in shard order.  comm NULL = one rank.  stats: this rank's share. */
+ * of THIS rank's views, in shard order (method 7: NULL).  comm NULL = one rank.  stats: this rank's share. */
 int prv_score_views_sharded(prv_ctx* ctx, prv_comm* comm, int method, const int* model_slots, int n_models,
                             const prv_camset* cs, int n_views_total, int interleaved, const prv_render_opts* opts,
                             const float* gt_shard_dev, prv_score_record* records_host, prv_stats* stats);

@@ -20,6 +20,7 @@ PRV_E_INTERNAL = -6
 SCORE_ENSEMBLE_RGB = 2
 SCORE_ENSEMBLE_RGB_DENSITY = 3
 SCORE_PSNR_COVERAGE = 5
+SCORE_RAY_ENTROPY = 7
 STEP_FIXED_S = 0  # prv.h: samples_per_ray uniform samples between the AABB hits (BASELINE configs[1], [3])
 STEP_NGP = 1      # instant-ngp's rule, what run.py:304 renders with: dt = sqrt(3)/1024, every step tested, no cap
 NGP_MAX_STEPS = 1024
@@ -136,6 +137,7 @@ SIGNATURES = {
     "prv_render": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), _vp, _P(Stats)]),
     "prv_render_rgba8": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), _vp, _P(Stats)]),
     "prv_render_depth": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), _vp, _vp, _P(Stats)]),
+    "prv_render_entropy": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), _vp, _vp, _P(Stats)]),
     "prv_first_hit": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, C.c_float, _vp]),
     "prv_precept": (_i, [_vp, _i, _vp, _i, _vp, _P(Rs2Intrinsics), C.c_float, _vp]),
     "prv_quantize_rgba8": (_i, [_vp, _vp, C.c_size_t, _vp, _vp]),

@@ -310,6 +310,20 @@ class Context:
                                             _ptr(out_depth), C.byref(st) if want_stats else None))
         return out, out_depth, st
 
+    def render_entropy(self, slot, camset, view_ids, opts, out=None, out_alpha=None, want_stats=True):
+        """prv_render_entropy -> (entropy [n, h, w] float32 in bits, alpha [n, h, w] float32, stats).  entropy: per ray the
+        entropy of its compositing weights and the escape term (include/prv.h); alpha: `render`'s alpha channel, bit for
+        bit.  One model, no reference image, no colour evaluated."""
+        ids = self._ids(camset, view_ids)
+        if out is None:
+            out = self.torch.empty((len(ids), opts.height, opts.width), dtype=self.torch.float32, device=self.device)
+        if out_alpha is None:
+            out_alpha = self.torch.empty((len(ids), opts.height, opts.width), dtype=self.torch.float32, device=self.device)
+        st = L.Stats()
+        self._chk(self.lib.prv_render_entropy(self.handle, slot, camset.handle, _ptr(ids), len(ids), C.byref(opts), _ptr(out),
+                                              _ptr(out_alpha), C.byref(st) if want_stats else None))
+        return out, out_alpha, st
+
     def first_hit(self, slot, camset, view_ids, width, height, max_range=1e30):
         ids = self._ids(camset, view_ids)
         out = self.torch.empty((len(ids), height, width), dtype=self.torch.int32, device=self.device)
@@ -366,6 +380,8 @@ class Context:
 
     def score_views(self, method, slots, camset, view_ids, opts, gt=None, records_dev=None, to_host=True,
                     want_stats=False):
+        """prv_score_views: SCORE_ENSEMBLE_RGB / _RGB_DENSITY (slots = the ensemble), SCORE_PSNR_COVERAGE (one slot, gt = the
+        views' reference images) or SCORE_RAY_ENTROPY (one slot, no gt: the mean of `render_entropy` per view)"""
         ids = self._ids(camset, view_ids)
         slots = np.ascontiguousarray(slots, np.int32)
         rec = np.zeros(len(ids), RECORD_DTYPE) if to_host else None
@@ -592,7 +608,8 @@ class Comm:
         self.ctx._chk(self.ctx.lib.prv_comm_barrier(self.handle))
 
     def score_views(self, method, slots, camset, n_views, opts, gt_shard=None, interleaved=True, want_stats=False):
-        """the sharded scoring round -> (records[n_views] in view order, identical on every rank; local stats)"""
+        """the sharded scoring round -> (records[n_views] in view order, identical on every rank; local stats).  Methods as
+        Context.score_views; gt_shard: SCORE_PSNR_COVERAGE only"""
         slots = np.ascontiguousarray(slots, np.int32)
         rec = np.zeros(int(n_views), RECORD_DTYPE)
         st = L.Stats()

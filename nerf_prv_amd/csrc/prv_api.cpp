@@ -743,7 +743,9 @@ int timed(prv_ctx* c, std::vector<hipEvent_t>& events, Launch launch) {
 
 
 // which render_queue64 instance and relocation policy a launch gets (results are identical either way)
-void render_policy(prv_ctx* c, const Model& m, size_t npix, bool ngp, RenderParams& rp) {
+// has_cached_instance: the launch can run the corner-cache instance (the colour render; the entropy render has none, and the
+// relocation that pays only WITH the cache must not be switched on for it)
+void render_policy(prv_ctx* c, const Model& m, size_t npix, bool ngp, RenderParams& rp, bool has_cached_instance = true) {
   // Tail merge + the block's tail pool raise slot utilisation (0.77 -> 0.93) at the price of incoherent gathers from the
   // relocated rays.  That pays where the gathers of a fresh cohort are coherent to begin with and the table is cache
   // resident -- large images of the 256^3 field: launch -8 % -- and costs elsewhere: the 512^3 field is bound by random
@@ -758,7 +760,7 @@ void render_policy(prv_ctx* c, const Model& m, size_t npix, bool ngp, RenderPara
   // change skips its eight loads of that level.  Costs ~50 VGPRs (two waves per SIMD, which those images run with
   // anyway) and a few VALU per level; off for large images, whose launch is issue-bound, and for the F = 2 fields (six
   // hashed levels do not fit the registers).  Cell keys hold 10 bits per axis.  PRV_CELL_CACHE overrides.
-  const bool cached = (c->cell_cache >= 0 ? c->cell_cache != 0 : (ngp && !coherent)) && m.desc.finest_res <= 1023 &&
+  const bool cached = has_cached_instance && (c->cell_cache >= 0 ? c->cell_cache != 0 : (ngp && !coherent)) && m.desc.finest_res <= 1023 &&
                       m.desc.n_features == 4 && m.dev.hash_shared && m.dev.n_dense_levels == 5;
   rp.cell_cache = cached ? 1 : 0;
   // With the cache in place the small-image launch is no longer request-bound and fuller slots pay again: relocation on
@@ -794,9 +796,11 @@ RenderParams render_params(prv_ctx* c, const Model& m, const prv_render_opts* o,
 // The render of one batch of views into out_f32 (+ optional out_u8).  Views are dealt to
 // the queue in batches so the queue stays within queue_budget bytes.  out_depth (prv_render_depth): the views' depth images
 // as well, n_views * H * W floats, through the depth instances of the render kernel; null: the colour render alone.
+// out_entropy + out_alpha (prv_render_entropy, PRV_SCORE_RAY_ENTROPY; out_f32 and out_u8 null): no colour at all -- the march
+// and the entropy kernel, which writes these two planes of n_views * H * W floats.
 int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views,
                  const prv_render_opts* o, float* out_f32, uint8_t* out_u8, bool zero_stats, bool private_output = false,
-                 float* out_depth = nullptr) {
+                 float* out_depth = nullptr, float* out_entropy = nullptr, float* out_alpha = nullptr) {
   if (o->spp != 1 || out_u8 || out_depth) private_output = false; // sub-sample staging, byte and depth images are written in full
   const Model& m = c->models[slot];
   const int W = o->width, H = o->height, spp = o->spp;
@@ -821,7 +825,7 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
   const size_t slot_bytes = kRecordBytes + (ngp ? kExtBytes : 0); // NGP: every queue slot has its mask-extension slot
   size_t batch = std::max<size_t>(1, c->queue_budget / (npix * slot_bytes * (size_t)spp));
   batch = std::min<size_t>(batch, (size_t)n_views);
-  const size_t stage_px = out_depth ? 16 + 4 : 16; // staging bytes per sub-sample pixel: RGBA (+ depth)
+  const size_t stage_px = out_entropy ? 4 + 4 : out_depth ? 16 + 4 : 16; // staging bytes per sub-sample pixel: RGBA (+ depth), or entropy + opacity
   if (spp > 1) batch = std::min<size_t>(batch, std::max<size_t>(1, c->stage_budget / (npix * stage_px * (size_t)spp)));
   if (batch * npix * (size_t)spp >= (1ull << 32)) batch = ((1ull << 32) - 1) / (npix * (size_t)spp); // 32-bit pixel ids
   if (batch == 0) return fail(c, PRV_E_INVALID, "image x spp too large");
@@ -830,18 +834,27 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
   if (seg_cap_max * (size_t)L.n_seg >= (1ull << 32)) return fail(c, PRV_E_INVALID, "image x spp too large");
   if ((rc = ensure(c, c->queue, seg_cap_max * (size_t)L.n_seg * kRecordBytes)) != PRV_OK) return rc;
   if (ngp && (rc = ensure(c, c->queue_ext, seg_cap_max * (size_t)L.n_seg * kExtBytes)) != PRV_OK) return rc;
-  if (spp > 1 && (rc = ensure(c, c->stage, batch * npix * (size_t)spp * 16)) != PRV_OK) return rc;
-  if (spp > 1 && out_depth && (rc = ensure(c, c->stage_depth, batch * npix * (size_t)spp * 4)) != PRV_OK) return rc;
+  if (spp > 1 && (rc = ensure(c, c->stage, batch * npix * (size_t)spp * (out_entropy ? 4 : 16))) != PRV_OK) return rc;
+  if (spp > 1 && (out_depth || out_entropy) && (rc = ensure(c, c->stage_depth, batch * npix * (size_t)spp * 4)) != PRV_OK) return rc;
 
   const int n_blocks = render_blocks(c, m, npix);
   for (size_t b0 = 0; b0 < (size_t)n_views; b0 += batch) {
     const int nb = (int)std::min(batch, (size_t)n_views - b0);
-    float* dst_f32 = out_f32 + b0 * npix * 4;
+    float* dst_f32 = out_f32 ? out_f32 + b0 * npix * 4 : nullptr;
     uint32_t* dst_u8 = out_u8 ? (uint32_t*)out_u8 + b0 * npix : nullptr;
     float* dst_depth = out_depth ? out_depth + b0 * npix : nullptr;
     float* depth_target = spp > 1 ? (float*)c->stage_depth.p : dst_depth;
     // the march writes no depth: every pixel starts at 0, which is what a dead ray contributes
     if (out_depth) HIPCHK(c, hipMemsetAsync(depth_target, 0, (size_t)nb * npix * (size_t)spp * 4, c->stream));
+    // the entropy render's planes: H where the depth would go, the opacity where the colour would (sub-samples: their staging)
+    float* dst_entropy = out_entropy ? out_entropy + b0 * npix : nullptr;
+    float* dst_alpha = out_entropy ? out_alpha + b0 * npix : nullptr;
+    float* entropy_target = spp > 1 ? (float*)c->stage_depth.p : dst_entropy;
+    float* alpha_target = spp > 1 ? (float*)c->stage.p : dst_alpha;
+    if (out_entropy) { // nor does it write these: a dead ray's entropy and opacity are 0
+      HIPCHK(c, hipMemsetAsync(entropy_target, 0, (size_t)nb * npix * (size_t)spp * 4, c->stream));
+      HIPCHK(c, hipMemsetAsync(alpha_target, 0, (size_t)nb * npix * (size_t)spp * 4, c->stream));
+    }
     // one fill per batch: heads and counts, and with them the statistics when this call starts a new window
     HIPCHK(c, hipMemsetAsync(c->counters.p, 0, b0 == 0 && zero_stats ? kCountersBytes : kStatOffset, c->stream));
     MarchParams mp;
@@ -852,7 +865,7 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
     mp.queue = c->queue.p;
     mp.queue_ext = (uint4*)c->queue_ext.p;
     mp.queue_count = q_count;
-    mp.out_f32 = spp > 1 ? (float*)c->stage.p : dst_f32;
+    mp.out_f32 = out_entropy ? nullptr : spp > 1 ? (float*)c->stage.p : dst_f32;
     mp.out_u8 = spp > 1 ? nullptr : dst_u8;
     // A caller that consumes the image through the views' cull rectangles (prv_score_views, method 5: the image is a private
     // temporary of the round) gets only the tiles inside them launched and nothing written outside: most of an 800x800
@@ -877,6 +890,20 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
     }
     if ((rc = timed(c, c->ev_march, [&] { HIPCHK(c, launch_march(mp, nb, spp, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
     const RenderParams rp = render_params(c, m, o, L, mp.seg_cap, {mp.queue, mp.queue_ext, mp.queue_count, mp.out_f32, mp.out_u8}, q_head, stat);
+    if (out_entropy) {
+      RenderEntropyParams ep;
+      memset(&ep, 0, sizeof(ep));
+      ep.r = rp;
+      render_policy(c, m, npix, ngp, ep.r, false);
+      ep.out_entropy = entropy_target;
+      ep.out_alpha = alpha_target;
+      if ((rc = timed(c, c->ev_render, [&] { HIPCHK(c, launch_render_entropy(ep, n_blocks, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
+      if (spp > 1) {
+        HIPCHK(c, launch_spp_reduce_depth(entropy_target, (size_t)nb * npix, spp, dst_entropy, c->stream));
+        HIPCHK(c, launch_spp_reduce_depth(alpha_target, (size_t)nb * npix, spp, dst_alpha, c->stream));
+      }
+      continue;
+    }
     if (out_depth) {
       RenderDepthParams dp;
       memset(&dp, 0, sizeof(dp));
@@ -1605,6 +1632,23 @@ int prv_render_depth(prv_ctx* c, int slot, const prv_camset* cs, const int* view
   return fetch_stats(c, o, n_views, 1, st);
 } catch (...) { return caught(c); }
 
+int prv_render_entropy(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, const prv_render_opts* o,
+                       float* out_entropy, float* out_alpha, prv_stats* st) try {
+  if (!c) return PRV_E_INVALID;
+  int rc;
+  if ((rc = check_model(c, slot)) != PRV_OK || (rc = check_opts(c, o)) != PRV_OK) return rc;
+  if (!cs || n_views < 0 || (!out_entropy && n_views > 0)) return fail(c, PRV_E_INVALID, "bad camset / view count / entropy output");
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = check_device_ptr(c, out_entropy, "out_entropy_dev")) != PRV_OK) return rc;
+  if ((rc = check_device_ptr(c, out_alpha, "out_alpha_dev")) != PRV_OK) return rc;
+  if (!out_alpha && n_views > 0) { // the kernel writes the opacity anyway: into the context's scratch
+    if ((rc = ensure(c, c->img_f32, (size_t)n_views * o->width * o->height * 4)) != PRV_OK) return rc;
+    out_alpha = (float*)c->img_f32.p;
+  }
+  if ((rc = render_views(c, slot, cs, view_ids, n_views, o, nullptr, nullptr, true, false, nullptr, out_entropy, out_alpha)) != PRV_OK) return rc;
+  return fetch_stats(c, o, n_views, 1, st);
+} catch (...) { return caught(c); }
+
 int prv_first_hit(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, int W, int H,
                   float max_range, int32_t* out) try {
   if (!c) return PRV_E_INVALID;
@@ -1838,9 +1882,11 @@ int prv_score_views(prv_ctx* c, int method, const int* model_slots, int n_models
   if ((rc = check_opts(c, o)) != PRV_OK) return rc;
   if (!cs || !model_slots || n_views < 0) return fail(c, PRV_E_INVALID, "bad argument");
   const bool ens = method == PRV_SCORE_ENSEMBLE_RGB || method == PRV_SCORE_ENSEMBLE_RGB_DENSITY;
-  if (!ens && method != PRV_SCORE_PSNR_COVERAGE) return fail(c, PRV_E_INVALID, "unknown score method %d", method);
+  const bool entropy = method == PRV_SCORE_RAY_ENTROPY;
+  if (!ens && !entropy && method != PRV_SCORE_PSNR_COVERAGE) return fail(c, PRV_E_INVALID, "unknown score method %d", method);
   if (ens && (n_models < 1 || n_models > PRV_MAX_MODELS)) return fail(c, PRV_E_INVALID, "ensemble size %d", n_models);
-  if (!ens && (n_models != 1 || !gt)) return fail(c, PRV_E_INVALID, "method 5 needs one model and reference images");
+  if (entropy && (n_models != 1 || gt)) return fail(c, PRV_E_INVALID, "method 7 scores one model and takes no reference images");
+  if (!ens && !entropy && (n_models != 1 || !gt)) return fail(c, PRV_E_INVALID, "method 5 needs one model and reference images");
   for (int e = 0; e < n_models; e++)
     if ((rc = check_model(c, model_slots[e])) != PRV_OK) return rc;
   HIPCHK(c, hipSetDevice(c->device));
@@ -1848,8 +1894,20 @@ int prv_score_views(prv_ctx* c, int method, const int* model_slots, int n_models
   const size_t npix = (size_t)o->width * o->height;
   if ((rc = ensure(c, c->records, std::max<size_t>(16, (size_t)n_views * sizeof(prv_score_record)))) != PRV_OK) return rc;
   prv_score_record* rec = (prv_score_record*)c->records.p;
-  if ((rc = ensure(c, c->img_f32, std::max<size_t>(16, (size_t)n_views * npix * 16))) != PRV_OK) return rc;
-  if (ens) {
+  if ((rc = ensure(c, c->img_f32, std::max<size_t>(16, (size_t)n_views * npix * (entropy ? 8 : 16)))) != PRV_OK) return rc;
+  if (entropy) {
+    // no colour image: the march and the entropy kernel fill the view's entropy and opacity planes (zeroed first, so the tiles
+    // outside a view's cull rectangle need not be launched), one reduce sums both
+    float* hp = (float*)c->img_f32.p;
+    float* ap = hp + (size_t)n_views * npix;
+    if ((rc = render_views(c, model_slots[0], cs, view_ids, n_views, o, nullptr, nullptr, true, o->spp == 1, nullptr, hp, ap)) != PRV_OK) return rc;
+    if (n_views) {
+      const int nblk = score_blocks(npix);
+      if ((rc = ensure(c, c->partial, (size_t)n_views * nblk * 2 * sizeof(double))) != PRV_OK) return rc;
+      HIPCHK(c, launch_score_entropy(hp, ap, npix, n_views, nblk, (double*)c->partial.p, c->stream));
+      HIPCHK(c, launch_score_finalize((const double*)c->partial.p, n_views, nblk, PRV_SCORE_RAY_ENTROPY, npix, 0.0, rec, c->stream));
+    }
+  } else if (ens) {
     const uint8_t* imgs[PRV_MAX_MODELS];
     uint8_t* out8[PRV_MAX_MODELS];
     for (int e = 0; e < n_models; e++) {

@@ -11,6 +11,8 @@
 //       registers.  Front-to-back compositing is sequential per ray inside one lane (deterministic).  A group of 32
 //       slots refills as a whole cohort from the queue; thinned-out tails merge / pool (see the kernel).
 //       render_depth: the same kernel body with one more per-ray sum, the depth (prv_render_depth).
+//       render_entropy: the same queue machinery around the density layers alone; per ray the entropy of its compositing
+//       weights instead of a colour (prv_render_entropy).
 //  K_S* score kernels : per-view reductions in fp64, fixed reduction order (no float
 //       atomics), so rankings are reproducible bit for bit.
 //
@@ -188,7 +190,8 @@ struct MarchSink {
 // Wave-level compaction of the live rays into the queue + the record + the statistics + the dead ray's pixel.
 //   m[4]: the record's own 128-step chunk (FIXED_S: the whole mask; NGP: filled here from word(first_nz ...));
 //   word(k): NGP, mask word k of this ray (0 outside what the walk wrote)
-template <bool NGP, bool WORDS_READY = false, class PT, class WordFn>
+//   IMAGE: a dead ray's pixel is written (false: the launch has no colour image -- the entropy render, whose planes start zeroed)
+template <bool NGP, bool WORDS_READY = false, bool IMAGE = true, class PT, class WordFn>
 __device__ __forceinline__ void march_write(const PT& P, const MarchSink& Q, uint4 (*stage)[64 * kRecordWords], const MarchRay& r, bool live,
                                             unsigned long long b, uint32_t base, float dt, uint32_t m[4], int first_nz, int last_nz, WordFn word) {
   // b = the wave's ballot of live rays, base = where its records start in the queue (march_reserve)
@@ -230,10 +233,12 @@ __device__ __forceinline__ void march_write(const PT& P, const MarchSink& Q, uin
     const uint32_t n_words = (uint32_t)__popcll(b) * kRecordWords;
     for (uint32_t i = (uint32_t)lane; i < ((PRV_ABLATE & 256) ? 1u : n_words); i += 64u) dst[i] = st[i];
   }
-  if (!live && r.valid && !(PRV_ABLATE & 64)) {
-    // dead ray: contributes exactly zero to its pixel
-    reinterpret_cast<float4*>(Q.out_f32)[r.pix] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (P.last_pass && Q.out_u8) Q.out_u8[r.pix] = quantize_rgba8(0.f, 0.f, 0.f, 0.f, P.bg);
+  if constexpr (IMAGE) {
+    if (!live && r.valid && !(PRV_ABLATE & 64)) {
+      // dead ray: contributes exactly zero to its pixel
+      reinterpret_cast<float4*>(Q.out_f32)[r.pix] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (P.last_pass && Q.out_u8) Q.out_u8[r.pix] = quantize_rgba8(0.f, 0.f, 0.f, 0.f, P.bg);
+    }
   }
 }
 
@@ -282,7 +287,7 @@ __device__ __forceinline__ void march_count(const PT& P, uint32_t n_live) {
 // Wave-level compaction of the live rays into the queue + the record + the statistics + the dead ray's pixel.
 //   m[4]: the record's own 128-step chunk (FIXED_S: the whole mask; NGP: filled here from word(first_nz ...));
 //   word(k): NGP, mask word k of this ray (0 outside what the walk wrote)
-template <bool NGP, class PT, class WordFn>
+template <bool NGP, bool IMAGE = true, class PT, class WordFn>
 __device__ __forceinline__ void march_emit(const PT& P, const MarchSink& Q, uint4 (*stage)[64 * kRecordWords], const MarchRay& r, bool live,
                                            uint32_t n_live, float dt, uint32_t m[4], int first_nz, int last_nz, WordFn word) {
   // wave-level compaction: ballot + prefix popcount, one atomic per wave.  The queue is cut into n_seg regions of
@@ -312,12 +317,13 @@ __device__ __forceinline__ void march_emit(const PT& P, const MarchSink& Q, uint
     }
     base = __shfl(base, (int)__builtin_ctzll(b));
   }
-  march_write<NGP>(P, Q, stage, r, live, b, base, dt, m, first_nz, last_nz, word);
+  march_write<NGP, false, IMAGE>(P, Q, stage, r, live, b, base, dt, m, first_nz, last_nz, word);
   if (b != 0ull) march_count(P, n_live);
 }
 
-template <bool NGP>
-__global__ __launch_bounds__(256) void march_compact_kernel(MarchParams P) {
+// the body of march_compact_kernel (IMAGE) and of march_compact_noimage_kernel (the entropy render's march: no pixel is written)
+template <bool NGP, bool IMAGE>
+__device__ __forceinline__ void march_compact_body(MarchParams P) {
   __shared__ uint4 stage[4][64 * kRecordWords]; // a wave's live records, written out as ONE contiguous block
   __shared__ uint32_t mw[NGP ? 32 : 1][256];    // NGP: the lanes' mask words ([word][thread]: conflict-free columns)
   const uint32_t vi = blockIdx.y;
@@ -444,8 +450,18 @@ __global__ __launch_bounds__(256) void march_compact_kernel(MarchParams P) {
 #endif
   }
   const MarchSink Q{P.queue, P.queue_ext, (size_t)P.seg_cap * (size_t)P.n_seg, P.queue_count, P.out_f32, P.out_u8};
-  march_emit<NGP>(P, Q, stage, r, live, n_live, dt, m, first_nz, last_nz,
-                  [&](int k) { return (k >= k_lo && k < k_hi) ? mw[k][threadIdx.x] : 0u; });
+  march_emit<NGP, IMAGE>(P, Q, stage, r, live, n_live, dt, m, first_nz, last_nz,
+                         [&](int k) { return (k >= k_lo && k < k_hi) ? mw[k][threadIdx.x] : 0u; });
+}
+
+template <bool NGP>
+__global__ __launch_bounds__(256) void march_compact_kernel(MarchParams P) {
+  march_compact_body<NGP, true>(P);
+}
+
+template <bool NGP>
+__global__ __launch_bounds__(256) void march_compact_noimage_kernel(MarchParams P) {
+  march_compact_body<NGP, false>(P);
 }
 
 // ---- the ensemble's march in ONE launch (PRV_STEP_NGP; the reference trains E members and renders every candidate with
@@ -703,19 +719,31 @@ __device__ __forceinline__ void clock_stamp_end(unsigned long long* stat) {
 // every weight fragment.  A group refills when all its 32 slots are idle (whole-group lockstep).
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
 
-// The body of render_queue64_kernel and render_depth_kernel.  DEPTH: the ray also sums D = sum_i w_i t_i (w_i = the
+// h(p) = -p log2(p) added to H (prv_render_entropy): one v_log_f32 and one FMA; p below the smallest normal float counts as 0
+// (the hardware log takes no denormals), and so does p = 0
+__device__ __forceinline__ float entropy_add(float p, float H) { return p >= 1.17549435e-38f ? fmaf(p, -__builtin_amdgcn_logf(p), H) : H; }
+
+// The body of render_queue64_kernel, render_depth_kernel and render_entropy_kernel.
+// kRenderDepth: the ray also sums D = sum_i w_i t_i (w_i = the
 // sample's compositing weight, t_i its ray parameter) and writes z = D * dot(d, f) to PD->out_depth[pix] when it ends
 // (f = the view's normalised forward axis, column 2 of its c2w: z-depth along the optical axis, premultiplied by opacity);
-// the ray's dynamic state that tail merge and pool move between lanes gains a 7th word, D.  PD is unused without DEPTH.
-template <int F, int NDENSE, bool NGP, bool CACHE, bool DEPTH>
-__device__ __forceinline__ void render_queue64_body(RenderParams P, const RenderDepthParams* PD) {
-  constexpr int kMoveWords = DEPTH ? 7 : 6; // {record, next sample, T, r, g, b (, D)}
-  __shared__ half8 wl[kNumFrags * 64];
+// the ray's dynamic state that tail merge and pool move between lanes gains a 7th word, D.  PD is unused otherwise.
+// kRenderEntropy: the density layers alone (mlp_density2: the colour kernel's first 16 MFMAs in its order, so sigma, alpha
+// and T are its bits), no SH rows, no colour sums; the ray sums H = sum_i h(w_i) and adds h(T) when it ends, and writes H and
+// 1 - T to PE->out_entropy[pix] / PE->out_alpha[pix].  Its movable state is four words, {record, next sample, T, H}; only
+// the 8 density fragment sets are staged in LDS.  P.out_f32 / out_u8 are not touched.  PE is unused otherwise.
+enum : int { kRenderColour = 0, kRenderDepth = 1, kRenderEntropy = 2 };
+template <int F, int NDENSE, bool NGP, bool CACHE, int MODE>
+__device__ __forceinline__ void render_queue64_body(RenderParams P, const RenderDepthParams* PD, const RenderEntropyParams* PE = nullptr) {
+  constexpr bool DEPTH = MODE == kRenderDepth, ENTROPY = MODE == kRenderEntropy;
+  constexpr int kMoveWords = ENTROPY ? 4 : DEPTH ? 7 : 6; // {record, next sample, T, r, g, b (, D)} or {record, next sample, T, H}
+  constexpr int kFrags = ENTROPY ? 8 : kNumFrags;       // fragment sets staged in LDS: the density layers', or both MLPs'
+  __shared__ half8 wl[kFrags * 64];
   __shared__ uint32_t mv[4][32][kMoveWords]; // tail merges: {record, next sample, T, r, g, b (, D)} of the rays that change slots, per wave
   constexpr uint32_t kPoolCap = 192;
   __shared__ uint32_t pool[kPoolCap][kMoveWords]; // the block's tail pool: rays a group gave up, waiting for an idle slot of ANY of the block's waves
   __shared__ uint32_t pool_n, pool_lock;
-  for (int i = threadIdx.x; i < kNumFrags * 64; i += 256) wl[i] = P.field.frags64[i];
+  for (int i = threadIdx.x; i < kFrags * 64; i += 256) wl[i] = P.field.frags64[i];
   if (threadIdx.x == 0) {
     pool_n = 0u;
     pool_lock = 0u;
@@ -748,6 +776,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
   uint32_t cur = 0, m1 = 0, m2 = 0, m3 = 0, base = 0;
   float T = 1.f, cr = 0.f, cg = 0.f, cb = 0.f;
   float D = 0.f; // DEPTH: sum of w_i t_i so far
+  float Hs = 0.f; // ENTROPY: sum of h(w_i) so far
   half8 shA = {0, 0, 0, 0, 0, 0, 0, 0}, shB = {0, 0, 0, 0, 0, 0, 0, 0}; // SH rows [8g, 8g+8) of the rays in slots (r, A) and (r, B)
   bool drained = false;
   unsigned long long n_eval = 0ull, n_rounds = 0ull;
@@ -845,9 +874,13 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
           e[0] = rec_i;
           e[1] = base + (uint32_t)__builtin_ctz(cur); // the next sample to take
           e[2] = __float_as_uint(T);
-          e[3] = __float_as_uint(cr);
-          e[4] = __float_as_uint(cg);
-          e[5] = __float_as_uint(cb);
+          if constexpr (ENTROPY) {
+            e[3] = __float_as_uint(Hs);
+          } else {
+            e[3] = __float_as_uint(cr);
+            e[4] = __float_as_uint(cg);
+            e[5] = __float_as_uint(cb);
+          }
           if constexpr (DEPTH) e[6] = __float_as_uint(D);
           active = false;
         }
@@ -858,11 +891,18 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
         if (!((a_dst >> r) & 1u) && kth < n_src) { // BOTH lanes of the slot: the slot's SH rows go to both halves
           const uint32_t* e = slot[kth];
           const uint32_t ri = e[0];
-          const half8 sh = reinterpret_cast<const half8*>(queue + (size_t)ri * kRecordWords)[4 + g];
-          if (src == 0) shB = sh;
-          else shA = sh;
+          if constexpr (!ENTROPY) {
+            const half8 sh = reinterpret_cast<const half8*>(queue + (size_t)ri * kRecordWords)[4 + g];
+            if (src == 0) shB = sh;
+            else shA = sh;
+          }
           if (g != src) { // the destination lane itself takes the ray over
-            T = __uint_as_float(e[2]); cr = __uint_as_float(e[3]); cg = __uint_as_float(e[4]); cb = __uint_as_float(e[5]);
+            T = __uint_as_float(e[2]);
+            if constexpr (ENTROPY) {
+              Hs = __uint_as_float(e[3]);
+            } else {
+              cr = __uint_as_float(e[3]); cg = __uint_as_float(e[4]); cb = __uint_as_float(e[5]);
+            }
             if constexpr (DEPTH) D = __uint_as_float(e[6]);
             take_ray(ri, e[1]);
           }
@@ -890,9 +930,13 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
             e[0] = rec_i;
             e[1] = base + (uint32_t)__builtin_ctz(cur);
             e[2] = __float_as_uint(T);
-            e[3] = __float_as_uint(cr);
-            e[4] = __float_as_uint(cg);
-            e[5] = __float_as_uint(cb);
+            if constexpr (ENTROPY) {
+              e[3] = __float_as_uint(Hs);
+            } else {
+              e[3] = __float_as_uint(cr);
+              e[4] = __float_as_uint(cg);
+              e[5] = __float_as_uint(cb);
+            }
             if constexpr (DEPTH) e[6] = __float_as_uint(D);
             active = false;
           }
@@ -920,11 +964,18 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
         if (lane == 0) *(volatile uint32_t*)&pool_n = from;
         pool_release();
         if (mine) {
-          const half8 sh = reinterpret_cast<const half8*>(queue + (size_t)ent[0] * kRecordWords)[4 + g];
-          if (grp == 0) shA = sh;
-          else shB = sh;
+          if constexpr (!ENTROPY) {
+            const half8 sh = reinterpret_cast<const half8*>(queue + (size_t)ent[0] * kRecordWords)[4 + g];
+            if (grp == 0) shA = sh;
+            else shB = sh;
+          }
           if (g == grp) {
-            T = __uint_as_float(ent[2]); cr = __uint_as_float(ent[3]); cg = __uint_as_float(ent[4]); cb = __uint_as_float(ent[5]);
+            T = __uint_as_float(ent[2]);
+            if constexpr (ENTROPY) {
+              Hs = __uint_as_float(ent[3]);
+            } else {
+              cr = __uint_as_float(ent[3]); cg = __uint_as_float(ent[4]); cb = __uint_as_float(ent[5]);
+            }
             if constexpr (DEPTH) D = __uint_as_float(ent[6]);
             take_ray(ent[0], ent[1]);
           }
@@ -955,12 +1006,15 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
         }
         const uint32_t avail = min(32u, q_end - q_cur);
         if ((uint32_t)r < avail) { // both lane halves: the group's SH rows go to every lane, the ray itself to its own lane
-          const half8 sh = reinterpret_cast<const half8*>(queue + (size_t)(q_cur + (uint32_t)r) * kRecordWords)[4 + g];
-          if (grp == 0) shA = sh;
-          else shB = sh;
+          if constexpr (!ENTROPY) {
+            const half8 sh = reinterpret_cast<const half8*>(queue + (size_t)(q_cur + (uint32_t)r) * kRecordWords)[4 + g];
+            if (grp == 0) shA = sh;
+            else shB = sh;
+          }
           if (g == grp) {
             T = 1.f; cr = 0.f; cg = 0.f; cb = 0.f;
             if constexpr (DEPTH) D = 0.f;
+            if constexpr (ENTROPY) Hs = 0.f;
             take_ray(q_cur + (uint32_t)r, 0u);
           }
         }
@@ -1006,28 +1060,44 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
     swap_halves(f[0], f[1]); // f[0] = group A k-step 0, f[1] = group B k-step 0
     swap_halves(f[2], f[3]);
     const half8 fA[2] = {f[0], f[2]}, fB[2] = {f[1], f[3]};
-    const MlpOut2 mo = mlp_forward2(wl, lane, fA, fB, shA, shB);
+    MlpOut2 mo;
+    if constexpr (ENTROPY) mlp_density2(wl, lane, fA, fB, mo.densA, mo.densB);
+    else mo = mlp_forward2(wl, lane, fA, fB, shA, shB);
     // the lane's own sample: group A's results sit in lane half 0 (rows 0..2 = registers 0..2), group B's copies in the
     // padding rows 20..22 = lane half 1, registers 8..10
     const float dens = g ? mo.densB[8] : mo.densA[0];
-    const float lr = g ? mo.rgbB[8] : mo.rgbA[0], lg = g ? mo.rgbB[9] : mo.rgbA[1], lb = g ? mo.rgbB[10] : mo.rgbA[2];
+    float lr = 0.f, lg = 0.f, lb = 0.f;
+    if constexpr (!ENTROPY) {
+      lr = g ? mo.rgbB[8] : mo.rgbA[0];
+      lg = g ? mo.rgbB[9] : mo.rgbA[1];
+      lb = g ? mo.rgbB[10] : mo.rgbA[2];
+    }
 
     bool done = false;
     if (active) {
       const float sigma = fast_exp(dens + P.field.density_bias);
       const float alpha = 1.0f - fast_exp(-(sigma * dt));
       const float wgt = alpha * T;
-      cr = fmaf(wgt, fast_sigmoid(lr), cr);
-      cg = fmaf(wgt, fast_sigmoid(lg), cg);
-      cb = fmaf(wgt, fast_sigmoid(lb), cb);
+      if constexpr (ENTROPY) {
+        Hs = entropy_add(wgt, Hs);
+      } else {
+        cr = fmaf(wgt, fast_sigmoid(lr), cr);
+        cg = fmaf(wgt, fast_sigmoid(lg), cg);
+        cb = fmaf(wgt, fast_sigmoid(lb), cb);
+      }
       if constexpr (DEPTH) D = fmaf(wgt, ts, D);
       T = T * (1.0f - alpha);
       done = last || T < P.min_T;
     }
     if (done) {
-      const float4 v = make_float4(cr, cg, cb, 1.0f - T);
-      reinterpret_cast<float4*>(P.out_f32)[pix] = v;
-      if (P.last_pass && P.out_u8) P.out_u8[pix] = quantize_rgba8(v.x, v.y, v.z, v.w, P.bg);
+      if constexpr (ENTROPY) {
+        PE->out_entropy[pix] = entropy_add(T, Hs); // + h(T_end): the ray escapes with what is left
+        PE->out_alpha[pix] = 1.0f - T;
+      } else {
+        const float4 v = make_float4(cr, cg, cb, 1.0f - T);
+        reinterpret_cast<float4*>(P.out_f32)[pix] = v;
+        if (P.last_pass && P.out_u8) P.out_u8[pix] = quantize_rgba8(v.x, v.y, v.z, v.w, P.bg);
+      }
       if constexpr (DEPTH) {
         // image pix / npix of the launch is a sub-sample of view (pix / npix) % nb
         const CamDev& cam = PD->cams[PD->view_ids[(pix / PD->npix) % PD->nb]];
@@ -1051,7 +1121,7 @@ __global__ __launch_bounds__(256)
 // they took 172 since the octant regions of round 6 -- two waves -- and three are 1.7-2.5 % faster (r06ay); the all-hashed ones would spill 50-80
 __attribute__((amdgpu_waves_per_eu(CACHE ? 2 : NDENSE == 0 ? 1 : 3)))
 void render_queue64_kernel(RenderParams P) {
-  render_queue64_body<F, NDENSE, NGP, CACHE, false>(P, nullptr);
+  render_queue64_body<F, NDENSE, NGP, CACHE, kRenderColour>(P, nullptr);
 }
 
 // prv_render_depth: the render with the depth sum (render_queue64_body, DEPTH), for the (F, NDENSE) set of the colour
@@ -1060,7 +1130,18 @@ void render_queue64_kernel(RenderParams P) {
 template <int F, int NDENSE, bool NGP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NDENSE == 0 ? 1 : 3)))
 void render_depth_kernel(RenderDepthParams P) {
-  render_queue64_body<F, NDENSE, NGP, false, true>(P.r, &P);
+  render_queue64_body<F, NDENSE, NGP, false, kRenderDepth>(P.r, &P);
+}
+
+// prv_render_entropy: the density-only render (render_queue64_body, kRenderEntropy), for the (F, NDENSE) set of the colour
+// instances; no corner-cache instance.  Waves per SIMD as the colour instances ask for.  Without the colour MLP's
+// accumulators, SH rows and colour sums the dense-level instances take 122-130 registers (colour: 160-168; three waves, the
+// F = 2 ones under the engine's rule four), the all-hashed ones 183-218 (two waves), none spills a VGPR
+// (scripts/kernel_resources.py prv_kernels.hip render_entropy)
+template <int F, int NDENSE, bool NGP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NDENSE == 0 ? 1 : 3)))
+void render_entropy_kernel(RenderEntropyParams P) {
+  render_queue64_body<F, NDENSE, NGP, false, kRenderEntropy>(P.r, nullptr, &P);
 }
 
 
@@ -1358,6 +1439,27 @@ __global__ __launch_bounds__(256) void score_psnr_kernel(PsnrParams P) {
   }
 }
 
+// PRV_SCORE_RAY_ENTROPY: the sums of a view's entropy and opacity images (render_entropy_kernel's, dead pixels 0), two
+// partial sums per block
+__global__ __launch_bounds__(256) void score_entropy_kernel(const float* __restrict__ entropy, const float* __restrict__ alpha,
+                                                            size_t npix, double* __restrict__ partial) {
+  __shared__ double sm[4];
+  const int v = blockIdx.y;
+  const float* hv = entropy + (size_t)v * npix;
+  const float* av = alpha + (size_t)v * npix;
+  double sh = 0.0, sa = 0.0;
+  for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < npix; p += (size_t)gridDim.x * 256) {
+    sh += (double)hv[p];
+    sa += (double)av[p];
+  }
+  const double s0 = block_reduce_sum(sh, sm);
+  const double s1 = block_reduce_sum(sa, sm);
+  if (threadIdx.x == 0) {
+    partial[((size_t)v * gridDim.x + blockIdx.x) * 2 + 0] = s0;
+    partial[((size_t)v * gridDim.x + blockIdx.x) * 2 + 1] = s1;
+  }
+}
+
 // ---- SSIM of run.py:260 (recipe assumed from upstream common.py; see oracle orc_ssim)
 __device__ __forceinline__ float ssim_lum(const float4 p, const float bg[4]) {
   const float rem = 1.0f - p.w;
@@ -1460,6 +1562,14 @@ __global__ void score_finalize_kernel(const double* __restrict__ partial, int n_
     out.score = -psnr + coverage_weight * (unc / (double)pixels_per_view);
     out.psnr = (float)psnr;
     out.coverage = (float)(cov / (double)pixels_per_view);
+  } else if (method == PRV_SCORE_RAY_ENTROPY) {
+    double sh = 0.0, sa = 0.0;
+    for (int b = 0; b < n_blocks; b++) {
+      sh += partial[((size_t)v * n_blocks + b) * 2 + 0];
+      sa += partial[((size_t)v * n_blocks + b) * 2 + 1];
+    }
+    out.score = sh / (double)pixels_per_view; // mean ray entropy, bits: the most uncertain view first
+    out.coverage = (float)(sa / (double)pixels_per_view);
   } else {
     double s = 0.0;
     for (int b = 0; b < n_blocks; b++) s += partial[(size_t)v * n_blocks + b];
@@ -1700,6 +1810,11 @@ hipError_t launch_spp_reduce_depth(const float* stage, size_t n_pixels, int spp,
 hipError_t launch_march(const MarchParams& P, int n_views, int n_spp, hipStream_t s) {
   dim3 grid((unsigned)(P.live_grid ? P.live_tiles_max : P.tiles_x * P.tiles_y), (unsigned)n_views, (unsigned)(P.spp_inner_log2 > 0 ? 1 : n_spp));
   if (grid.x == 0) return hipSuccess; // no view of the batch can see the object
+  if (!P.out_f32) { // the entropy render: no colour image, dead rays write nothing
+    if (P.step_mode == PRV_STEP_NGP) hipLaunchKernelGGL(march_compact_noimage_kernel<true>, grid, dim3(256), 0, s, P);
+    else hipLaunchKernelGGL(march_compact_noimage_kernel<false>, grid, dim3(256), 0, s, P);
+    return hipGetLastError();
+  }
   if (P.step_mode == PRV_STEP_NGP) hipLaunchKernelGGL(march_compact_kernel<true>, grid, dim3(256), 0, s, P);
   else hipLaunchKernelGGL(march_compact_kernel<false>, grid, dim3(256), 0, s, P);
   return hipGetLastError();
@@ -1776,6 +1891,32 @@ static void launch_render_depth_mode(const RenderDepthParams& P, int n_blocks, h
 hipError_t launch_render_depth(const RenderDepthParams& P, int n_blocks, hipStream_t s) {
   if (P.r.step_mode == PRV_STEP_NGP) launch_render_depth_mode<true>(P, n_blocks, s);
   else launch_render_depth_mode<false>(P, n_blocks, s);
+  return hipGetLastError();
+}
+
+template <bool NGP>
+static void launch_render_entropy_mode(const RenderEntropyParams& P, int n_blocks, hipStream_t s) {
+  const int nd = render_instance_dense_levels(P.r.field); // (no cached entropy instance either)
+  if (P.r.field.n_features == 4) {
+    if (nd == 5) hipLaunchKernelGGL((render_entropy_kernel<4, 5, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
+    else if (nd == 3) hipLaunchKernelGGL((render_entropy_kernel<4, 3, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
+    else hipLaunchKernelGGL((render_entropy_kernel<4, 0, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
+  } else {
+    if (nd == 10) hipLaunchKernelGGL((render_entropy_kernel<2, 10, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
+    else if (nd == 6) hipLaunchKernelGGL((render_entropy_kernel<2, 6, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
+    else hipLaunchKernelGGL((render_entropy_kernel<2, 0, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
+  }
+}
+
+hipError_t launch_render_entropy(const RenderEntropyParams& P, int n_blocks, hipStream_t s) {
+  if (P.r.step_mode == PRV_STEP_NGP) launch_render_entropy_mode<true>(P, n_blocks, s);
+  else launch_render_entropy_mode<false>(P, n_blocks, s);
+  return hipGetLastError();
+}
+
+hipError_t launch_score_entropy(const float* entropy, const float* alpha, size_t npix, int n_views, int n_blocks, double* partial,
+                                hipStream_t s) {
+  hipLaunchKernelGGL(score_entropy_kernel, dim3((unsigned)n_blocks, (unsigned)n_views), dim3(256), 0, s, entropy, alpha, npix, partial);
   return hipGetLastError();
 }
 

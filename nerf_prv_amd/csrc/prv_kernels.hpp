@@ -116,6 +116,14 @@ struct RenderDepthParams {
   uint32_t nb;          // views in the launch
 };
 
+// the entropy render (prv_render_entropy, render_entropy_kernel): the colour launch's queue, field and policy (its images are
+// not touched) and the two planes a ray writes when it ends; both start zeroed, which is what a dead ray contributes
+struct RenderEntropyParams {
+  RenderParams r;
+  float* out_entropy; // one float per pixel of the launch's images: H, bits
+  float* out_alpha;   // 1 - T_end
+};
+
 struct EnsembleParams {
   const uint32_t* imgs[PRV_MAX_MODELS];
   int E;
@@ -145,6 +153,9 @@ hipError_t launch_spp_reduce(const float* stage, size_t n_pixels, int spp, const
 hipError_t launch_render(const RenderParams& P, int n_blocks, hipStream_t s);
 hipError_t launch_render_depth(const RenderDepthParams& P, int n_blocks, hipStream_t s);
 hipError_t launch_spp_reduce_depth(const float* stage, size_t n_pixels, int spp, float* out, hipStream_t s);
+hipError_t launch_render_entropy(const RenderEntropyParams& P, int n_blocks, hipStream_t s);
+hipError_t launch_score_entropy(const float* entropy, const float* alpha, size_t npix, int n_views, int n_blocks, double* partial,
+                                hipStream_t s);
 int render_instance_dense_levels(const FieldDev& fd); // NDENSE of the render_queue64_kernel<F, NDENSE> instance launch_render picks
 struct PreceptPose {
   double w2c[16], c2w[16];

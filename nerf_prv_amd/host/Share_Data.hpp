@@ -16,8 +16,9 @@
 
 namespace prvhost {
 
-// method_of_IG values (Share_Data.hpp:198-202) + the single-model score of this build
-enum { RandomIterative = 0, RandomOneshot = 1, EnsembleRGB = 2, EnsembleRGBDensity = 3, PVBCoverage = 4, PSNRCoverage = 5 };
+// method_of_IG values (Share_Data.hpp:198-202) + the single-model scores of this build: 5 (against reference images) and
+// 7 (ray entropy: no ground truth; 6 is unassigned)
+enum { RandomIterative = 0, RandomOneshot = 1, EnsembleRGB = 2, EnsembleRGBDensity = 3, PVBCoverage = 4, PSNRCoverage = 5, RayEntropy = 7 };
 
 struct rs2_intrinsics { // Share_Data.hpp:79-89 (float fields, like librealsense)
   int width = 0, height = 0;

@@ -62,7 +62,10 @@ struct HipScorer {
   bool dump_records = false; // view_planning sets it (yaml dump_scores: 1, or PRV_PLANNER_DUMP_RECORDS in the environment)
   int train_patch_w = 0, train_patch_h = 0; // yaml train_patch_w / train_patch_h: prv_train_opts.patch_w / patch_h (0: the library default, single pixels)
   int train_step_mode = -1; // yaml train_step_mode: prv_train_opts.step_mode (-1: the library default = the engine's marcher; 0: 128 uniform samples per ray, rounds 1-5)
+  bool train_deterministic = false; // yaml train_deterministic: 1 -> prv_train_opts.deterministic (bit-reproducible members: tests)
+  bool save_members = false;        // yaml save_members: 1 -> <save_path>/members/<iteration>/member_<e>.prvf, the fields an iteration scored with
   void apply_train_opts(prv_train_opts& to) const {
+    if (train_deterministic) to.deterministic = 1;
     if (train_step_mode == PRV_STEP_FIXED_S) {
       to.step_mode = PRV_STEP_FIXED_S;
       to.n_samples = 128;
@@ -441,6 +444,15 @@ struct HipScorer {
       const int trc = train_members(scene_json);
       if (trc != PRV_OK) return trc;
     }
+    if (save_members) {
+      const std::string dir = sd->save_path + "/members/" + std::to_string(iteration);
+      sd->access_directory(dir);
+      for (int e = 0; e < n_members; e++)
+        if (prv_model_save_file(ctx, slot_of(e), (dir + "/member_" + std::to_string(e) + ".prvf").c_str()) != PRV_OK) {
+          std::cerr << "prv: " << prv_last_error(ctx) << std::endl;
+          return -26;
+        }
+    }
     const bool timing = getenv("PRV_PLANNER_TIMING") != nullptr; // dev: where an iteration's seconds go
     const double t_round = now_seconds();
     prv_camset* cams = nullptr;
@@ -472,7 +484,7 @@ struct HipScorer {
       o.background[3] = 0.f;
       rc = prv_score_views_sharded(ctx, comm, PRV_SCORE_PSNR_COVERAGE, slots.data(), 1, cams, n, 1, &o, gt_sel, rec.data(), nullptr);
       prv_free(ctx, gt_sel);
-    } else {
+    } else { // the ensembles, and RayEntropy (= PRV_SCORE_RAY_ENTROPY): one member, no reference images
       rc = prv_score_views_sharded(ctx, comm, method, slots.data(), n_members, cams, n, 1, &o, nullptr, rec.data(), nullptr);
       if (rc == PRV_OK && save_renders) { // <save_path>/render/<it>/ensemble_<e>/rgbaClip_<view id>.png, the files :2047 reads
         uint8_t* dev = nullptr;
@@ -554,7 +566,7 @@ int PlanningJob::setup(prv_ctx* ctx_, const std::string& cfg, const std::string&
   ctx = ctx_;
   if (!NBV_Net_Labeler::method_in_scope(method)) { // before any directory, model or training: methods 1 / 4 are the PRVNet pipeline's
     std::cerr << "method_of_IG " << method << " is not built: this planner runs methods 0 (RandomIterative), 2 (EnsembleRGB), 3 "
-                 "(EnsembleRGBDensity) and 5 (PSNRCoverage); 1 (RandomOneshot) and 4 (PVBCoverage) need the reference's PRVNet server" << std::endl;
+                 "(EnsembleRGBDensity), 5 (PSNRCoverage) and 7 (RayEntropy); 1 (RandomOneshot) and 4 (PVBCoverage) need the reference's PRVNet server" << std::endl;
     return -10;
   }
   sd = std::make_shared<Share_Data>(cfg, name, -1, -1, method); // main.cpp:3876
@@ -609,6 +621,7 @@ int PlanningJob::setup(prv_ctx* ctx_, const std::string& cfg, const std::string&
   scorer.slot_base = slot_base;
   scorer.pair_base = pair_base;
   scorer.save_renders = fs.has("save_renders") && fs.num("save_renders") > 0;
+  scorer.save_members = fs.has("save_members") && fs.num("save_members") > 0;
   if (train_steps > 0) { // members are trained from scratch every iteration
     const int rc = configure_training(ctx, fs, desc, train_steps, scorer);
     if (rc != PRV_OK) return rc;
@@ -813,6 +826,7 @@ int configure_training(prv_ctx* ctx, const FileStorage& fs, const prv_field_desc
   scorer.train_desc.density_bias = fs.has("train_density_bias") ? (float)fs.num("train_density_bias") : 0.0f;
   scorer.train_desc.table_amp = 1e-4f;
   if (fs.has("train_seed")) scorer.train_seed = (uint64_t)fs.num("train_seed");
+  scorer.train_deterministic = fs.has("train_deterministic") && fs.num("train_deterministic") > 0;
   scorer.images_from_files = fs.has("train_images") && fs.str("train_images") == "files";
   return PRV_OK;
 }

@@ -278,10 +278,10 @@ public:
   // Methods 1 (RandomOneshot, main.cpp:1981-2037) and 4 (PVBCoverage, :2163-2242: PRVNet's view budget) never render and
   // are outside this build's scope: refused BEFORE the loop writes anything, with a message.
   static bool method_in_scope(int method) {
-    return method == RandomIterative || method == EnsembleRGB || method == EnsembleRGBDensity || method == PSNRCoverage;
+    return method == RandomIterative || method == EnsembleRGB || method == EnsembleRGBDensity || method == PSNRCoverage || method == RayEntropy;
   }
 
-  // main.cpp:1718-2277 for methods 0, 2, 3 (and 5, this build's single-model score); chosen views in `chosen_nbvs`.
+  // main.cpp:1718-2277 for methods 0, 2, 3 (and 5 and 7, this build's single-model scores); chosen views in `chosen_nbvs`.
   // The loop is three resumable pieces -- nbv_begin (everything before the reference's `while (true)`), nbv_prepare (an
   // iteration's json / render_json and the termination test, :1885-1966) and nbv_decide (score, pick, movement cost,
   // :1969-2264) -- so that a shell can walk SEVERAL objects' loops in lockstep (prv_planner `shard: members`: the
@@ -310,8 +310,9 @@ public:
     if (first_view_id == -1) first_view_id = 0; // :1725-1728
     Share_Data& sd = *share_data;
     if (!method_in_scope(sd.method_of_IG)) {
-      std::cerr << "nbv_loop: method_of_IG " << sd.method_of_IG << " is not built (RandomOneshot = 1 and PVBCoverage = 4 belong to the "
-                   "reference's PRVNet pipeline, outside this build's scope); nothing was written" << std::endl;
+      std::cerr << "nbv_loop: method_of_IG " << sd.method_of_IG << " is not built: the loop runs 0, 2, 3, 5 (PSNRCoverage) and 7 (RayEntropy); "
+                   "RandomOneshot = 1 and PVBCoverage = 4 belong to the reference's PRVNet pipeline, outside this build's scope; "
+                   "nothing was written" << std::endl;
       return -10;
     }
     { // :1735-1747: the methods run with the view budget a method-4 run of the REFERENCE left behind, when there is one
@@ -401,9 +402,11 @@ public:
       }
       case EnsembleRGB:
       case EnsembleRGBDensity:
-      case PSNRCoverage: { // :2039-2161: score every unchosen view, keep the arg-max
+      case PSNRCoverage:
+      case RayEntropy: { // :2039-2161: score every unchosen view, keep the arg-max
         std::vector<double> scores(candidates.size(), 0.0);
-        if (sd.score_from_pngs && sd.method_of_IG != PSNRCoverage) {
+        // (the single-model scores are device reductions with no PNG form: `score_path: png` does not apply to them)
+        if (sd.score_from_pngs && sd.method_of_IG != PSNRCoverage && sd.method_of_IG != RayEntropy) {
           // the reference's data flow, call for call: one engine run per member (:2041-2043, :2101-2103), then the PNGs
           // (no train_time/<it>.txt here: the reference writes it for ensemble_id == -1 only, :1707-1711)
           for (int ensemble_id = 0; ensemble_id < sd.ensemble_num; ensemble_id++) {

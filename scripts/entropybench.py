@@ -1,0 +1,58 @@
+"""Entropy render timings (dev tool, not bench.py): prv_render_entropy against prv_render of the same views -- the render
+launches' milliseconds from HIP events (prv_profile_begin / end) and the ratio -- on the BASELINE.md section 6 scene (FIELD_256,
+table U(-0.1, 0.1), no density bias; 64 views, 800x800, 128 samples per ray) and on a scoring round of the reference's size
+(540 candidates, 80x45, 16 sub-samples, the engine's stepping rule, min_T 0.01).
+
+    python scripts/entropybench.py [--reps 5] [--json out.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--json", default="")
+args = ap.parse_args()
+
+import torch
+
+from nerf_prv_amd import api, planner
+
+ctx = api.Context(0)
+fov_x = 2.0 * np.arctan(0.5 * 1280 / 915.60668945312500)
+ctx.synthetic_model(0, api.L.FieldDesc(**dict(api.FIELD_256, table_amp=0.1, density_bias=0.0)), 0x5EED0001)
+cases = {"section6_64x800x800_S128": (64, 800, 800, api.render_opts(800, 800, 128, 1, 1e-4)),
+         "round_540x80x45_spp16_ngp": (540, 80, 45, api.engine_render_opts(80, 45, 0, 16, 0.01))}
+rows = []
+for name, (n, w, h, opts) in cases.items():
+    tms, scale, offset = planner.hemisphere_transforms(planner.hemisphere_generate(n), 0.3, 0.1, [1e-10] * 3)
+    cams = ctx.cameras_from_matrices(tms, fov_x, w, h, scale, offset)
+    rgba = torch.empty((n, h, w, 4), dtype=torch.float32, device=ctx.device)
+    ent = torch.empty((n, h, w), dtype=torch.float32, device=ctx.device)
+    alpha = torch.empty((n, h, w), dtype=torch.float32, device=ctx.device)
+    runs = {"colour": lambda: ctx.render(0, cams, None, opts, out=rgba, want_stats=False),
+            "entropy": lambda: ctx.render_entropy(0, cams, None, opts, out=ent, out_alpha=alpha, want_stats=False)}
+    ms = {k: [] for k in runs}
+    for r in range(args.reps + 1):  # the first round is a warm-up
+        for k, fn in runs.items():  # interleaved, so clock drift hits both alike
+            ctx.profile_begin()
+            fn()
+            torch.cuda.synchronize()
+            prof = ctx.profile_end()
+            if r:
+                ms[k].append(prof["render_ms"])
+    _, _, st = ctx.render_entropy(0, cams, None, opts, out=ent, out_alpha=alpha)
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    row = dict(case=name, samples_evaluated=st.samples_evaluated, render_ms_median=med, render_ms_best={k: min(v) for k, v in ms.items()},
+               render_ms_all=ms, entropy_over_colour=med["entropy"] / med["colour"], mean_entropy_bits=float(ent.double().mean()))
+    rows.append(row)
+    print(json.dumps(row), flush=True)
+    cams.close()
+if args.json:
+    with open(args.json, "w") as fh:
+        json.dump(rows, fh, indent=1)
+ctx.close()
