@@ -384,6 +384,82 @@ int prv_mesh_write_file(const char* path, uint64_t n_vertices, const float* xyz,
                         uint64_t n_triangles, const uint32_t* tri, double scale, const double offset[3]);
 void prv_mesh_destroy(prv_mesh* m);
 
+/* ---- geometric evaluation: surface samples, nearest neighbours, Chamfer ----- */
+/* replaces: nothing in the reference -- it judges a reconstruction through images only (run.py:257-272).  This build's
+ * own: how close the reconstructed surface is to the real one, and how much of it is covered.
+ *
+ * prv_mesh_sample: n points on the mesh's surface, area-weighted, in the engine frame.  A pure function of (mesh, n, seed):
+ *   two calls return identical bytes.  out_xyz_dev n*3 float32, out_tri_dev n triangle ids (may be NULL); n <= 2^31.
+ *   Weights: a triangle's area in fp64 from its fp32 vertices -- e1 = b - a, e2 = c - a, c = e1 x e2 (each component
+ *     y*z' - z*y' etc.), area = 0.5 * sqrt((cx*cx + cy*cy) + cz*cz) -- quantised to the integer w = floor(area * 2^40)
+ *     (0 if that is below 1, not finite or >= 2^62): a res-256 cell's triangle (area ~ 2^-17) keeps 23 bits, a total of
+ *     2^22 unit areas stays below 2^62.
+ *   Scan: the weights are exclusive-scanned in integers (the mesh extraction's scan): no floating-point prefix sum, no
+ *     order dependence.  W = their sum.
+ *   Choice: sample k is stratified: its target lies in stratum k = [floor(k W / n), floor((k+1) W / n)) of length len, at
+ *     offset floor(len * u48 / 2^48), u48 = (r0 << 24) | r1 from two 24-bit draws of the counter RNG, streams 0x5A0 and
+ *     0x5A1, counter k (the RNG of prv_model_synthetic / the training sampler: mix64(seed + (stream + 1) * 0xD1B54A32D192ED03
+ *     + k * 0x9E3779B97F4A7C15) >> 40).  The triangle is the last one whose exclusive prefix is <= target (binary search),
+ *     so a zero-weight triangle is never chosen.
+ *   Position: u = (float)r2 * 2^-24, v = (float)r3 * 2^-24 (streams 0x5A2, 0x5A3); if u + v > 1 (fp32): u = 1 - u,
+ *     v = 1 - v; per axis p = (a + u * (b - a)) + v * (c - a), every operation its own fp32 rounding (no contraction).
+ *   Errors: n == 0 or NULL / host pointers PRV_E_INVALID; a mesh without triangles or without area PRV_E_STATE. */
+int prv_mesh_sample(const prv_mesh* m, uint64_t n, uint64_t seed, float* out_xyz_dev, uint32_t* out_tri_dev);
+
+/* Nearest neighbours.  An index holds n reference points (device n*3 float32, any frame, any bounding box; copied: the
+ * caller's array may go away).  A query of m points returns per query the squared distance to, and the id of, its nearest
+ * reference point.  ARITHMETIC CONTRACT: dx = q.x - p.x, dy, dz in fp32; d2 = (dx*dx + dy*dy) + dz*dz (no contraction);
+ * the minimum is over ALL reference points and on equal d2 the smallest id wins -- an order-independent result, bit-identical
+ * to a brute-force float32 restatement whatever the search structure does.
+ * PRV_NN_GRID (default): a uniform grid over the reference points' bounding box, about four points per cell (at most 2^23
+ *   cells, 1024 per axis: prv_nn_index_info says whether a cap was hit; an axis thinner than a cell gets one layer, so planes,
+ *   lines and a single repeated point work), built by counting sort (integer atomics, the mesh scan, a scatter).  A query
+ *   is binned with the same grid, clamped to the border cell if outside; a wave takes 64 neighbouring queries, walks
+ *   shells of cells outwards around them and stops when no unvisited cell can hold a nearer or equal point, by a bound that
+ *   is conservative in fp32 (rounding may cost a visited shell, never a neighbour).
+ * PRV_NN_BRUTE: every pair, tiled through LDS: the on-device check of the grid at sizes a CPU cannot reach.  Both
+ *   return identical bytes.
+ * Limits: 1 <= n, m <= 2^31; NaN / Inf coordinates on either side are refused with PRV_E_INVALID (a validation pass). */
+#define PRV_NN_GRID 0
+#define PRV_NN_BRUTE 1
+typedef struct prv_nn_index prv_nn_index; /* owns its device buffers; inert (PRV_E_STATE) if it outlives its context */
+typedef struct prv_nn_opts {
+  int32_t algorithm; /* PRV_NN_GRID | PRV_NN_BRUTE */
+  int32_t reserved;  /* 0 */
+} prv_nn_opts;
+int prv_nn_default_opts(prv_nn_opts* o);
+int prv_nn_index_create(prv_ctx* ctx, const float* xyz_dev, uint64_t n, const prv_nn_opts* opts /* NULL: defaults */,
+                        prv_nn_index** out);
+/* out_d2_dev m float32, out_id_dev m uint32, in the caller's query order; synchronises */
+int prv_nn_query(prv_nn_index* index, const float* query_xyz_dev, uint64_t m, float* out_d2_dev, uint32_t* out_id_dev);
+/* points held, grid cells per axis (0 for PRV_NN_BRUTE), whether a cell cap was hit; any pointer may be NULL */
+int prv_nn_index_info(const prv_nn_index* index, uint64_t* n, int32_t dims[3], int32_t* capped);
+/* (query, reference) pairs whose distance the last prv_nn_query formed (PRV_NN_BRUTE: m * n) */
+int prv_debug_nn_tests(const prv_nn_index* index, uint64_t* tests);
+void prv_nn_index_destroy(prv_nn_index* index);
+
+/* The accuracy / completeness / Chamfer / F-score family between a reconstruction's points and a reference's (device n*3
+ * float32 each, the same frame).  Builds a grid index per side and queries both ways; per direction, on the device:
+ * dist = the correctly rounded fp32 sqrt of the query's d2, widened to fp64; sums over a fixed grid of blocks, the
+ * blocks' partials added in block order (deterministic run to run); dist <= tau counted in integers.
+ * Distances are in the frame of the inputs, and so is tau: for engine-frame inputs divide the distances by the
+ * transforms' `scale` (the squared ones by scale^2) to get dataset units, and pass tau * scale. */
+typedef struct prv_geom_metrics {
+  uint64_t n_rec, n_ref;
+  double accuracy, completeness;       /* mean distance rec->ref, ref->rec */
+  double accuracy_sq, completeness_sq; /* mean squared distances */
+  double chamfer;                      /* (accuracy + completeness) / 2 */
+  double precision, recall, fscore;    /* share of rec / ref points within tau; harmonic mean (0 if both are 0) */
+  double hausdorff_rec, hausdorff_ref; /* largest distance each way */
+} prv_geom_metrics;
+int prv_geometry_metrics(prv_ctx* ctx, const float* rec_xyz_dev, uint64_t n_rec, const float* ref_xyz_dev, uint64_t n_ref,
+                         float tau, prv_geom_metrics* out);
+/* the same with the caller's index of the reference points (prv_nn_index_create on ref_xyz_dev, either algorithm): the
+ * reference side is not indexed again -- a loop that compares every iteration against one reference builds it once.
+ * ref_xyz_dev / n_ref must be the points the index was made of (n_ref is checked); identical results. */
+int prv_geometry_metrics_indexed(prv_ctx* ctx, const float* rec_xyz_dev, uint64_t n_rec, prv_nn_index* ref_index,
+                                 const float* ref_xyz_dev, uint64_t n_ref, float tau, prv_geom_metrics* out);
+
 /* ---- several GPUs: view sharding + one all-gather ----------------------------- */
 /* replaces: nothing in the reference -- its loops over the candidates are serial (main.cpp:2045-2094, 2105-2158;
  * run.py:293) and it has no multi-GPU path.  One process per GPU (RANK / WORLD_SIZE / LOCAL_RANK as torchrun exports

@@ -25,6 +25,9 @@ STEP_FIXED_S = 0  # prv.h: samples_per_ray uniform samples between the AABB hits
 STEP_NGP = 1      # instant-ngp's rule, what run.py:304 renders with: dt = sqrt(3)/1024, every step tested, no cap
 NGP_MAX_STEPS = 1024
 
+NN_GRID = 0   # prv.h: uniform grid + shell walk (default)
+NN_BRUTE = 1  # every pair, tiled through LDS: the grid's on-device twin
+
 MAX_MODELS = 8
 MAX_SLOTS = 64
 MLP_HALFS = 10240
@@ -70,6 +73,16 @@ class ModelLayout(C.Structure):
 class MeshOpts(C.Structure):
     _fields_ = [("res", C.c_int32 * 3), ("aabb_lo", C.c_float * 3), ("aabb_hi", C.c_float * 3), ("threshold", C.c_float),
                 ("use_occupancy", C.c_int32), ("colors", C.c_int32)]
+
+
+class NNOpts(C.Structure):
+    _fields_ = [("algorithm", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GeomMetrics(C.Structure):
+    _fields_ = [("n_rec", C.c_uint64), ("n_ref", C.c_uint64)] + [(n, C.c_double) for n in (
+        "accuracy", "completeness", "accuracy_sq", "completeness_sq", "chamfer", "precision", "recall", "fscore", "hausdorff_rec",
+        "hausdorff_ref")]
 
 
 class ScoreRecord(C.Structure):
@@ -150,6 +163,15 @@ SIGNATURES = {
     "prv_mesh_save": (_i, [_vp, C.c_char_p, C.c_double, _vp]),
     "prv_mesh_write_file": (_i, [C.c_char_p, C.c_uint64, _vp, _vp, _vp, C.c_uint64, _vp, C.c_double, _vp]),
     "prv_mesh_destroy": (None, [_vp]),
+    "prv_mesh_sample": (_i, [_vp, C.c_uint64, C.c_uint64, _vp, _vp]),
+    "prv_nn_default_opts": (_i, [_P(NNOpts)]),
+    "prv_nn_index_create": (_i, [_vp, _vp, C.c_uint64, _P(NNOpts), _P(_vp)]),
+    "prv_nn_query": (_i, [_vp, _vp, C.c_uint64, _vp, _vp]),
+    "prv_nn_index_info": (_i, [_vp, _P(C.c_uint64), _P(C.c_int32), _P(C.c_int32)]),
+    "prv_debug_nn_tests": (_i, [_vp, _P(C.c_uint64)]),
+    "prv_nn_index_destroy": (None, [_vp]),
+    "prv_geometry_metrics": (_i, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_float, _P(GeomMetrics)]),
+    "prv_geometry_metrics_indexed": (_i, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.c_float, _P(GeomMetrics)]),
     "prv_score_ensemble_images": (_i, [_vp, _i, _vp, _i, _i, C.c_size_t, _vp]),
     "prv_score_psnr_images": (_i, [_vp, _vp, _vp, _i, C.c_size_t, _vp, _vp]),
     "prv_evaluate_images": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

@@ -465,6 +465,36 @@ class Context:
         self._chk(self.lib.prv_marching_cubes_grid(self.handle, _ptr(sigma), C.byref(o), C.byref(h)))
         return Mesh(self, h)
 
+    # -- geometric evaluation (include/prv.h, geometric evaluation section)
+    def _points(self, xyz):
+        """(n, 3) float32 on the context's device, from a torch tensor or anything numpy takes"""
+        t = self.torch
+        if not isinstance(xyz, t.Tensor):
+            xyz = t.from_numpy(np.ascontiguousarray(np.asarray(xyz, np.float32).reshape(-1, 3)))
+        return xyz.to(device=self.device, dtype=t.float32).reshape(-1, 3).contiguous()
+
+    def nn_index(self, points, algorithm=L.NN_GRID):
+        """a nearest-neighbour index over `points` ((n, 3), any frame) -> NNIndex"""
+        pts = self._points(points)
+        o = L.NNOpts()
+        self.lib.prv_nn_default_opts(C.byref(o))
+        o.algorithm = int(algorithm)
+        h = C.c_void_p()
+        self._chk(self.lib.prv_nn_index_create(self.handle, _ptr(pts), pts.shape[0], C.byref(o), C.byref(h)))
+        return NNIndex(self, h)
+
+    def geometry_metrics(self, rec, ref, tau, ref_index=None):
+        """accuracy / completeness / Chamfer / F-score between two point sets of one frame -> dict of prv_geom_metrics' fields
+        (distances and tau in that frame)"""
+        a, b = self._points(rec), self._points(ref)
+        out = L.GeomMetrics()
+        if ref_index is not None:  # the caller's index of `ref`: the reference side is not indexed again
+            self._chk(self.lib.prv_geometry_metrics_indexed(self.handle, _ptr(a), a.shape[0], ref_index.handle, _ptr(b), b.shape[0],
+                                                            float(tau), C.byref(out)))
+        else:
+            self._chk(self.lib.prv_geometry_metrics(self.handle, _ptr(a), a.shape[0], _ptr(b), b.shape[0], float(tau), C.byref(out)))
+        return {name: getattr(out, name) for name, _ in L.GeomMetrics._fields_}
+
     def mesh_stage_ms(self):
         """milliseconds of the last extraction's stages: density grid, classify + scans, emit, colours"""
         ms = (C.c_float * 4)()
@@ -538,9 +568,66 @@ class Mesh:
         if rc != 0:
             _mesh_file_error(rc)
 
+    def sample(self, n, seed=0, want_triangles=False):
+        """n area-weighted surface points (prv_mesh_sample: stratified, a pure function of (mesh, n, seed)) -> float32 (n, 3)
+        device tensor in the engine frame; with want_triangles also the int32 (n,) triangle ids"""
+        t = self.ctx.torch
+        xyz = t.empty((int(n), 3), dtype=t.float32, device=self.ctx.device)
+        tri = t.empty((int(n),), dtype=t.int32, device=self.ctx.device) if want_triangles else None
+        rc = self.ctx.lib.prv_mesh_sample(self.handle, int(n), int(seed) & (2 ** 64 - 1), _ptr(xyz), _ptr(tri))
+        if rc != 0:
+            raise PrvError(rc, (self.ctx.lib.prv_last_error(self.ctx.handle if self.ctx.handle else None) or b"").decode())
+        return (xyz, tri) if want_triangles else xyz
+
     def close(self):
         if self.handle:
             self.ctx.lib.prv_mesh_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NNIndex:
+    """a nearest-neighbour index owned by the library (prv_nn_index)"""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.handle = ctx, handle
+
+    def _chk(self, rc):
+        if rc != 0:
+            msg = self.ctx.lib.prv_last_error(self.ctx.handle if self.ctx.handle else None) or b""
+            if not msg or rc == L.PRV_E_STATE:
+                msg = self.ctx.lib.prv_last_error(None) or msg
+            raise PrvError(rc, msg.decode())
+
+    def query(self, points):
+        """-> (d2 float32 (m,), ids int32 (m,)) device tensors: squared distance to and id of each point's nearest reference
+        point (d2 = (dx*dx + dy*dy) + dz*dz in float32, ties to the smallest id)"""
+        t = self.ctx.torch
+        q = self.ctx._points(points)
+        d2 = t.empty((q.shape[0],), dtype=t.float32, device=self.ctx.device)
+        ids = t.empty((q.shape[0],), dtype=t.int32, device=self.ctx.device)
+        self._chk(self.ctx.lib.prv_nn_query(self.handle, _ptr(q), q.shape[0], _ptr(d2), _ptr(ids)))
+        return d2, ids
+
+    def info(self):
+        n, dims, capped = C.c_uint64(), (C.c_int32 * 3)(), C.c_int32()
+        self._chk(self.ctx.lib.prv_nn_index_info(self.handle, C.byref(n), dims, C.byref(capped)))
+        return dict(n=n.value, dims=tuple(dims), capped=bool(capped.value))
+
+    def tests(self):
+        """(query, reference) pairs whose distance the last query formed"""
+        v = C.c_uint64()
+        self._chk(self.ctx.lib.prv_debug_nn_tests(self.handle, C.byref(v)))
+        return v.value
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.prv_nn_index_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -570,6 +657,32 @@ def engine_to_dataset(xyz, scale, offset):
     """engine-frame positions -> the dataset (transforms.json) frame: q = (e2, e0, e1), (q - offset) / scale"""
     e = np.asarray(xyz, np.float64).reshape(-1, 3)
     return (e[:, [2, 0, 1]] - np.asarray(offset, np.float64)) / float(scale)
+
+
+GEOMETRY_FIELDS = tuple(name for name, _ in L.GeomMetrics._fields_)
+
+
+def write_geometry_metrics(path, metrics):
+    """a `*_geometry.txt` metrics file: one `name<TAB>value` line per field of prv_geom_metrics in struct order, in the style
+    of the PSNR / SSIM metrics file (run.py:273-277); the doubles with 17 significant digits, so the file round-trips"""
+    with open(path, "w") as f:
+        for k in GEOMETRY_FIELDS:
+            f.write(f"{k}\t{int(metrics[k])}\n" if k.startswith("n_") else f"{k}\t{float(metrics[k]):.17g}\n")
+
+
+def read_geometry_metrics(path):
+    out = {}
+    with open(path) as f:
+        for line in f:
+            k, v = line.rstrip("\n").split("\t")
+            out[k] = int(v) if k.startswith("n_") else float(v)
+    return out
+
+
+def dataset_to_engine(xyz, scale, offset):
+    """the inverse of engine_to_dataset: q = p * scale + offset, e = (q1, q2, q0)"""
+    q = np.asarray(xyz, np.float64).reshape(-1, 3) * float(scale) + np.asarray(offset, np.float64)
+    return q[:, [1, 2, 0]]
 
 
 class Comm:
@@ -966,6 +1079,27 @@ class Testbed:
             m.save(filename, self.scale, self.offset)
         finally:
             m.close()
+
+    def compute_geometry_metrics(self, reference_points, resolution=(256, 256, 256), n_samples=1 << 20, tau=None, thresh=2.5, seed=0):
+        """mesh the current model (marching cubes at `resolution`, iso-level `thresh`), sample n_samples surface points and
+        compare them with reference_points ((n, 3), dataset frame) -> dict of prv_geom_metrics' fields in DATASET units.
+        tau (dataset units) defaults to 1 % of the reference's largest extent."""
+        if not self._have_model:
+            raise PrvError(L.PRV_E_STATE, "no model loaded")
+        ref = np.asarray(reference_points, np.float64).reshape(-1, 3)
+        if tau is None:
+            tau = 0.01 * float((ref.max(axis=0) - ref.min(axis=0)).max())
+        m = self.ctx.marching_cubes(self._slot, resolution, None, thresh, colors=False)
+        try:
+            rec = m.sample(n_samples, seed)
+        finally:
+            m.close()
+        out = self.ctx.geometry_metrics(rec, dataset_to_engine(ref, self.scale, self.offset).astype(np.float32), float(tau) * self.scale)
+        for k in ("accuracy", "completeness", "chamfer", "hausdorff_rec", "hausdorff_ref"):
+            out[k] /= self.scale
+        for k in ("accuracy_sq", "completeness_sq"):
+            out[k] /= self.scale ** 2
+        return out
 
     def _ground_truth(self, i, width, height):
         """render_ground_truth (run.py:241-244): the dataset image of view i, linear premultiplied RGBA"""

@@ -28,6 +28,7 @@ extern "C" {
 }
 #include "planner.hpp"
 #include "fit_curve.hpp"
+#include "geometry_eval.hpp"
 #include "extras/pcd_io.hpp" // mode 3 only: the coloured cloud the splat rasteriser turns into rgbaClip images (not exported)
 #include "png_io.hpp"
 
@@ -295,7 +296,10 @@ struct HipScorer {
       if (rc != PRV_OK) return rc;
       char buf[128];
       snprintf(buf, sizeof(buf), "PSNR\t%.17g\nSSIM\t%.17g", psnr, ssim); // run.py:275-277
-      return write_text(a.save_metrics, buf) ? 0 : PRV_E_IO;
+      if (!write_text(a.save_metrics, buf)) return PRV_E_IO;
+      std::string g = a.save_metrics; // <...>/<it>.txt -> <...>/<it>_geometry.txt
+      if (g.size() >= 4 && g.substr(g.size() - 4) == ".txt") g.resize(g.size() - 4);
+      return geometry_evaluate(slot, g + "_geometry.txt");
     }
     return 0;
   }
@@ -435,6 +439,111 @@ struct HipScorer {
     test_gt_key.clear();
   }
   int eval_views = 100;
+
+  // `evaluate_geometry: 1` (geometry_eval.hpp): beside every metrics/<it>.txt the loop writes, member 0's marching-cubes mesh is
+  // sampled and compared with a reference surface -- a .pcd cloud (`geometry_reference`, read here and nowhere else) or samples of
+  // the ground-truth field's mesh (slot 6), made once per object -- and metrics/<it>_geometry.txt gets prv_geom_metrics in
+  // dataset units.  The reference's index is built once: every iteration compares against the same points.
+  GeometryEvalConfig geom;
+  float* geom_ref_dev = nullptr;
+  uint64_t geom_ref_n = 0;
+  prv_nn_index* geom_ref_index = nullptr;
+  double geom_scale = 1.0, geom_size = 0.1; // engine units per dataset unit (the json's scale); the object size
+  void drop_geometry() {
+    if (geom_ref_index) prv_nn_index_destroy(geom_ref_index);
+    if (geom_ref_dev) prv_free(ctx, geom_ref_dev);
+    geom_ref_index = nullptr;
+    geom_ref_dev = nullptr;
+    geom_ref_n = 0;
+  }
+  // the reference surface in the engine frame + its index; every failure is a message and an error BEFORE any training
+  int geometry_setup(const Vec3& center, double size) {
+    const std::string problem = geometry_eval_problem(geom);
+    if (!problem.empty()) {
+      std::cerr << "evaluate_geometry: " << problem << std::endl;
+      return -80;
+    }
+    drop_geometry();
+    geom_size = size;
+    geom_scale = 0.5 / size; // the json's scale and offset (transforms_header; prv_splat_points takes the same pair)
+    const double offset[3] = {0.5 + center.z, 0.5 + center.x, 0.5 + center.y};
+    int rc = PRV_OK;
+    if (!geom.reference.empty()) {
+      std::vector<float> xyz;
+      std::vector<uint8_t> rgb;
+      const int prc = pcd_read(geom.reference, xyz, rgb);
+      if (prc != 0 || xyz.size() < 3) {
+        std::cerr << "evaluate_geometry: cannot read a cloud from geometry_reference " << geom.reference << " (" << prc << "); nothing was trained" << std::endl;
+        return -81;
+      }
+      geometry_to_engine(xyz, geom_scale, offset);
+      geom_ref_n = xyz.size() / 3;
+      rc = prv_malloc(ctx, (void**)&geom_ref_dev, xyz.size() * 4);
+      if (rc == PRV_OK) rc = prv_memcpy_h2d(ctx, geom_ref_dev, xyz.data(), xyz.size() * 4);
+    } else {
+      prv_field_desc d;
+      if (prv_model_desc(ctx, 6, &d) != PRV_OK) {
+        std::cerr << "evaluate_geometry: no usable reference -- no geometry_reference cloud is named and there is no ground-truth field in "
+                     "slot 6 (train_steps or evaluate puts one there); nothing was trained" << std::endl;
+        return -82;
+      }
+      prv_mesh_opts mo;
+      prv_mesh_default_opts(&mo);
+      for (int a = 0; a < 3; a++) mo.res[a] = geom.mc_res;
+      mo.colors = 0;
+      prv_mesh* m = nullptr;
+      rc = prv_marching_cubes(ctx, 6, &mo, &m);
+      uint64_t nt = 0;
+      if (rc == PRV_OK) prv_mesh_counts(m, nullptr, &nt);
+      if (rc == PRV_OK && nt == 0) {
+        std::cerr << "evaluate_geometry: no usable reference -- the ground-truth field has no surface at the iso-level; nothing was trained" << std::endl;
+        prv_mesh_destroy(m);
+        return -83;
+      }
+      geom_ref_n = geom.samples;
+      if (rc == PRV_OK) rc = prv_malloc(ctx, (void**)&geom_ref_dev, geom_ref_n * 12);
+      if (rc == PRV_OK) rc = prv_mesh_sample(m, geom_ref_n, 1, geom_ref_dev, nullptr);
+      if (m) prv_mesh_destroy(m);
+    }
+    if (rc == PRV_OK) rc = prv_nn_index_create(ctx, geom_ref_dev, geom_ref_n, nullptr, &geom_ref_index);
+    if (rc != PRV_OK) {
+      std::cerr << "evaluate_geometry: " << prv_last_error(ctx) << std::endl;
+      drop_geometry();
+    }
+    return rc;
+  }
+  // the field in `slot` against the reference -> `path`.  A field without a surface yet is not an error: the file says n_rec 0.
+  int geometry_evaluate(int slot, const std::string& path) {
+    if (!geom.on || !geom_ref_index) return PRV_OK;
+    prv_mesh_opts mo;
+    prv_mesh_default_opts(&mo);
+    for (int a = 0; a < 3; a++) mo.res[a] = geom.mc_res;
+    mo.colors = 0;
+    prv_mesh* m = nullptr;
+    int rc = prv_marching_cubes(ctx, slot, &mo, &m);
+    uint64_t nt = 0;
+    if (rc == PRV_OK) prv_mesh_counts(m, nullptr, &nt);
+    prv_geom_metrics gm{};
+    gm.n_ref = geom_ref_n;
+    float* rec = nullptr;
+    if (rc == PRV_OK && nt > 0) {
+      rc = prv_malloc(ctx, (void**)&rec, geom.samples * 12);
+      if (rc == PRV_OK) rc = prv_mesh_sample(m, geom.samples, 0, rec, nullptr);
+      if (rc == PRV_OK)
+        rc = prv_geometry_metrics_indexed(ctx, rec, geom.samples, geom_ref_index, geom_ref_dev, geom_ref_n,
+                                          (float)(geom.tau_for(geom_size) * geom_scale), &gm);
+    } else if (rc == PRV_OK) {
+      std::cerr << "evaluate_geometry: the field has no surface at the iso-level yet (" << path << ": n_rec 0)" << std::endl;
+      gm.accuracy = gm.completeness = gm.accuracy_sq = gm.completeness_sq = gm.chamfer = gm.hausdorff_rec = gm.hausdorff_ref = NAN;
+    }
+    if (rec) prv_free(ctx, rec);
+    if (m) prv_mesh_destroy(m);
+    if (rc != PRV_OK) {
+      std::cerr << "evaluate_geometry: " << prv_last_error(ctx) << std::endl;
+      return rc;
+    }
+    return write_text(path, geometry_metrics_text(gm, geom_scale)) ? PRV_OK : PRV_E_IO;
+  }
 
   bool save_renders = false; // save_renders: 1 -> the PNG tree the reference's run.py leaves (main.cpp:1676-1684)
 
@@ -700,6 +809,14 @@ int PlanningJob::setup(prv_ctx* ctx_, const std::string& cfg, const std::string&
       return sc ? sc->evaluate(scene, center, size, p, q) : -42;
     };
   }
+  if (HipScorer* sc = labeler.scorer.target<HipScorer>()) {
+    sc->geom = geometry_eval_config(fs);
+    if (sc->geom.on) { // the reference surface once per object; a run without a usable one stops here, before any training
+      const int rc = sc->geometry_setup(center, size);
+      if (rc != PRV_OK) return rc;
+      labeler.geometry_evaluator = [sc](const std::string& path) { return sc->geometry_evaluate(sc->slot_of(0), path); };
+    }
+  }
   // train_by_instantNGP's reference signature -> the in-process engine (one run.py invocation per call); the engine
   // shares the loop's scorer object, so `score_path: png` and the fused path train and render the same members
   HipScorer* engine_state = labeler.scorer.target<HipScorer>();
@@ -719,6 +836,7 @@ int PlanningJob::finish(int rc) {
   if (engine_state) {
     engine_state->drop_training_data();
     engine_state->drop_test_images();
+    engine_state->drop_geometry();
   }
   if (gt_dev) prv_free(ctx, gt_dev);
   gt_dev = nullptr;

@@ -185,6 +185,7 @@ public:
   Scorer scorer;
   Engine engine;      // the in-process run.py behind train_by_instantNGP's reference signature
   EvalFn evaluator;   // empty: `evaluate: 1` is ignored
+  std::function<int(const std::string&)> geometry_evaluator; // `evaluate_geometry: 1`: writes the geometry file named, beside every metrics/<it>.txt
   std::vector<int> chosen_nbvs;
   std::vector<double> last_scores;
   // called after every scoring iteration with (iteration, unchosen view ids, their scores): logging / test dumps live in
@@ -377,6 +378,10 @@ public:
         char buf[128];
         snprintf(buf, sizeof(buf), "PSNR\t%.17g\nSSIM\t%.17g", psnr, ssim);
         write_text(sd.save_path + "/metrics/" + it + ".txt", buf);
+        if (geometry_evaluator) { // evaluate_geometry: 1 -> metrics/<it>_geometry.txt beside it, from the member just evaluated
+          const int grc = geometry_evaluator(sd.save_path + "/metrics/" + it + "_geometry.txt");
+          if (grc != 0) return grc < 0 ? grc : -13;
+        }
         final_psnr = psnr;
         final_ssim = ssim;
       }
