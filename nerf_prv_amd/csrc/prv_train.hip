@@ -1725,6 +1725,9 @@ __global__ __launch_bounds__(256) void adam_table_kernel(AdamParams P, size_t n,
     *reinterpret_cast<ushort4v*>(w16 + i4) = h4;
     return;
   }
+  // Unreachable through the C ABI: compute_levels (prv_levels.hpp) rounds a dense level to a multiple of 8 entries and a hashed
+  // level holds 2^log2_hashmap >= 16 of them, so with F = 2 or 4 every table is whole groups of four scalars (asserted over the
+  // descriptor shapes of tests/instances.py in tests/test_adam_host.py).  Kept for a caller that hands in any other n.
   float* r = wmv + i4 * 3;
   for (size_t i = i4; i < n; i++) { // the last, partial group
     float g;
