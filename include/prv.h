@@ -270,6 +270,15 @@ int prv_render_entropy(prv_ctx* ctx, int model_slot, const prv_camset* cs, const
                        const prv_render_opts* opts, float* out_entropy_dev, float* out_alpha_dev, prv_stats* stats);
 int prv_quantize_rgba8(prv_ctx* ctx, const float* rgba_dev, size_t n_pixels, const float bg[4],
                        uint8_t* out_rgba8_dev);
+/* Entropy, opacity and depth of the same views from ONE density-only launch (this build's own; what the selection stage below
+ * consumes): the entropy kernel's density layers plus the depth kernel's one FMA per sample, D = fmaf(w_i, t_i, D), and
+ * z = D * dot(d, f) at ray end.  No colour is evaluated.  All three planes are n_views*h*w float32 and all three are required.
+ * CONTRACT: out_entropy_dev and out_alpha_dev are bit-identical to prv_render_entropy's, out_depth_dev is bit-identical to
+ * prv_render_depth's depth plane, stats are identical to both, for the same views and options (either stepping rule, any spp:
+ * each plane is reduced over its sub-samples in order, then scaled by 1/spp). */
+int prv_render_footprint(prv_ctx* ctx, int model_slot, const prv_camset* cs, const int* view_ids, int n_views,
+                         const prv_render_opts* opts, float* out_entropy_dev, float* out_alpha_dev, float* out_depth_dev,
+                         prv_stats* stats);
 
 /* replaces: Perception_3D::precept / precept_thread_process, the reference's CPU render path
  * (main.cpp:98-284: project -> ray -> OctoMap castRay, max range main.cpp:258).  Per pixel the
@@ -337,6 +346,54 @@ int prv_score_views(prv_ctx* ctx, int method, const int* model_slots, int n_mode
  * strict '>' never selects a NaN either); host only. */
 int prv_rank(const prv_score_record* records, const int* view_ids, int n, int* order);
 int prv_argmax(const prv_score_record* records, const int* view_ids, int n);
+
+/* ---- several next views per round: greedy, redundancy-aware selection ---------- */
+/* replaces: nothing in the reference -- it adds ONE view per training round (main.cpp:1971-1972).  This build's own: choose k
+ * views of a round's candidates so that a later choice is not paid for what an earlier one already sees.  The k best by
+ * score do not do that: neighbouring candidates with high ray entropy look at the same unfinished part of the object.
+ * Inputs are the three planes of prv_render_footprint for the candidates (width x height each).  Every float operation below
+ * is one IEEE float32 operation in the order written, so a float32 restatement is bit-exact.  For pixel (x, y) of view v,
+ * with H, alpha, z its entropy, opacity and depth:
+ *   gain      q = H > 0 ? (uint32) min(floorf(H * 65536.0f), 4294967040.0f) : 0        (NaN or negative H: 0)
+ *   located   iff alpha >= alpha_min and z > 0 (a NaN fails either)
+ *   point of a located pixel:
+ *     (o, d) = the ray generator's ray of that pixel at sub-sample 0 of a 1-spp render (prv_debug_raygen, spp_index 0);
+ *     c = fmaf(d0, fx, fmaf(d1, fy, d2 * fz)) * (1.0f / sqrtf(fmaf(fx, fx, fmaf(fy, fy, fz * fz)))), (fx, fy, fz) = column 2 of
+ *         the view's engine-frame c2w: the forward cosine exactly as the depth kernel forms it;
+ *     t = (z / alpha) / c                      two IEEE divisions
+ *     p_a = o_a + (t * d_a)                    a float32 multiply, then a float32 add: NO FMA
+ *     f_a = floorf(p_a * G), G = (float)grid_res; if any f_a is not in [0, G) (NaN included) the pixel is unlocated after
+ *     all; otherwise g_a = (int)f_a and voxel = g_x + G * (g_y + G * g_z).  Unlocated pixels carry 0xFFFFFFFF.
+ *   greedy rounds: C = a set of voxels (G^3 bits), empty at the start.  k times:
+ *     for every view not yet chosen  gain_i = sum over its pixels of q * [unlocated or voxel not in C], an exact uint64 sum;
+ *     the view with the largest gain is chosen, on a tie the one that comes first in view_ids;
+ *     the voxels of that view's located pixels are added to C.
+ *   Unlocated pixels are never discounted, so round 1 ranks the candidates as PRV_SCORE_RAY_ENTROPY does, up to the 2^-16 bit
+ *   quantisation of q.
+ * chosen_out[j] (host, k ints) = the view id chosen in round j (view_ids[i], or i when view_ids is NULL); gains_out[j] (host, k
+ * uint64, may be NULL) = its gain in that round.  voxel_dev / q_dev (device, n_views*h*w uint32 each, optional) receive the
+ * per-pixel words.  The sums are integer atomics (order-independent) and the arg-max is taken on the host from a read-back of
+ * the n_views sums per round: two calls return identical bytes.  Synchronises.
+ * Errors: k < 1, k > n_views, grid_res not a power of two in [16, 256], a NULL or host plane: PRV_E_INVALID with a message.
+ * LIMITS: the expected depth z / alpha is a poor locator on rays whose weights are spread widely (exactly the high-entropy rays:
+ * the point then lies between the surfaces the ray may stop at); coverage is binary (a voxel seen once counts as seen, from
+ * whatever angle); the stage is SINGLE-RANK: it needs every candidate's planes on one device, a sharded variant (all-gather of
+ * voxel / q words, or of bitsets) is out of scope here. */
+typedef struct prv_select_opts {
+  int32_t k;        /* views to choose, 1..n_views */
+  int32_t grid_res; /* G: power of two, 16..256, default 64 */
+  float alpha_min;  /* default 0.5 */
+} prv_select_opts;
+int prv_select_default_opts(prv_select_opts* opts); /* k 1, grid_res 64, alpha_min 0.5 */
+int prv_select_from_images(prv_ctx* ctx, const prv_camset* cs, const int* view_ids, int n_views, int width, int height,
+                           const float* entropy_dev, const float* alpha_dev, const float* depth_dev,
+                           const prv_select_opts* opts, int* chosen_out, uint64_t* gains_out, uint32_t* voxel_dev,
+                           uint32_t* q_dev);
+/* prv_render_footprint of the views into context scratch, then prv_select_from_images on those planes at the render's size;
+ * stats: the render's */
+int prv_select_views(prv_ctx* ctx, int model_slot, const prv_camset* cs, const int* view_ids, int n_views,
+                     const prv_render_opts* render_opts, const prv_select_opts* opts, int* chosen_out, uint64_t* gains_out,
+                     prv_stats* stats);
 
 /* replaces: Perception_3D::render (the PCL screenshot of the coloured ground-truth cloud with
  * points_size_cloud-pixel points on white, main.cpp:68-96) + convertToAlpha (Share_Data.hpp:771-784) +

@@ -79,6 +79,10 @@ class NNOpts(C.Structure):
     _fields_ = [("algorithm", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SelectOpts(C.Structure):
+    _fields_ = [("k", C.c_int32), ("grid_res", C.c_int32), ("alpha_min", C.c_float)]
+
+
 class GeomMetrics(C.Structure):
     _fields_ = [("n_rec", C.c_uint64), ("n_ref", C.c_uint64)] + [(n, C.c_double) for n in (
         "accuracy", "completeness", "accuracy_sq", "completeness_sq", "chamfer", "precision", "recall", "fscore", "hausdorff_rec",
@@ -151,6 +155,10 @@ SIGNATURES = {
     "prv_render_rgba8": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), _vp, _P(Stats)]),
     "prv_render_depth": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), _vp, _vp, _P(Stats)]),
     "prv_render_entropy": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), _vp, _vp, _P(Stats)]),
+    "prv_render_footprint": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), _vp, _vp, _vp, _P(Stats)]),
+    "prv_select_default_opts": (_i, [_P(SelectOpts)]),
+    "prv_select_from_images": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _P(SelectOpts), _vp, _vp, _vp, _vp]),
+    "prv_select_views": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), _P(SelectOpts), _vp, _vp, _P(Stats)]),
     "prv_first_hit": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, C.c_float, _vp]),
     "prv_precept": (_i, [_vp, _i, _vp, _i, _vp, _P(Rs2Intrinsics), C.c_float, _vp]),
     "prv_quantize_rgba8": (_i, [_vp, _vp, C.c_size_t, _vp, _vp]),

@@ -74,6 +74,20 @@ def engine_render_opts(width, height, samples_per_ray, spp, min_transmittance, b
     return render_opts(width, height, n, spp, min_transmittance, background, step_mode=L.STEP_NGP if n == 0 else L.STEP_FIXED_S)
 
 
+def select_opts(k=None, grid_res=None, alpha_min=None):
+    """prv_select_opts: the library's defaults (k 1, grid_res 64, alpha_min 0.5) with the given fields replaced"""
+    o = L.SelectOpts()
+    if L.load().prv_select_default_opts(C.byref(o)) != 0:
+        raise PrvError(L.PRV_E_INVALID, "prv_select_default_opts failed")
+    if k is not None:
+        o.k = int(k)
+    if grid_res is not None:
+        o.grid_res = int(grid_res)
+    if alpha_min is not None:
+        o.alpha_min = float(alpha_min)
+    return o
+
+
 def model_sizes(desc):
     lib = L.load()
     t, m, o = C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -323,6 +337,42 @@ class Context:
         self._chk(self.lib.prv_render_entropy(self.handle, slot, camset.handle, _ptr(ids), len(ids), C.byref(opts), _ptr(out),
                                               _ptr(out_alpha), C.byref(st) if want_stats else None))
         return out, out_alpha, st
+
+    def render_footprint(self, slot, camset, view_ids, opts, want_stats=True):
+        """prv_render_footprint -> (entropy, alpha, depth: [n, h, w] float32 each, stats): `render_entropy`'s two planes and
+        `render_depth`'s depth plane, bit for bit, from one density-only launch"""
+        ids = self._ids(camset, view_ids)
+        ent, alpha, depth = (self.torch.empty((len(ids), opts.height, opts.width), dtype=self.torch.float32, device=self.device)
+                             for _ in range(3))
+        st = L.Stats()
+        self._chk(self.lib.prv_render_footprint(self.handle, slot, camset.handle, _ptr(ids), len(ids), C.byref(opts), _ptr(ent),
+                                                _ptr(alpha), _ptr(depth), C.byref(st) if want_stats else None))
+        return ent, alpha, depth, st
+
+    def select_from_images(self, camset, view_ids, entropy, alpha, depth, opts, want_words=False):
+        """prv_select_from_images on device planes [n, h, w] -> (chosen view ids [k] int32, gains [k] uint64) and, with
+        want_words, the per-pixel (voxel, q) words as int32-typed device tensors [n, h, w] holding uint32 bit patterns"""
+        ids = self._ids(camset, view_ids)
+        h, w = int(entropy.shape[1]), int(entropy.shape[2])
+        k = max(int(opts.k), 0)
+        chosen, gains = np.zeros(k, np.int32), np.zeros(k, np.uint64)
+        voxel = q = None
+        if want_words:
+            voxel = self.torch.empty((len(ids), h, w), dtype=self.torch.int32, device=self.device)
+            q = self.torch.empty((len(ids), h, w), dtype=self.torch.int32, device=self.device)
+        self._chk(self.lib.prv_select_from_images(self.handle, camset.handle, _ptr(ids), len(ids), w, h, _ptr(entropy), _ptr(alpha),
+                                                  _ptr(depth), C.byref(opts), _ptr(chosen), _ptr(gains), _ptr(voxel), _ptr(q)))
+        return (chosen, gains, voxel, q) if want_words else (chosen, gains)
+
+    def select_views(self, slot, camset, view_ids, render_opts, opts, want_stats=False):
+        """prv_select_views: the footprint render of the candidates, then the greedy rounds -> (chosen [k], gains [k], stats)"""
+        ids = self._ids(camset, view_ids)
+        k = max(int(opts.k), 0)
+        chosen, gains = np.zeros(k, np.int32), np.zeros(k, np.uint64)
+        st = L.Stats()
+        self._chk(self.lib.prv_select_views(self.handle, slot, camset.handle, _ptr(ids), len(ids), C.byref(render_opts), C.byref(opts),
+                                            _ptr(chosen), _ptr(gains), C.byref(st) if want_stats else None))
+        return chosen, gains, st
 
     def first_hit(self, slot, camset, view_ids, width, height, max_range=1e30):
         ids = self._ids(camset, view_ids)

@@ -21,6 +21,7 @@
 #include "prv_kernels.hpp"
 #include "prv_mesh.hpp"
 #include "prv_geom.hpp"
+#include "prv_select.hpp"
 #include "prv_levels.hpp"
 #include "prv_ingp.hpp"
 #include "prv_train.hpp"
@@ -82,6 +83,8 @@ struct prv_ctx {
   // grow-only workspaces
   Buffer queue, queue_ext, stage, counters, view_ids, img_f32, partial, records, dbg[6];
   Buffer stage_depth; // prv_render_depth with spp > 1: the sub-samples' depth images (spp x batch x image floats)
+  Buffer stage_foot;  // prv_render_footprint with spp > 1: the sub-samples' depth images (stage_depth holds their entropy)
+  Buffer sel_planes, sel_voxel, sel_q, sel_bits, sel_sums; // prv_select_*: the footprint planes of prv_select_views, voxel and gain per pixel, the covered bitset, the views' sums
   Buffer counters_multi, occ_multi; // the ensemble's one-launch march: queue heads + counts per member, the interleaved occupancy bytes
   int march_multi = -1;             // PRV_MARCH_MULTI=0/1 (-1: on where an instance exists, render_ensemble_ngp)
   Buffer img_u8[PRV_MAX_MODELS];
@@ -800,7 +803,8 @@ RenderParams render_params(prv_ctx* c, const Model& m, const prv_render_opts* o,
 // the queue in batches so the queue stays within queue_budget bytes.  out_depth (prv_render_depth): the views' depth images
 // as well, n_views * H * W floats, through the depth instances of the render kernel; null: the colour render alone.
 // out_entropy + out_alpha (prv_render_entropy, PRV_SCORE_RAY_ENTROPY; out_f32 and out_u8 null): no colour at all -- the march
-// and the entropy kernel, which writes these two planes of n_views * H * W floats.
+// and the entropy kernel, which writes these two planes of n_views * H * W floats.  out_entropy AND out_depth
+// (prv_render_footprint): the march and the footprint kernel, which writes all three planes.
 int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views,
                  const prv_render_opts* o, float* out_f32, uint8_t* out_u8, bool zero_stats, bool private_output = false,
                  float* out_depth = nullptr, float* out_entropy = nullptr, float* out_alpha = nullptr) {
@@ -828,7 +832,8 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
   const size_t slot_bytes = kRecordBytes + (ngp ? kExtBytes : 0); // NGP: every queue slot has its mask-extension slot
   size_t batch = std::max<size_t>(1, c->queue_budget / (npix * slot_bytes * (size_t)spp));
   batch = std::min<size_t>(batch, (size_t)n_views);
-  const size_t stage_px = out_entropy ? 4 + 4 : out_depth ? 16 + 4 : 16; // staging bytes per sub-sample pixel: RGBA (+ depth), or entropy + opacity
+  const bool footprint = out_entropy && out_depth;
+  const size_t stage_px = footprint ? 4 + 4 + 4 : out_entropy ? 4 + 4 : out_depth ? 16 + 4 : 16; // staging bytes per sub-sample pixel: RGBA (+ depth), or entropy + opacity
   if (spp > 1) batch = std::min<size_t>(batch, std::max<size_t>(1, c->stage_budget / (npix * stage_px * (size_t)spp)));
   if (batch * npix * (size_t)spp >= (1ull << 32)) batch = ((1ull << 32) - 1) / (npix * (size_t)spp); // 32-bit pixel ids
   if (batch == 0) return fail(c, PRV_E_INVALID, "image x spp too large");
@@ -839,6 +844,7 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
   if (ngp && (rc = ensure(c, c->queue_ext, seg_cap_max * (size_t)L.n_seg * kExtBytes)) != PRV_OK) return rc;
   if (spp > 1 && (rc = ensure(c, c->stage, batch * npix * (size_t)spp * (out_entropy ? 4 : 16))) != PRV_OK) return rc;
   if (spp > 1 && (out_depth || out_entropy) && (rc = ensure(c, c->stage_depth, batch * npix * (size_t)spp * 4)) != PRV_OK) return rc;
+  if (spp > 1 && footprint && (rc = ensure(c, c->stage_foot, batch * npix * (size_t)spp * 4)) != PRV_OK) return rc;
 
   const int n_blocks = render_blocks(c, m, npix);
   for (size_t b0 = 0; b0 < (size_t)n_views; b0 += batch) {
@@ -846,7 +852,7 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
     float* dst_f32 = out_f32 ? out_f32 + b0 * npix * 4 : nullptr;
     uint32_t* dst_u8 = out_u8 ? (uint32_t*)out_u8 + b0 * npix : nullptr;
     float* dst_depth = out_depth ? out_depth + b0 * npix : nullptr;
-    float* depth_target = spp > 1 ? (float*)c->stage_depth.p : dst_depth;
+    float* depth_target = spp > 1 ? (float*)(footprint ? c->stage_foot.p : c->stage_depth.p) : dst_depth;
     // the march writes no depth: every pixel starts at 0, which is what a dead ray contributes
     if (out_depth) HIPCHK(c, hipMemsetAsync(depth_target, 0, (size_t)nb * npix * (size_t)spp * 4, c->stream));
     // the entropy render's planes: H where the depth would go, the opacity where the colour would (sub-samples: their staging)
@@ -893,6 +899,26 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
     }
     if ((rc = timed(c, c->ev_march, [&] { HIPCHK(c, launch_march(mp, nb, spp, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
     const RenderParams rp = render_params(c, m, o, L, mp.seg_cap, {mp.queue, mp.queue_ext, mp.queue_count, mp.out_f32, mp.out_u8}, q_head, stat);
+    if (footprint) {
+      RenderFootprintParams fp;
+      memset(&fp, 0, sizeof(fp));
+      fp.z.r = rp;
+      render_policy(c, m, npix, ngp, fp.z.r, false);
+      fp.z.out_depth = depth_target;
+      fp.z.cams = mp.cams;
+      fp.z.view_ids = mp.view_ids;
+      fp.z.npix = (uint32_t)npix;
+      fp.z.nb = (uint32_t)nb;
+      fp.out_entropy = entropy_target;
+      fp.out_alpha = alpha_target;
+      if ((rc = timed(c, c->ev_render, [&] { HIPCHK(c, launch_render_footprint(fp, n_blocks, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
+      if (spp > 1) {
+        HIPCHK(c, launch_spp_reduce_depth(entropy_target, (size_t)nb * npix, spp, dst_entropy, c->stream));
+        HIPCHK(c, launch_spp_reduce_depth(alpha_target, (size_t)nb * npix, spp, dst_alpha, c->stream));
+        HIPCHK(c, launch_spp_reduce_depth(depth_target, (size_t)nb * npix, spp, dst_depth, c->stream));
+      }
+      continue;
+    }
     if (out_entropy) {
       RenderEntropyParams ep;
       memset(&ep, 0, sizeof(ep));
@@ -1129,6 +1155,8 @@ void prv_destroy(prv_ctx* c) {
   release(c->queue_ext);
   release(c->stage);
   release(c->stage_depth);
+  release(c->stage_foot);
+  for (Buffer* b : {&c->sel_planes, &c->sel_voxel, &c->sel_q, &c->sel_bits, &c->sel_sums}) release(*b);
   release(c->counters);
   if (c->pin) (void)hipHostFree(c->pin);
   if (c->pin_ev) (void)hipEventDestroy(c->pin_ev);
@@ -1653,6 +1681,22 @@ int prv_render_entropy(prv_ctx* c, int slot, const prv_camset* cs, const int* vi
   return fetch_stats(c, o, n_views, 1, st);
 } catch (...) { return caught(c); }
 
+int prv_render_footprint(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, const prv_render_opts* o,
+                         float* out_entropy, float* out_alpha, float* out_depth, prv_stats* st) try {
+  if (!c) return PRV_E_INVALID;
+  int rc;
+  if ((rc = check_model(c, slot)) != PRV_OK || (rc = check_opts(c, o)) != PRV_OK) return rc;
+  if (!cs || n_views < 0 || ((!out_entropy || !out_alpha || !out_depth) && n_views > 0))
+    return fail(c, PRV_E_INVALID, "bad camset / view count / footprint output (entropy, alpha and depth planes are all required)");
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = check_device_ptr(c, out_entropy, "out_entropy_dev")) != PRV_OK) return rc;
+  if ((rc = check_device_ptr(c, out_alpha, "out_alpha_dev")) != PRV_OK) return rc;
+  if ((rc = check_device_ptr(c, out_depth, "out_depth_dev")) != PRV_OK) return rc;
+  if (n_views == 0) out_entropy = out_alpha = out_depth = nullptr;
+  if ((rc = render_views(c, slot, cs, view_ids, n_views, o, nullptr, nullptr, true, false, out_depth, out_entropy, out_alpha)) != PRV_OK) return rc;
+  return fetch_stats(c, o, n_views, 1, st);
+} catch (...) { return caught(c); }
+
 int prv_first_hit(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, int W, int H,
                   float max_range, int32_t* out) try {
   if (!c) return PRV_E_INVALID;
@@ -2070,3 +2114,4 @@ int prv_debug_field(prv_ctx* c, int slot, const float* pos, const float* dir, in
 #include "prv_comm_api.inc"
 #include "prv_mesh_api.inc"
 #include "prv_geom_api.inc"
+#include "prv_select_api.inc"

@@ -13,6 +13,8 @@
 //       render_depth: the same kernel body with one more per-ray sum, the depth (prv_render_depth).
 //       render_entropy: the same queue machinery around the density layers alone; per ray the entropy of its compositing
 //       weights instead of a colour (prv_render_entropy).
+//       render_footprint: the entropy render plus the depth sum -- entropy, opacity and depth from one density-only launch
+//       (prv_render_footprint; what the selection stage of prv_select.hip consumes).
 //  K_S* score kernels : per-view reductions in fp64, fixed reduction order (no float
 //       atomics), so rankings are reproducible bit for bit.
 //
@@ -732,11 +734,18 @@ __device__ __forceinline__ float entropy_add(float p, float H) { return p >= 1.1
 // and T are its bits), no SH rows, no colour sums; the ray sums H = sum_i h(w_i) and adds h(T) when it ends, and writes H and
 // 1 - T to PE->out_entropy[pix] / PE->out_alpha[pix].  Its movable state is four words, {record, next sample, T, H}; only
 // the 8 density fragment sets are staged in LDS.  P.out_f32 / out_u8 are not touched.  PE is unused otherwise.
-enum : int { kRenderColour = 0, kRenderDepth = 1, kRenderEntropy = 2 };
+// kRenderFootprint (prv_render_footprint): the entropy mode plus the depth mode's one FMA per sample -- D = fmaf(w, t, D) in the
+// depth kernel's place, t kept live across mlp_density2 -- and z = D * dot(d, f) to PF->out_depth[pix] at ray end, formed as
+// kRenderDepth forms it.  sigma, alpha and T are the colour kernel's bits in density-only mode already, so H and 1 - T are
+// render_entropy_kernel's bits and z is render_depth_kernel's.  Movable state: five words, {record, next sample, T, H, D}.
+enum : int { kRenderColour = 0, kRenderDepth = 1, kRenderEntropy = 2, kRenderFootprint = 3 };
 template <int F, int NDENSE, bool NGP, bool CACHE, int MODE>
-__device__ __forceinline__ void render_queue64_body(RenderParams P, const RenderDepthParams* PD, const RenderEntropyParams* PE = nullptr) {
-  constexpr bool DEPTH = MODE == kRenderDepth, ENTROPY = MODE == kRenderEntropy;
-  constexpr int kMoveWords = ENTROPY ? 4 : DEPTH ? 7 : 6; // {record, next sample, T, r, g, b (, D)} or {record, next sample, T, H}
+__device__ __forceinline__ void render_queue64_body(RenderParams P, const RenderDepthParams* PD, const RenderEntropyParams* PE = nullptr,
+                                                    const RenderFootprintParams* PF = nullptr) {
+  constexpr bool FOOT = MODE == kRenderFootprint;
+  constexpr bool DEPTH = MODE == kRenderDepth || FOOT, ENTROPY = MODE == kRenderEntropy || FOOT; // DEPTH: the D sum; ENTROPY: density layers only, the H sum
+  constexpr int kDWord = FOOT ? 4 : 6;                          // where D sits in the movable state
+  constexpr int kMoveWords = FOOT ? 5 : ENTROPY ? 4 : DEPTH ? 7 : 6; // {record, next sample, T, r, g, b (, D)} or {record, next sample, T, H (, D)}
   constexpr int kFrags = ENTROPY ? 8 : kNumFrags;       // fragment sets staged in LDS: the density layers', or both MLPs'
   __shared__ half8 wl[kFrags * 64];
   __shared__ uint32_t mv[4][32][kMoveWords]; // tail merges: {record, next sample, T, r, g, b (, D)} of the rays that change slots, per wave
@@ -881,7 +890,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
             e[4] = __float_as_uint(cg);
             e[5] = __float_as_uint(cb);
           }
-          if constexpr (DEPTH) e[6] = __float_as_uint(D);
+          if constexpr (DEPTH) e[kDWord] = __float_as_uint(D);
           active = false;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -903,7 +912,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
             } else {
               cr = __uint_as_float(e[3]); cg = __uint_as_float(e[4]); cb = __uint_as_float(e[5]);
             }
-            if constexpr (DEPTH) D = __uint_as_float(e[6]);
+            if constexpr (DEPTH) D = __uint_as_float(e[kDWord]);
             take_ray(ri, e[1]);
           }
         }
@@ -937,7 +946,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
               e[4] = __float_as_uint(cg);
               e[5] = __float_as_uint(cb);
             }
-            if constexpr (DEPTH) e[6] = __float_as_uint(D);
+            if constexpr (DEPTH) e[kDWord] = __float_as_uint(D);
             active = false;
           }
           if (fits && lane == 0) *(volatile uint32_t*)&pool_n = at + n_g;
@@ -976,7 +985,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
             } else {
               cr = __uint_as_float(ent[3]); cg = __uint_as_float(ent[4]); cb = __uint_as_float(ent[5]);
             }
-            if constexpr (DEPTH) D = __uint_as_float(ent[6]);
+            if constexpr (DEPTH) D = __uint_as_float(ent[kDWord]);
             take_ray(ent[0], ent[1]);
           }
         }
@@ -1090,7 +1099,10 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
       done = last || T < P.min_T;
     }
     if (done) {
-      if constexpr (ENTROPY) {
+      if constexpr (FOOT) {
+        PF->out_entropy[pix] = entropy_add(T, Hs);
+        PF->out_alpha[pix] = 1.0f - T;
+      } else if constexpr (ENTROPY) {
         PE->out_entropy[pix] = entropy_add(T, Hs); // + h(T_end): the ray escapes with what is left
         PE->out_alpha[pix] = 1.0f - T;
       } else {
@@ -1100,10 +1112,13 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
       }
       if constexpr (DEPTH) {
         // image pix / npix of the launch is a sub-sample of view (pix / npix) % nb
-        const CamDev& cam = PD->cams[PD->view_ids[(pix / PD->npix) % PD->nb]];
+        const RenderDepthParams* PZ = nullptr;
+        if constexpr (FOOT) PZ = &PF->z;
+        else PZ = PD;
+        const CamDev& cam = PZ->cams[PZ->view_ids[(pix / PZ->npix) % PZ->nb]];
         const float fx = cam.c2w[2], fy = cam.c2w[6], fz = cam.c2w[10];
         const float inv = 1.0f / sqrtf(fmaf(fx, fx, fmaf(fy, fy, fz * fz)));
-        PD->out_depth[pix] = D * (fmaf(d[0], fx, fmaf(d[1], fy, d[2] * fz)) * inv);
+        PZ->out_depth[pix] = D * (fmaf(d[0], fx, fmaf(d[1], fy, d[2] * fz)) * inv);
       }
       active = false;
     }
@@ -1144,6 +1159,14 @@ void render_entropy_kernel(RenderEntropyParams P) {
   render_queue64_body<F, NDENSE, NGP, false, kRenderEntropy>(P.r, nullptr, &P);
 }
 
+// prv_render_footprint: entropy, opacity and depth in one density-only launch (render_queue64_body, kRenderFootprint), for the
+// (F, NDENSE, NGP) set of the entropy instances; no corner-cache instance.  Waves per SIMD as the entropy instances ask for
+// (scripts/kernel_resources.py prv_kernels.hip render_footprint)
+template <int F, int NDENSE, bool NGP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NDENSE == 0 ? 1 : 3)))
+void render_footprint_kernel(RenderFootprintParams P) {
+  render_queue64_body<F, NDENSE, NGP, false, kRenderFootprint>(P.z.r, nullptr, nullptr, &P);
+}
 
 // ------------------------------------------------------------------ first-hit ray cast (a13)
 // first occupied cell along (o, d) within max_range, or -1: Amanatides-Woo over the occupancy bits
@@ -1911,6 +1934,26 @@ static void launch_render_entropy_mode(const RenderEntropyParams& P, int n_block
 hipError_t launch_render_entropy(const RenderEntropyParams& P, int n_blocks, hipStream_t s) {
   if (P.r.step_mode == PRV_STEP_NGP) launch_render_entropy_mode<true>(P, n_blocks, s);
   else launch_render_entropy_mode<false>(P, n_blocks, s);
+  return hipGetLastError();
+}
+
+template <bool NGP>
+static void launch_render_footprint_mode(const RenderFootprintParams& P, int n_blocks, hipStream_t s) {
+  const int nd = render_instance_dense_levels(P.z.r.field); // (no cached footprint instance either)
+  if (P.z.r.field.n_features == 4) {
+    if (nd == 5) hipLaunchKernelGGL((render_footprint_kernel<4, 5, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
+    else if (nd == 3) hipLaunchKernelGGL((render_footprint_kernel<4, 3, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
+    else hipLaunchKernelGGL((render_footprint_kernel<4, 0, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
+  } else {
+    if (nd == 10) hipLaunchKernelGGL((render_footprint_kernel<2, 10, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
+    else if (nd == 6) hipLaunchKernelGGL((render_footprint_kernel<2, 6, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
+    else hipLaunchKernelGGL((render_footprint_kernel<2, 0, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
+  }
+}
+
+hipError_t launch_render_footprint(const RenderFootprintParams& P, int n_blocks, hipStream_t s) {
+  if (P.z.r.step_mode == PRV_STEP_NGP) launch_render_footprint_mode<true>(P, n_blocks, s);
+  else launch_render_footprint_mode<false>(P, n_blocks, s);
   return hipGetLastError();
 }
 

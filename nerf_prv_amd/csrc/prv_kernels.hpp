@@ -124,6 +124,14 @@ struct RenderEntropyParams {
   float* out_alpha;   // 1 - T_end
 };
 
+// the footprint render (prv_render_footprint, render_footprint_kernel): the entropy render's two planes and the depth render's
+// plane from one density-only launch; z.r.out_f32 / out_u8 are not touched.  All three planes start zeroed
+struct RenderFootprintParams {
+  RenderDepthParams z; // the launch's parameters, the depth plane, and how a ray finds its view's camera
+  float* out_entropy;  // as RenderEntropyParams
+  float* out_alpha;
+};
+
 struct EnsembleParams {
   const uint32_t* imgs[PRV_MAX_MODELS];
   int E;
@@ -154,6 +162,7 @@ hipError_t launch_render(const RenderParams& P, int n_blocks, hipStream_t s);
 hipError_t launch_render_depth(const RenderDepthParams& P, int n_blocks, hipStream_t s);
 hipError_t launch_spp_reduce_depth(const float* stage, size_t n_pixels, int spp, float* out, hipStream_t s);
 hipError_t launch_render_entropy(const RenderEntropyParams& P, int n_blocks, hipStream_t s);
+hipError_t launch_render_footprint(const RenderFootprintParams& P, int n_blocks, hipStream_t s);
 hipError_t launch_score_entropy(const float* entropy, const float* alpha, size_t npix, int n_views, int n_blocks, double* partial,
                                 hipStream_t s);
 int render_instance_dense_levels(const FieldDev& fd); // NDENSE of the render_queue64_kernel<F, NDENSE> instance launch_render picks

@@ -95,6 +95,9 @@ public:
   //             png = the reference's own data flow: per member train_by_instantNGP(it, "100", true, e) writes
   //             render/<it>/ensemble_<e>/rgbaClip_<v>.png, then the planner's loops read the PNGs (main.cpp:2045-2094, 2105-2158)
   bool score_from_pngs = false;
+  // views_per_iteration: 1 (default) = the reference's loop, one view per training round.  k > 1 = k views per round, chosen by
+  //             the selection stage (prv_select_views: greedy, redundancy-aware); method_of_IG 7 with score_path: fused only
+  int views_per_iteration = 1;
   // state
   std::vector<std::vector<double>> pt_sphere;
   double pt_norm = 0;
@@ -166,6 +169,13 @@ public:
         return;
       }
       score_from_pngs = how == "png";
+    }
+    if (fs.has("views_per_iteration")) {
+      views_per_iteration = (int)fs.num("views_per_iteration");
+      if (views_per_iteration < 1) {
+        error = "views_per_iteration must be at least 1";
+        return;
+      }
     }
     // constructor overrides (Share_Data.hpp:402-409)
     if (test_name != "") name_of_pcd = test_name;

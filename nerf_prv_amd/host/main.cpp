@@ -547,8 +547,8 @@ struct HipScorer {
 
   bool save_renders = false; // save_renders: 1 -> the PNG tree the reference's run.py leaves (main.cpp:1676-1684)
 
-  int operator()(int method, int iteration, const std::string& scene_json, const std::string& render_json,
-                 const std::vector<int>& ids, std::vector<double>& scores) {
+  // the members an iteration scores (or selects) with: trained on the scene json's views, saved when the yaml asks
+  int prepare_members(int iteration, const std::string& scene_json) {
     if (train_steps > 0) {
       const int trc = train_members(scene_json);
       if (trc != PRV_OK) return trc;
@@ -561,6 +561,52 @@ struct HipScorer {
           std::cerr << "prv: " << prv_last_error(ctx) << std::endl;
           return -26;
         }
+    }
+    return PRV_OK;
+  }
+
+  // views_per_iteration > 1 (planner.hpp: Selector): train the member, then prv_select_views on the candidates of the render
+  // json -- the footprint render and the greedy rounds; chosen = k candidate ids in selection order
+  int select_grid_res = 0; // yaml select_grid_res / select_alpha_min (0 / negative: prv_select_default_opts')
+  float select_alpha_min = -1.f;
+  int select(int iteration, const std::string& scene_json, const std::string& render_json, const std::vector<int>& ids, int k,
+             std::vector<int>& chosen) {
+    int rc = prepare_members(iteration, scene_json);
+    if (rc != PRV_OK) return rc;
+    prv_camset* cams = nullptr;
+    if (prv_cameras_from_json(ctx, render_json.c_str(), &cams) != PRV_OK) {
+      std::cerr << "prv: " << prv_last_error(ctx) << std::endl;
+      return -20;
+    }
+    const int n = prv_camset_count(cams);
+    const prv_render_opts o = candidate_opts(cams);
+    prv_select_opts so;
+    prv_select_default_opts(&so);
+    so.k = k;
+    if (select_grid_res > 0) so.grid_res = select_grid_res;
+    if (select_alpha_min >= 0.f) so.alpha_min = select_alpha_min;
+    std::vector<int> frames((size_t)std::max(k, 1));
+    std::vector<uint64_t> gains((size_t)std::max(k, 1));
+    rc = n == (int)ids.size() ? prv_select_views(ctx, slot_of(0), cams, nullptr, n, &o, &so, frames.data(), gains.data(), nullptr) : PRV_E_INVALID;
+    prv_camset_destroy(cams);
+    if (rc != PRV_OK) {
+      std::cerr << "prv: " << (n == (int)ids.size() ? prv_last_error(ctx) : "the render json does not hold the candidates") << std::endl;
+      return rc;
+    }
+    chosen.clear();
+    for (int j = 0; j < k; j++) chosen.push_back(ids[(size_t)frames[(size_t)j]]); // frame i of the render json is candidate ids[i]
+    if (dump_records) { // the gains of the round, raw uint64, beside the other diagnostics
+      sd->access_directory(sd->save_path + "/gains");
+      write_text(sd->save_path + "/gains/" + std::to_string(iteration) + ".bin", std::string((const char*)gains.data(), (size_t)k * sizeof(uint64_t)));
+    }
+    return 0;
+  }
+
+  int operator()(int method, int iteration, const std::string& scene_json, const std::string& render_json,
+                 const std::vector<int>& ids, std::vector<double>& scores) {
+    {
+      const int prc = prepare_members(iteration, scene_json);
+      if (prc != PRV_OK) return prc;
     }
     const bool timing = getenv("PRV_PLANNER_TIMING") != nullptr; // dev: where an iteration's seconds go
     const double t_round = now_seconds();
@@ -684,6 +730,11 @@ int PlanningJob::setup(prv_ctx* ctx_, const std::string& cfg, const std::string&
     return -1;
   }
   const int rank = comm ? prv_comm_rank(comm) : 0, world = comm ? prv_comm_world(comm) : 1;
+  if (sd->views_per_iteration > 1 && (!NBV_Net_Labeler::batch_in_scope(method, sd->score_from_pngs) || world > 1)) { // before anything is written
+    std::cerr << "views_per_iteration " << sd->views_per_iteration << " needs method_of_IG 7 (RayEntropy), score_path: fused and one rank "
+                 "(the selection stage is single-rank); nothing was written" << std::endl;
+    return -14;
+  }
   if (rank > 0) sd->relocate_outputs(sd->pre_path + "rank" + std::to_string(rank) + "/"); // same loop, own scratch tree
   FileStorage fs;
   fs.open(cfg);
@@ -821,6 +872,12 @@ int PlanningJob::setup(prv_ctx* ctx_, const std::string& cfg, const std::string&
   // shares the loop's scorer object, so `score_path: png` and the fused path train and render the same members
   HipScorer* engine_state = labeler.scorer.target<HipScorer>();
   state = engine_state;
+  if (engine_state && sd->views_per_iteration > 1) {
+    if (fs.has("select_grid_res")) engine_state->select_grid_res = (int)fs.num("select_grid_res");
+    if (fs.has("select_alpha_min")) engine_state->select_alpha_min = (float)fs.num("select_alpha_min");
+    labeler.selector = [engine_state](int iteration, const std::string& scene, const std::string& render, const std::vector<int>& ids, int k,
+                                      std::vector<int>& chosen) { return engine_state->select(iteration, scene, render, ids, k, chosen); };
+  }
   gt_dev = scorer.gt_dev;
   labeler.engine = [engine_state](const RunPyArgs& a) { return engine_state ? engine_state->run_py(a) : -42; };
   if (sd->score_from_pngs && comm) {

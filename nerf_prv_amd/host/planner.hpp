@@ -6,6 +6,7 @@
 // point-cloud / OctoMap asset preparation, PCL rendering, PRVNet itself (method 4 takes its view budget
 // from a callback or from the file PRVNet's server would have written).
 #pragma once
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -107,6 +108,11 @@ using Scorer = std::function<int(int method, int iteration, const std::string& s
                                  const std::string& render_json, const std::vector<int>& candidate_ids,
                                  std::vector<double>& scores)>;
 
+// `views_per_iteration: k > 1`: choose k of this iteration's candidates in one round (main.cpp: prv_select_views behind it).
+// chosen = k of candidate_ids, in selection order
+using Selector = std::function<int(int iteration, const std::string& scene_json, const std::string& render_json,
+                                   const std::vector<int>& candidate_ids, int k, std::vector<int>& chosen)>;
+
 // What train_by_instantNGP hands run.py (the command line composed at main.cpp:1666-1685), as a struct: the in-process
 // engine behind the boundary receives exactly the reference's arguments.  Empty strings = flag absent.
 struct RunPyArgs {
@@ -183,6 +189,7 @@ public:
   std::shared_ptr<Share_Data> share_data;
   std::shared_ptr<View_Space> view_space;
   Scorer scorer;
+  Selector selector;  // views_per_iteration > 1 only
   Engine engine;      // the in-process run.py behind train_by_instantNGP's reference signature
   EvalFn evaluator;   // empty: `evaluate: 1` is ignored
   std::function<int(const std::string&)> geometry_evaluator; // `evaluate_geometry: 1`: writes the geometry file named, beside every metrics/<it>.txt
@@ -282,6 +289,10 @@ public:
     return method == RandomIterative || method == EnsembleRGB || method == EnsembleRGBDensity || method == PSNRCoverage || method == RayEntropy;
   }
 
+  // `views_per_iteration: k > 1` rests on the footprint render of the single-model entropy score: RayEntropy on the fused path
+  // only.  Anything else is refused BEFORE the loop writes anything, as method_in_scope refuses.
+  static bool batch_in_scope(int method, bool score_from_pngs) { return method == RayEntropy && !score_from_pngs; }
+
   // main.cpp:1718-2277 for methods 0, 2, 3 (and 5 and 7, this build's single-model scores); chosen views in `chosen_nbvs`.
   // The loop is three resumable pieces -- nbv_begin (everything before the reference's `while (true)`), nbv_prepare (an
   // iteration's json / render_json and the termination test, :1885-1966) and nbv_decide (score, pick, movement cost,
@@ -315,6 +326,15 @@ public:
                    "RandomOneshot = 1 and PVBCoverage = 4 belong to the reference's PRVNet pipeline, outside this build's scope; "
                    "nothing was written" << std::endl;
       return -10;
+    }
+    if (sd.views_per_iteration > 1 && !batch_in_scope(sd.method_of_IG, sd.score_from_pngs)) {
+      std::cerr << "nbv_loop: views_per_iteration " << sd.views_per_iteration << " needs method_of_IG 7 (RayEntropy) and score_path: fused, not method "
+                << sd.method_of_IG << (sd.score_from_pngs ? " with score_path: png" : "") << "; nothing was written" << std::endl;
+      return -14;
+    }
+    if (sd.views_per_iteration > 1 && !selector) {
+      std::cerr << "nbv_loop: views_per_iteration " << sd.views_per_iteration << " needs a selector; nothing was written" << std::endl;
+      return -15;
     }
     { // :1735-1747: the methods run with the view budget a method-4 run of the REFERENCE left behind, when there is one
       std::ifstream fin(sd.pre_path + "Compare/ShapeNet/" + sd.name_of_pcd + "_m4_v1_t" + std::to_string(test_id) + "/view_budget.txt");
@@ -368,7 +388,9 @@ public:
     run.render_json = sd.save_path + "/render_json/" + it + ".json";
     write_text(run.scene_json, prvjson::to_styled_string(now_nbvs_json));     // :1918-1920
     write_text(run.render_json, prvjson::to_styled_string(now_render_json)); // :1922-1924
-    if (run.iteration == sd.num_of_max_iteration || run.candidates.empty()) { // :1946-1966
+    // (views_per_iteration > 1: the loop ends at the same TOTAL number of views as the one-view loop, whatever the round count)
+    const bool budget_spent = sd.views_per_iteration > 1 ? (int)chosen_nbvs.size() - 1 >= sd.num_of_max_iteration : run.iteration == sd.num_of_max_iteration;
+    if (budget_spent || run.candidates.empty()) { // :1946-1966
       const double loops_time = now_seconds() - run.loop_t0;
       write_text(sd.save_path + "/run_time.txt", std::to_string(loops_time) + "\n");
       if (sd.evaluate && evaluator) { // "final evaluating..." (:1954-1965): metrics/<it>.txt in run.py's format
@@ -393,6 +415,7 @@ public:
   // score the prepared iteration's candidates, keep the arg-max, account for the movement (:1969-2264); -> 0 or an error
   int nbv_decide() {
     Share_Data& sd = *share_data;
+    if (sd.views_per_iteration > 1) return nbv_decide_batch();
     const int n_views = (int)view_space->views.size();
     const std::vector<int>& candidates = run.candidates;
     const int iteration = run.iteration;
@@ -453,6 +476,40 @@ public:
     total_movement_cost += local_path.second;
     write_text(sd.save_path + "/movement/" + it + ".txt",
                std::to_string(next_view_id) + "\t" + std::to_string(local_path.second) + "\t" + std::to_string(total_movement_cost) + "\n");
+    run.iteration++;
+    return 0;
+  }
+
+  // views_per_iteration > 1: the selector names k of the prepared iteration's candidates (the last round fewer, if the view
+  // budget or the candidates run out); they are appended in selection order and the movement is the chain of local paths
+  // through them in that order.  The per-round files keep their formats: movement/<it>.txt holds one line per view.
+  int nbv_decide_batch() {
+    Share_Data& sd = *share_data;
+    const std::vector<int>& candidates = run.candidates;
+    const std::string it = std::to_string(run.iteration);
+    const int left = sd.num_of_max_iteration - ((int)chosen_nbvs.size() - 1);
+    const int k = std::min(std::min(sd.views_per_iteration, left), (int)candidates.size());
+    if (k < 1 || !selector) return -15;
+    const double infer_t0 = now_seconds();
+    std::vector<int> picked;
+    const int rc = selector(run.iteration, run.scene_json, run.render_json, candidates, k, picked);
+    write_text(sd.save_path + "/train_time/" + it + ".txt", std::to_string(now_seconds() - infer_t0) + "\n"); // (score_candidates' file)
+    if (rc != 0) return rc;
+    if ((int)picked.size() != k) return -11;
+    std::set<int> seen;
+    for (int v : picked)
+      if (std::find(candidates.begin(), candidates.end(), v) == candidates.end() || !seen.insert(v).second) return -11;
+    write_text(sd.save_path + "/infer_time/" + it + ".txt", std::to_string(now_seconds() - infer_t0) + "\n");
+    std::string movement;
+    for (int next_view_id : picked) {
+      const auto local_path = get_local_path(view_space->views[chosen_nbvs.back()].init_pos, view_space->views[next_view_id].init_pos,
+                                             view_space->object_center_world + Vec3(1e-10, 1e-10, 1e-10), view_space->predicted_size);
+      total_movement_cost += local_path.second;
+      movement += std::to_string(next_view_id) + "\t" + std::to_string(local_path.second) + "\t" + std::to_string(total_movement_cost) + "\n";
+      chosen_nbvs.push_back(next_view_id);
+      run.chosen_nbvs_set.insert(next_view_id);
+    }
+    write_text(sd.save_path + "/movement/" + it + ".txt", movement);
     run.iteration++;
     return 0;
   }
