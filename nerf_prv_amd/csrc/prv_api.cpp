@@ -749,9 +749,9 @@ int timed(prv_ctx* c, std::vector<hipEvent_t>& events, Launch launch) {
 
 
 // which render_queue64 instance and relocation policy a launch gets (results are identical either way)
-// has_cached_instance: the launch can run the corner-cache instance (the colour render; the entropy render has none, and the
-// relocation that pays only WITH the cache must not be switched on for it)
-void render_policy(prv_ctx* c, const Model& m, size_t npix, bool ngp, RenderParams& rp, bool has_cached_instance = true) {
+// has_cached_instance: the launch can run the corner-cache instance (the colour render; the plane renders have none, and the
+// relocation that pays only WITH the cache must not be switched on for them)
+void render_policy(prv_ctx* c, const Model& m, size_t npix, bool ngp, RenderParams& rp, bool has_cached_instance) {
   // Tail merge + the block's tail pool raise slot utilisation (0.77 -> 0.93) at the price of incoherent gathers from the
   // relocated rays.  That pays where the gathers of a fresh cohort are coherent to begin with and the table is cache
   // resident -- large images of the 256^3 field: launch -8 % -- and costs elsewhere: the 512^3 field is bound by random
@@ -775,9 +775,9 @@ void render_policy(prv_ctx* c, const Model& m, size_t npix, bool ngp, RenderPara
   rp.pool_on = (c->pool_on >= 0 ? c->pool_on != 0 : (coherent || cached)) && rp.merge_max > 0;
 }
 
-// the render launch over one queue the march filled (q: its records, counts and images; queue_head: its heads)
+// the render launch over one queue the march filled (q: its records, counts and images; queue_head: its heads), in mode kRender*
 RenderParams render_params(prv_ctx* c, const Model& m, const prv_render_opts* o, const MarchLayout& L, uint32_t seg_cap,
-                           const MarchMember& q, uint32_t* queue_head, unsigned long long* stat) {
+                           const MarchMember& q, uint32_t* queue_head, unsigned long long* stat, int mode) {
   RenderParams rp;
   memset(&rp, 0, sizeof(rp));
   rp.field = m.dev;
@@ -795,20 +795,30 @@ RenderParams render_params(prv_ctx* c, const Model& m, const prv_render_opts* o,
   rp.min_T = o->min_transmittance;
   rp.last_pass = o->spp == 1;
   memcpy(rp.bg, o->background, sizeof(rp.bg));
-  render_policy(c, m, (size_t)o->width * o->height, o->step_mode == PRV_STEP_NGP, rp);
+  render_policy(c, m, (size_t)o->width * o->height, o->step_mode == PRV_STEP_NGP, rp, mode == kRenderColour);
   return rp;
 }
 
-// The render of one batch of views into out_f32 (+ optional out_u8).  Views are dealt to
-// the queue in batches so the queue stays within queue_budget bytes.  out_depth (prv_render_depth): the views' depth images
-// as well, n_views * H * W floats, through the depth instances of the render kernel; null: the colour render alone.
-// out_entropy + out_alpha (prv_render_entropy, PRV_SCORE_RAY_ENTROPY; out_f32 and out_u8 null): no colour at all -- the march
-// and the entropy kernel, which writes these two planes of n_views * H * W floats.  out_entropy AND out_depth
-// (prv_render_footprint): the march and the footprint kernel, which writes all three planes.
-int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views,
-                 const prv_render_opts* o, float* out_f32, uint8_t* out_u8, bool zero_stats, bool private_output = false,
-                 float* out_depth = nullptr, float* out_entropy = nullptr, float* out_alpha = nullptr) {
-  if (o->spp != 1 || out_u8 || out_depth) private_output = false; // sub-sample staging, byte and depth images are written in full
+// what render_views writes, n_views images each.  mode says which of the pointers are looked at:
+//   kRenderColour    (prv_render, prv_render_rgba8, the scores): rgba (+ optional rgba8)
+//   kRenderDepth     (prv_render_depth):     rgba and depth, through the depth instances of the planes kernel
+//   kRenderEntropy   (prv_render_entropy, PRV_SCORE_RAY_ENTROPY): no colour at all -- the march and the planes kernel, which writes entropy and alpha
+//   kRenderFootprint (prv_render_footprint): as kRenderEntropy, and depth from the same launch
+struct RenderTargets {
+  int mode = kRenderColour;
+  float* rgba = nullptr;    // H * W * 4 floats per view
+  uint8_t* rgba8 = nullptr; // H * W * 4 bytes per view
+  float *depth = nullptr, *entropy = nullptr, *alpha = nullptr; // H * W floats per view
+  bool zero_stats = true;      // the call starts a new statistics window
+  bool private_output = false; // the caller consumes rgba / the planes through the views' cull rectangles only
+};
+
+// The render of n_views views into t.  Views are dealt to the queue in batches so the queue stays within queue_budget bytes.
+int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, const prv_render_opts* o,
+                 const RenderTargets& t) {
+  const bool colour = t.mode == kRenderColour || t.mode == kRenderDepth; // the launch writes an RGBA image
+  const bool depth = t.mode == kRenderDepth || t.mode == kRenderFootprint;
+  const bool private_output = t.private_output && o->spp == 1 && !t.rgba8 && !depth; // sub-sample staging, byte and depth images are written in full
   const Model& m = c->models[slot];
   const int W = o->width, H = o->height, spp = o->spp;
   const size_t npix = (size_t)W * H;
@@ -819,7 +829,7 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
   uint32_t* q_count = (uint32_t*)c->counters.p + kMaxSegments * 16;
   unsigned long long* stat = (unsigned long long*)((char*)c->counters.p + kStatOffset);
   if (n_views == 0) {
-    if (zero_stats) HIPCHK(c, hipMemsetAsync(stat, 0, kCountersBytes - kStatOffset, c->stream));
+    if (t.zero_stats) HIPCHK(c, hipMemsetAsync(stat, 0, kCountersBytes - kStatOffset, c->stream));
     return PRV_OK;
   }
   Upload up;
@@ -832,8 +842,20 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
   const size_t slot_bytes = kRecordBytes + (ngp ? kExtBytes : 0); // NGP: every queue slot has its mask-extension slot
   size_t batch = std::max<size_t>(1, c->queue_budget / (npix * slot_bytes * (size_t)spp));
   batch = std::min<size_t>(batch, (size_t)n_views);
-  const bool footprint = out_entropy && out_depth;
-  const size_t stage_px = footprint ? 4 + 4 + 4 : out_entropy ? 4 + 4 : out_depth ? 16 + 4 : 16; // staging bytes per sub-sample pixel: RGBA (+ depth), or entropy + opacity
+  // the launch's scalar planes, in the order they are reduced: where the plane goes, where its sub-samples are staged, and the
+  // kernel parameter that carries it.  The march writes none of them: every pixel starts at 0, which is what a dead ray contributes
+  struct Plane {
+    float* out;
+    Buffer* stage;
+    float* RenderPlanesParams::*slot;
+  } planes[3];
+  int n_planes = 0;
+  if (!colour) { // H where the depth render's depth would go, the opacity where the colour would
+    planes[n_planes++] = {t.entropy, &c->stage_depth, &RenderPlanesParams::out_entropy};
+    planes[n_planes++] = {t.alpha, &c->stage, &RenderPlanesParams::out_alpha};
+  }
+  if (depth) planes[n_planes++] = {t.depth, colour ? &c->stage_depth : &c->stage_foot, &RenderPlanesParams::out_depth};
+  const size_t stage_px = (colour ? 16 : 0) + 4 * (size_t)n_planes; // staging bytes per sub-sample pixel
   if (spp > 1) batch = std::min<size_t>(batch, std::max<size_t>(1, c->stage_budget / (npix * stage_px * (size_t)spp)));
   if (batch * npix * (size_t)spp >= (1ull << 32)) batch = ((1ull << 32) - 1) / (npix * (size_t)spp); // 32-bit pixel ids
   if (batch == 0) return fail(c, PRV_E_INVALID, "image x spp too large");
@@ -842,30 +864,23 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
   if (seg_cap_max * (size_t)L.n_seg >= (1ull << 32)) return fail(c, PRV_E_INVALID, "image x spp too large");
   if ((rc = ensure(c, c->queue, seg_cap_max * (size_t)L.n_seg * kRecordBytes)) != PRV_OK) return rc;
   if (ngp && (rc = ensure(c, c->queue_ext, seg_cap_max * (size_t)L.n_seg * kExtBytes)) != PRV_OK) return rc;
-  if (spp > 1 && (rc = ensure(c, c->stage, batch * npix * (size_t)spp * (out_entropy ? 4 : 16))) != PRV_OK) return rc;
-  if (spp > 1 && (out_depth || out_entropy) && (rc = ensure(c, c->stage_depth, batch * npix * (size_t)spp * 4)) != PRV_OK) return rc;
-  if (spp > 1 && footprint && (rc = ensure(c, c->stage_foot, batch * npix * (size_t)spp * 4)) != PRV_OK) return rc;
+  if (spp > 1 && colour && (rc = ensure(c, c->stage, batch * npix * (size_t)spp * 16)) != PRV_OK) return rc;
+  for (int i = 0; i < n_planes && spp > 1; i++)
+    if ((rc = ensure(c, *planes[i].stage, batch * npix * (size_t)spp * 4)) != PRV_OK) return rc;
 
   const int n_blocks = render_blocks(c, m, npix);
   for (size_t b0 = 0; b0 < (size_t)n_views; b0 += batch) {
     const int nb = (int)std::min(batch, (size_t)n_views - b0);
-    float* dst_f32 = out_f32 ? out_f32 + b0 * npix * 4 : nullptr;
-    uint32_t* dst_u8 = out_u8 ? (uint32_t*)out_u8 + b0 * npix : nullptr;
-    float* dst_depth = out_depth ? out_depth + b0 * npix : nullptr;
-    float* depth_target = spp > 1 ? (float*)(footprint ? c->stage_foot.p : c->stage_depth.p) : dst_depth;
-    // the march writes no depth: every pixel starts at 0, which is what a dead ray contributes
-    if (out_depth) HIPCHK(c, hipMemsetAsync(depth_target, 0, (size_t)nb * npix * (size_t)spp * 4, c->stream));
-    // the entropy render's planes: H where the depth would go, the opacity where the colour would (sub-samples: their staging)
-    float* dst_entropy = out_entropy ? out_entropy + b0 * npix : nullptr;
-    float* dst_alpha = out_entropy ? out_alpha + b0 * npix : nullptr;
-    float* entropy_target = spp > 1 ? (float*)c->stage_depth.p : dst_entropy;
-    float* alpha_target = spp > 1 ? (float*)c->stage.p : dst_alpha;
-    if (out_entropy) { // nor does it write these: a dead ray's entropy and opacity are 0
-      HIPCHK(c, hipMemsetAsync(entropy_target, 0, (size_t)nb * npix * (size_t)spp * 4, c->stream));
-      HIPCHK(c, hipMemsetAsync(alpha_target, 0, (size_t)nb * npix * (size_t)spp * 4, c->stream));
+    float* dst_f32 = t.rgba ? t.rgba + b0 * npix * 4 : nullptr;
+    uint32_t* dst_u8 = t.rgba8 ? (uint32_t*)t.rgba8 + b0 * npix : nullptr;
+    float *dst[3], *target[3]; // the batch's part of each plane, and what the kernel writes: that, or the sub-samples' staging
+    for (int i = 0; i < n_planes; i++) {
+      dst[i] = planes[i].out + b0 * npix;
+      target[i] = spp > 1 ? (float*)planes[i].stage->p : dst[i];
+      HIPCHK(c, hipMemsetAsync(target[i], 0, (size_t)nb * npix * (size_t)spp * 4, c->stream));
     }
     // one fill per batch: heads and counts, and with them the statistics when this call starts a new window
-    HIPCHK(c, hipMemsetAsync(c->counters.p, 0, b0 == 0 && zero_stats ? kCountersBytes : kStatOffset, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->counters.p, 0, b0 == 0 && t.zero_stats ? kCountersBytes : kStatOffset, c->stream));
     MarchParams mp;
     march_common(mp, c, L, o, up, b0, (size_t)nb, stat);
     mp.field = m.dev;
@@ -874,7 +889,7 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
     mp.queue = c->queue.p;
     mp.queue_ext = (uint4*)c->queue_ext.p;
     mp.queue_count = q_count;
-    mp.out_f32 = out_entropy ? nullptr : spp > 1 ? (float*)c->stage.p : dst_f32;
+    mp.out_f32 = !colour ? nullptr : spp > 1 ? (float*)c->stage.p : dst_f32;
     mp.out_u8 = spp > 1 ? nullptr : dst_u8;
     // A caller that consumes the image through the views' cull rectangles (prv_score_views, method 5: the image is a private
     // temporary of the round) gets only the tiles inside them launched and nothing written outside: most of an 800x800
@@ -898,56 +913,21 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
       mp.live_tiles_max = (uint32_t)live_max;
     }
     if ((rc = timed(c, c->ev_march, [&] { HIPCHK(c, launch_march(mp, nb, spp, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
-    const RenderParams rp = render_params(c, m, o, L, mp.seg_cap, {mp.queue, mp.queue_ext, mp.queue_count, mp.out_f32, mp.out_u8}, q_head, stat);
-    if (footprint) {
-      RenderFootprintParams fp;
-      memset(&fp, 0, sizeof(fp));
-      fp.z.r = rp;
-      render_policy(c, m, npix, ngp, fp.z.r, false);
-      fp.z.out_depth = depth_target;
-      fp.z.cams = mp.cams;
-      fp.z.view_ids = mp.view_ids;
-      fp.z.npix = (uint32_t)npix;
-      fp.z.nb = (uint32_t)nb;
-      fp.out_entropy = entropy_target;
-      fp.out_alpha = alpha_target;
-      if ((rc = timed(c, c->ev_render, [&] { HIPCHK(c, launch_render_footprint(fp, n_blocks, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
-      if (spp > 1) {
-        HIPCHK(c, launch_spp_reduce_depth(entropy_target, (size_t)nb * npix, spp, dst_entropy, c->stream));
-        HIPCHK(c, launch_spp_reduce_depth(alpha_target, (size_t)nb * npix, spp, dst_alpha, c->stream));
-        HIPCHK(c, launch_spp_reduce_depth(depth_target, (size_t)nb * npix, spp, dst_depth, c->stream));
-      }
-      continue;
-    }
-    if (out_entropy) {
-      RenderEntropyParams ep;
-      memset(&ep, 0, sizeof(ep));
-      ep.r = rp;
-      render_policy(c, m, npix, ngp, ep.r, false);
-      ep.out_entropy = entropy_target;
-      ep.out_alpha = alpha_target;
-      if ((rc = timed(c, c->ev_render, [&] { HIPCHK(c, launch_render_entropy(ep, n_blocks, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
-      if (spp > 1) {
-        HIPCHK(c, launch_spp_reduce_depth(entropy_target, (size_t)nb * npix, spp, dst_entropy, c->stream));
-        HIPCHK(c, launch_spp_reduce_depth(alpha_target, (size_t)nb * npix, spp, dst_alpha, c->stream));
-      }
-      continue;
-    }
-    if (out_depth) {
-      RenderDepthParams dp;
-      memset(&dp, 0, sizeof(dp));
-      dp.r = rp;
-      dp.out_depth = depth_target;
-      dp.cams = mp.cams;
-      dp.view_ids = mp.view_ids;
-      dp.npix = (uint32_t)npix;
-      dp.nb = (uint32_t)nb;
-      if ((rc = timed(c, c->ev_render, [&] { HIPCHK(c, launch_render_depth(dp, n_blocks, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
-    } else {
-      if ((rc = timed(c, c->ev_render, [&] { HIPCHK(c, launch_render(rp, n_blocks, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
-    }
-    if (spp > 1) HIPCHK(c, launch_spp_reduce((const float*)c->stage.p, (size_t)nb * npix, spp, o->background, dst_f32, dst_u8, c->stream));
-    if (spp > 1 && out_depth) HIPCHK(c, launch_spp_reduce_depth((const float*)c->stage_depth.p, (size_t)nb * npix, spp, dst_depth, c->stream));
+    RenderPlanesParams pp;
+    memset(&pp, 0, sizeof(pp));
+    pp.r = render_params(c, m, o, L, mp.seg_cap, {mp.queue, mp.queue_ext, mp.queue_count, mp.out_f32, mp.out_u8}, q_head, stat, t.mode);
+    for (int i = 0; i < n_planes; i++) pp.*planes[i].slot = target[i];
+    pp.cams = mp.cams;
+    pp.view_ids = mp.view_ids;
+    pp.npix = (uint32_t)npix;
+    pp.nb = (uint32_t)nb;
+    if ((rc = timed(c, c->ev_render, [&] {
+           HIPCHK(c, n_planes ? launch_render_planes(pp, t.mode, n_blocks, c->stream) : launch_render(pp.r, n_blocks, c->stream));
+           return PRV_OK;
+         })) != PRV_OK)
+      return rc;
+    if (spp > 1 && colour) HIPCHK(c, launch_spp_reduce((const float*)c->stage.p, (size_t)nb * npix, spp, o->background, dst_f32, dst_u8, c->stream));
+    for (int i = 0; i < n_planes && spp > 1; i++) HIPCHK(c, launch_spp_reduce_depth(target[i], (size_t)nb * npix, spp, dst[i], c->stream));
   }
   return PRV_OK;
 }
@@ -1054,7 +1034,7 @@ int render_ensemble_ngp(prv_ctx* c, const int* slots, int E, const prv_camset* c
     const Model& m = c->models[slots[e]];
     const int n_blocks = render_blocks(c, m, npix);
     uint32_t* q_head = (uint32_t*)((char*)c->counters_multi.p + (size_t)e * kStatOffset);
-    const RenderParams rp = render_params(c, m, o, L, mp.seg_cap, mp.mem[e], q_head, stat);
+    const RenderParams rp = render_params(c, m, o, L, mp.seg_cap, mp.mem[e], q_head, stat, kRenderColour);
     if ((rc = timed(c, c->ev_render, [&] { HIPCHK(c, launch_render(rp, n_blocks, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
     if (spp > 1)
       HIPCHK(c, launch_spp_reduce((const float*)mp.mem[e].out_f32, (size_t)n_views * npix, spp, o->background, scratch_f32, (uint32_t*)out_u8[e], c->stream));
@@ -1075,6 +1055,31 @@ int fetch_stats(prv_ctx* c, const prv_render_opts* o, int n_views, int n_models,
   st->samples_live = 0;
   for (int s = 0; s < 8; s++) st->samples_live += ev[8 * (1 + s)]; // the march pass's sharded counter
   return PRV_OK;
+}
+
+// What the five prv_render* entry points share: the argument checks in their order, then render_views and the statistics.
+// outs: the output pointers to verify, in order; missing: a required one is null (bad: that error's text);
+// scratch: the image the mode writes whether or not the caller wants it -- null: the context's scratch, scratch_px bytes a pixel
+struct NamedPtr {
+  const void* p;
+  const char* name;
+};
+int render_entry(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, const prv_render_opts* o, prv_stats* st,
+                 RenderTargets t, std::initializer_list<NamedPtr> outs, bool missing, const char* bad,
+                 float* RenderTargets::*scratch = nullptr, size_t scratch_px = 0) {
+  if (!c) return PRV_E_INVALID;
+  int rc;
+  if ((rc = check_model(c, slot)) != PRV_OK || (rc = check_opts(c, o)) != PRV_OK) return rc;
+  if (!cs || n_views < 0 || (missing && n_views > 0)) return fail(c, PRV_E_INVALID, "%s", bad);
+  HIPCHK(c, hipSetDevice(c->device));
+  for (const NamedPtr& out : outs)
+    if ((rc = check_device_ptr(c, out.p, out.name)) != PRV_OK) return rc;
+  if (scratch && !(t.*scratch) && n_views > 0) {
+    if ((rc = ensure(c, c->img_f32, (size_t)n_views * o->width * o->height * scratch_px)) != PRV_OK) return rc;
+    t.*scratch = (float*)c->img_f32.p;
+  }
+  if ((rc = render_views(c, slot, cs, view_ids, n_views, o, t)) != PRV_OK) return rc;
+  return fetch_stats(c, o, n_views, 1, st);
 }
 
 int score_blocks(size_t npix) { return (int)std::min<size_t>(64, std::max<size_t>(1, (npix + 4095) / 4096)); }
@@ -1623,78 +1628,50 @@ void prv_camset_destroy(prv_camset* cs) { delete cs; }
 
 int prv_render(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, const prv_render_opts* o,
                float* out, prv_stats* st) try {
-  if (!c) return PRV_E_INVALID;
-  int rc;
-  if ((rc = check_model(c, slot)) != PRV_OK || (rc = check_opts(c, o)) != PRV_OK) return rc;
-  if (!cs || n_views < 0 || (!out && n_views > 0)) return fail(c, PRV_E_INVALID, "bad camset / view count / output");
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = check_device_ptr(c, out, "out_rgba_dev")) != PRV_OK) return rc;
-  if ((rc = render_views(c, slot, cs, view_ids, n_views, o, out, nullptr, true)) != PRV_OK) return rc;
-  return fetch_stats(c, o, n_views, 1, st);
+  RenderTargets t;
+  t.rgba = out;
+  return render_entry(c, slot, cs, view_ids, n_views, o, st, t, {{out, "out_rgba_dev"}}, !out, "bad camset / view count / output");
 } catch (...) { return caught(c); }
 
 int prv_render_rgba8(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views,
                      const prv_render_opts* o, uint8_t* out, prv_stats* st) try {
-  if (!c) return PRV_E_INVALID;
-  int rc;
-  if ((rc = check_model(c, slot)) != PRV_OK || (rc = check_opts(c, o)) != PRV_OK) return rc;
-  if (!cs || n_views < 0 || (!out && n_views > 0)) return fail(c, PRV_E_INVALID, "bad camset / view count / output");
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = check_device_ptr(c, out, "out_rgba8_dev")) != PRV_OK) return rc;
-  const size_t npix = (size_t)o->width * o->height;
-  if ((rc = ensure(c, c->img_f32, std::max<size_t>(16, (size_t)n_views * npix * 16))) != PRV_OK) return rc;
-  if ((rc = render_views(c, slot, cs, view_ids, n_views, o, (float*)c->img_f32.p, out, true)) != PRV_OK) return rc;
-  return fetch_stats(c, o, n_views, 1, st);
+  RenderTargets t; // the float image the kernel writes beside the bytes goes to the context's scratch
+  t.rgba8 = out;
+  return render_entry(c, slot, cs, view_ids, n_views, o, st, t, {{out, "out_rgba8_dev"}}, !out, "bad camset / view count / output",
+                      &RenderTargets::rgba, 16);
 } catch (...) { return caught(c); }
 
 int prv_render_depth(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, const prv_render_opts* o,
                      float* out_rgba, float* out_depth, prv_stats* st) try {
-  if (!c) return PRV_E_INVALID;
-  int rc;
-  if ((rc = check_model(c, slot)) != PRV_OK || (rc = check_opts(c, o)) != PRV_OK) return rc;
-  if (!cs || n_views < 0 || (!out_depth && n_views > 0)) return fail(c, PRV_E_INVALID, "bad camset / view count / depth output");
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = check_device_ptr(c, out_depth, "out_depth_dev")) != PRV_OK) return rc;
-  if ((rc = check_device_ptr(c, out_rgba, "out_rgba_dev")) != PRV_OK) return rc;
-  if (!out_rgba && n_views > 0) { // the colour is rendered anyway (the opacity terminates the rays): into the context's scratch
-    if ((rc = ensure(c, c->img_f32, (size_t)n_views * o->width * o->height * 16)) != PRV_OK) return rc;
-    out_rgba = (float*)c->img_f32.p;
-  }
-  if ((rc = render_views(c, slot, cs, view_ids, n_views, o, out_rgba, nullptr, true, false, out_depth)) != PRV_OK) return rc;
-  return fetch_stats(c, o, n_views, 1, st);
+  RenderTargets t; // a null out_rgba: the colour is rendered anyway (the opacity terminates the rays), into the context's scratch
+  t.mode = kRenderDepth;
+  t.rgba = out_rgba;
+  t.depth = out_depth;
+  return render_entry(c, slot, cs, view_ids, n_views, o, st, t, {{out_depth, "out_depth_dev"}, {out_rgba, "out_rgba_dev"}}, !out_depth,
+                      "bad camset / view count / depth output", &RenderTargets::rgba, 16);
 } catch (...) { return caught(c); }
 
 int prv_render_entropy(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, const prv_render_opts* o,
                        float* out_entropy, float* out_alpha, prv_stats* st) try {
-  if (!c) return PRV_E_INVALID;
-  int rc;
-  if ((rc = check_model(c, slot)) != PRV_OK || (rc = check_opts(c, o)) != PRV_OK) return rc;
-  if (!cs || n_views < 0 || (!out_entropy && n_views > 0)) return fail(c, PRV_E_INVALID, "bad camset / view count / entropy output");
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = check_device_ptr(c, out_entropy, "out_entropy_dev")) != PRV_OK) return rc;
-  if ((rc = check_device_ptr(c, out_alpha, "out_alpha_dev")) != PRV_OK) return rc;
-  if (!out_alpha && n_views > 0) { // the kernel writes the opacity anyway: into the context's scratch
-    if ((rc = ensure(c, c->img_f32, (size_t)n_views * o->width * o->height * 4)) != PRV_OK) return rc;
-    out_alpha = (float*)c->img_f32.p;
-  }
-  if ((rc = render_views(c, slot, cs, view_ids, n_views, o, nullptr, nullptr, true, false, nullptr, out_entropy, out_alpha)) != PRV_OK) return rc;
-  return fetch_stats(c, o, n_views, 1, st);
+  RenderTargets t; // a null out_alpha: the kernel writes the opacity anyway, into the context's scratch
+  t.mode = kRenderEntropy;
+  t.entropy = out_entropy;
+  t.alpha = out_alpha;
+  return render_entry(c, slot, cs, view_ids, n_views, o, st, t, {{out_entropy, "out_entropy_dev"}, {out_alpha, "out_alpha_dev"}}, !out_entropy,
+                      "bad camset / view count / entropy output", &RenderTargets::alpha, 4);
 } catch (...) { return caught(c); }
 
 int prv_render_footprint(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, const prv_render_opts* o,
                          float* out_entropy, float* out_alpha, float* out_depth, prv_stats* st) try {
-  if (!c) return PRV_E_INVALID;
-  int rc;
-  if ((rc = check_model(c, slot)) != PRV_OK || (rc = check_opts(c, o)) != PRV_OK) return rc;
-  if (!cs || n_views < 0 || ((!out_entropy || !out_alpha || !out_depth) && n_views > 0))
-    return fail(c, PRV_E_INVALID, "bad camset / view count / footprint output (entropy, alpha and depth planes are all required)");
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = check_device_ptr(c, out_entropy, "out_entropy_dev")) != PRV_OK) return rc;
-  if ((rc = check_device_ptr(c, out_alpha, "out_alpha_dev")) != PRV_OK) return rc;
-  if ((rc = check_device_ptr(c, out_depth, "out_depth_dev")) != PRV_OK) return rc;
-  if (n_views == 0) out_entropy = out_alpha = out_depth = nullptr;
-  if ((rc = render_views(c, slot, cs, view_ids, n_views, o, nullptr, nullptr, true, false, out_depth, out_entropy, out_alpha)) != PRV_OK) return rc;
-  return fetch_stats(c, o, n_views, 1, st);
+  RenderTargets t;
+  t.mode = kRenderFootprint;
+  t.entropy = out_entropy;
+  t.alpha = out_alpha;
+  t.depth = out_depth;
+  return render_entry(c, slot, cs, view_ids, n_views, o, st, t,
+                      {{out_entropy, "out_entropy_dev"}, {out_alpha, "out_alpha_dev"}, {out_depth, "out_depth_dev"}},
+                      !out_entropy || !out_alpha || !out_depth,
+                      "bad camset / view count / footprint output (entropy, alpha and depth planes are all required)");
 } catch (...) { return caught(c); }
 
 int prv_first_hit(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, int W, int H,
@@ -1908,7 +1885,9 @@ int prv_evaluate(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
   if ((rc = check_device_ptr(c, gt, "gt_rgba_dev")) != PRV_OK) return rc;
   const size_t npix = (size_t)o->width * o->height;
   if ((rc = ensure(c, c->img_f32, (size_t)n_views * npix * 16)) != PRV_OK) return rc;
-  if ((rc = render_views(c, slot, cs, view_ids, n_views, o, (float*)c->img_f32.p, nullptr, true)) != PRV_OK) return rc;
+  RenderTargets t;
+  t.rgba = (float*)c->img_f32.p;
+  if ((rc = render_views(c, slot, cs, view_ids, n_views, o, t)) != PRV_OK) return rc;
   std::vector<double> ps(n_views), ss(n_views);
   if ((rc = prv_evaluate_images(c, (const float*)c->img_f32.p, gt, n_views, o->width, o->height, o->background, ps.data(), ss.data())) != PRV_OK)
     return rc;
@@ -1948,7 +1927,12 @@ int prv_score_views(prv_ctx* c, int method, const int* model_slots, int n_models
     // outside a view's cull rectangle need not be launched), one reduce sums both
     float* hp = (float*)c->img_f32.p;
     float* ap = hp + (size_t)n_views * npix;
-    if ((rc = render_views(c, model_slots[0], cs, view_ids, n_views, o, nullptr, nullptr, true, o->spp == 1, nullptr, hp, ap)) != PRV_OK) return rc;
+    RenderTargets t;
+    t.mode = kRenderEntropy;
+    t.entropy = hp;
+    t.alpha = ap;
+    t.private_output = o->spp == 1;
+    if ((rc = render_views(c, model_slots[0], cs, view_ids, n_views, o, t)) != PRV_OK) return rc;
     if (n_views) {
       const int nblk = score_blocks(npix);
       if ((rc = ensure(c, c->partial, (size_t)n_views * nblk * 2 * sizeof(double))) != PRV_OK) return rc;
@@ -1965,15 +1949,22 @@ int prv_score_views(prv_ctx* c, int method, const int* model_slots, int n_models
     }
     bool one_march = false; // the engine's rule, an ensemble size with an instance: ONE march launch for all members
     if ((rc = render_ensemble_ngp(c, model_slots, n_models, cs, view_ids, n_views, o, (float*)c->img_f32.p, out8, &one_march)) != PRV_OK) return rc;
-    for (int e = 0; e < n_models && !one_march; e++)
-      if ((rc = render_views(c, model_slots[e], cs, view_ids, n_views, o, (float*)c->img_f32.p, out8[e], e == 0)) != PRV_OK) return rc;
+    for (int e = 0; e < n_models && !one_march; e++) {
+      RenderTargets t;
+      t.rgba = (float*)c->img_f32.p;
+      t.rgba8 = out8[e];
+      t.zero_stats = e == 0;
+      if ((rc = render_views(c, model_slots[e], cs, view_ids, n_views, o, t)) != PRV_OK) return rc;
+    }
     if (n_views && (rc = score_ensemble_dev(c, method, imgs, n_models, n_views, npix, rec)) != PRV_OK) return rc;
   } else {
     // the image is a private temporary of the round: only the tiles inside each view's cull rectangle are rendered and
     // the score reads it through the same rectangles (view i of this call = camera i of the upload in c->view_ids)
     const bool priv = o->spp == 1;
-    if ((rc = render_views(c, model_slots[0], cs, view_ids, n_views, o, (float*)c->img_f32.p, nullptr, true, priv)) != PRV_OK)
-      return rc;
+    RenderTargets t;
+    t.rgba = (float*)c->img_f32.p;
+    t.private_output = priv;
+    if ((rc = render_views(c, model_slots[0], cs, view_ids, n_views, o, t)) != PRV_OK) return rc;
     if (n_views && (rc = score_psnr_dev(c, (const float*)c->img_f32.p, gt, n_views, npix, o->background, c->coverage_weight, rec,
                                         priv ? (const CamDev*)c->view_ids.p : nullptr, o->width)) != PRV_OK)
       return rc;

@@ -725,23 +725,21 @@ __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
 // (the hardware log takes no denormals), and so does p = 0
 __device__ __forceinline__ float entropy_add(float p, float H) { return p >= 1.17549435e-38f ? fmaf(p, -__builtin_amdgcn_logf(p), H) : H; }
 
-// The body of render_queue64_kernel, render_depth_kernel and render_entropy_kernel.
+// The body of render_queue64_kernel (kRenderColour, X null) and render_planes_kernel (the other modes; X: its planes).
 // kRenderDepth: the ray also sums D = sum_i w_i t_i (w_i = the
-// sample's compositing weight, t_i its ray parameter) and writes z = D * dot(d, f) to PD->out_depth[pix] when it ends
+// sample's compositing weight, t_i its ray parameter) and writes z = D * dot(d, f) to X->out_depth[pix] when it ends
 // (f = the view's normalised forward axis, column 2 of its c2w: z-depth along the optical axis, premultiplied by opacity);
-// the ray's dynamic state that tail merge and pool move between lanes gains a 7th word, D.  PD is unused otherwise.
+// the ray's dynamic state that tail merge and pool move between lanes gains a 7th word, D.
 // kRenderEntropy: the density layers alone (mlp_density2: the colour kernel's first 16 MFMAs in its order, so sigma, alpha
 // and T are its bits), no SH rows, no colour sums; the ray sums H = sum_i h(w_i) and adds h(T) when it ends, and writes H and
-// 1 - T to PE->out_entropy[pix] / PE->out_alpha[pix].  Its movable state is four words, {record, next sample, T, H}; only
-// the 8 density fragment sets are staged in LDS.  P.out_f32 / out_u8 are not touched.  PE is unused otherwise.
+// 1 - T to X->out_entropy[pix] / X->out_alpha[pix].  Its movable state is four words, {record, next sample, T, H}; only
+// the 8 density fragment sets are staged in LDS.  P.out_f32 / out_u8 are not touched.
 // kRenderFootprint (prv_render_footprint): the entropy mode plus the depth mode's one FMA per sample -- D = fmaf(w, t, D) in the
-// depth kernel's place, t kept live across mlp_density2 -- and z = D * dot(d, f) to PF->out_depth[pix] at ray end, formed as
+// depth mode's place, t kept live across mlp_density2 -- and z = D * dot(d, f) to X->out_depth[pix] at ray end, formed as
 // kRenderDepth forms it.  sigma, alpha and T are the colour kernel's bits in density-only mode already, so H and 1 - T are
-// render_entropy_kernel's bits and z is render_depth_kernel's.  Movable state: five words, {record, next sample, T, H, D}.
-enum : int { kRenderColour = 0, kRenderDepth = 1, kRenderEntropy = 2, kRenderFootprint = 3 };
+// the entropy mode's bits and z is the depth mode's.  Movable state: five words, {record, next sample, T, H, D}.
 template <int F, int NDENSE, bool NGP, bool CACHE, int MODE>
-__device__ __forceinline__ void render_queue64_body(RenderParams P, const RenderDepthParams* PD, const RenderEntropyParams* PE = nullptr,
-                                                    const RenderFootprintParams* PF = nullptr) {
+__device__ __forceinline__ void render_queue64_body(RenderParams P, const RenderPlanesParams* X) {
   constexpr bool FOOT = MODE == kRenderFootprint;
   constexpr bool DEPTH = MODE == kRenderDepth || FOOT, ENTROPY = MODE == kRenderEntropy || FOOT; // DEPTH: the D sum; ENTROPY: density layers only, the H sum
   constexpr int kDWord = FOOT ? 4 : 6;                          // where D sits in the movable state
@@ -1099,26 +1097,21 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
       done = last || T < P.min_T;
     }
     if (done) {
-      if constexpr (FOOT) {
-        PF->out_entropy[pix] = entropy_add(T, Hs);
-        PF->out_alpha[pix] = 1.0f - T;
-      } else if constexpr (ENTROPY) {
-        PE->out_entropy[pix] = entropy_add(T, Hs); // + h(T_end): the ray escapes with what is left
-        PE->out_alpha[pix] = 1.0f - T;
-      } else {
+      if constexpr (!ENTROPY) {
         const float4 v = make_float4(cr, cg, cb, 1.0f - T);
         reinterpret_cast<float4*>(P.out_f32)[pix] = v;
         if (P.last_pass && P.out_u8) P.out_u8[pix] = quantize_rgba8(v.x, v.y, v.z, v.w, P.bg);
       }
+      if constexpr (ENTROPY) {
+        X->out_entropy[pix] = entropy_add(T, Hs); // + h(T_end): the ray escapes with what is left
+        X->out_alpha[pix] = 1.0f - T;
+      }
       if constexpr (DEPTH) {
         // image pix / npix of the launch is a sub-sample of view (pix / npix) % nb
-        const RenderDepthParams* PZ = nullptr;
-        if constexpr (FOOT) PZ = &PF->z;
-        else PZ = PD;
-        const CamDev& cam = PZ->cams[PZ->view_ids[(pix / PZ->npix) % PZ->nb]];
+        const CamDev& cam = X->cams[X->view_ids[(pix / X->npix) % X->nb]];
         const float fx = cam.c2w[2], fy = cam.c2w[6], fz = cam.c2w[10];
         const float inv = 1.0f / sqrtf(fmaf(fx, fx, fmaf(fy, fy, fz * fz)));
-        PZ->out_depth[pix] = D * (fmaf(d[0], fx, fmaf(d[1], fy, d[2] * fz)) * inv);
+        X->out_depth[pix] = D * (fmaf(d[0], fx, fmaf(d[1], fy, d[2] * fz)) * inv);
       }
       active = false;
     }
@@ -1139,33 +1132,16 @@ void render_queue64_kernel(RenderParams P) {
   render_queue64_body<F, NDENSE, NGP, CACHE, kRenderColour>(P, nullptr);
 }
 
-// prv_render_depth: the render with the depth sum (render_queue64_body, DEPTH), for the (F, NDENSE) set of the colour
-// instances; no corner-cache instance.  Waves per SIMD as the colour instances ask for: no spills at either
-// (scripts/kernel_resources.py prv_kernels.hip render_depth)
-template <int F, int NDENSE, bool NGP>
+// prv_render_depth / prv_render_entropy / prv_render_footprint: the render that writes scalar planes (render_queue64_body,
+// MODE = kRenderDepth / kRenderEntropy / kRenderFootprint), for the (F, NDENSE) set of the colour instances; no corner-cache
+// instance.  Waves per SIMD as the colour instances ask for.  Depth: no spills at either.  Entropy and footprint: without the
+// colour MLP's accumulators, SH rows and colour sums the dense-level instances take 122-130 registers (colour: 160-168; three
+// waves, the F = 2 ones under the engine's rule four), the all-hashed ones 183-218 (two waves), none spills a VGPR
+// (scripts/kernel_resources.py prv_kernels.hip render_planes)
+template <int F, int NDENSE, bool NGP, int MODE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NDENSE == 0 ? 1 : 3)))
-void render_depth_kernel(RenderDepthParams P) {
-  render_queue64_body<F, NDENSE, NGP, false, kRenderDepth>(P.r, &P);
-}
-
-// prv_render_entropy: the density-only render (render_queue64_body, kRenderEntropy), for the (F, NDENSE) set of the colour
-// instances; no corner-cache instance.  Waves per SIMD as the colour instances ask for.  Without the colour MLP's
-// accumulators, SH rows and colour sums the dense-level instances take 122-130 registers (colour: 160-168; three waves, the
-// F = 2 ones under the engine's rule four), the all-hashed ones 183-218 (two waves), none spills a VGPR
-// (scripts/kernel_resources.py prv_kernels.hip render_entropy)
-template <int F, int NDENSE, bool NGP>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NDENSE == 0 ? 1 : 3)))
-void render_entropy_kernel(RenderEntropyParams P) {
-  render_queue64_body<F, NDENSE, NGP, false, kRenderEntropy>(P.r, nullptr, &P);
-}
-
-// prv_render_footprint: entropy, opacity and depth in one density-only launch (render_queue64_body, kRenderFootprint), for the
-// (F, NDENSE, NGP) set of the entropy instances; no corner-cache instance.  Waves per SIMD as the entropy instances ask for
-// (scripts/kernel_resources.py prv_kernels.hip render_footprint)
-template <int F, int NDENSE, bool NGP>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NDENSE == 0 ? 1 : 3)))
-void render_footprint_kernel(RenderFootprintParams P) {
-  render_queue64_body<F, NDENSE, NGP, false, kRenderFootprint>(P.z.r, nullptr, nullptr, &P);
+void render_planes_kernel(RenderPlanesParams P) {
+  render_queue64_body<F, NDENSE, NGP, false, MODE>(P.r, &P);
 }
 
 // ------------------------------------------------------------------ first-hit ray cast (a13)
@@ -1462,7 +1438,7 @@ __global__ __launch_bounds__(256) void score_psnr_kernel(PsnrParams P) {
   }
 }
 
-// PRV_SCORE_RAY_ENTROPY: the sums of a view's entropy and opacity images (render_entropy_kernel's, dead pixels 0), two
+// PRV_SCORE_RAY_ENTROPY: the sums of a view's entropy and opacity images (the entropy render's, dead pixels 0), two
 // partial sums per block
 __global__ __launch_bounds__(256) void score_entropy_kernel(const float* __restrict__ entropy, const float* __restrict__ alpha,
                                                             size_t npix, double* __restrict__ partial) {
@@ -1860,35 +1836,17 @@ hipError_t launch_march_multi(const MarchMultiParams& P, int n_views, int n_spp,
   return hipGetLastError();
 }
 
-// compiled instances of the field-evaluating kernels (render, depth, mesh, field hook): NDENSE = the field's count of leading dense levels when an
-// instance for exactly that count exists (5 / 3 for F = 4, 10 / 6 for F = 2: api.FIELD_256 / FIELD_512 run <4,5> / <2,10>) and its hashed levels share their hash
-// constants; any other field -- util.SMALL (4 dense), SMALL_F2 (9), instant-ngp's base.json (F = 2, 5 dense), levels > 16 MiB -- runs <F, 0> (tests/instances.py)
-int render_instance_dense_levels(const FieldDev& fd) {
-  const int n = fd.n_dense_levels;
-  if (!fd.hash_shared) return 0;
-  if (fd.n_features == 4) return n == 5 ? 5 : n == 3 ? 3 : 0;
-  return n == 10 ? 10 : n == 6 ? 6 : 0;
-}
-
 template <bool NGP>
 static void launch_render_mode(const RenderParams& P, int n_blocks, hipStream_t s) {
-  const int nd = render_instance_dense_levels(P.field);
-  if (P.cell_cache && nd > 0) { // the caller asked for the per-lane corner cache (prv_api.cpp: render_policy says when)
-    if (P.field.n_features == 4 && nd == 5) {
-      hipLaunchKernelGGL((render_queue64_kernel<4, 5, NGP, true>), dim3(n_blocks), dim3(256), 0, s, P);
-      return;
-    }
-    // (the F = 2 fields have six hashed levels: their cache does not fit 256 registers -- 128 spilled -- so they run without)
+  // the caller asked for the per-lane corner cache (prv_api.cpp: render_policy says when).  Only <4, 5> has the instance
+  // (the F = 2 fields have six hashed levels: their cache does not fit 256 registers -- 128 spilled -- so they run without)
+  if (P.cell_cache && P.field.n_features == 4 && render_instance_dense_levels(P.field) == 5) {
+    hipLaunchKernelGGL((render_queue64_kernel<4, 5, NGP, true>), dim3(n_blocks), dim3(256), 0, s, P);
+    return;
   }
-  if (P.field.n_features == 4) {
-    if (nd == 5) hipLaunchKernelGGL((render_queue64_kernel<4, 5, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-    else if (nd == 3) hipLaunchKernelGGL((render_queue64_kernel<4, 3, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-    else hipLaunchKernelGGL((render_queue64_kernel<4, 0, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-  } else {
-    if (nd == 10) hipLaunchKernelGGL((render_queue64_kernel<2, 10, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-    else if (nd == 6) hipLaunchKernelGGL((render_queue64_kernel<2, 6, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-    else hipLaunchKernelGGL((render_queue64_kernel<2, 0, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-  }
+  with_field_instance(P.field, [&](auto f, auto nd) {
+    hipLaunchKernelGGL((render_queue64_kernel<decltype(f)::value, decltype(nd)::value, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
+  });
 }
 
 hipError_t launch_render(const RenderParams& P, int n_blocks, hipStream_t s) {
@@ -1897,63 +1855,20 @@ hipError_t launch_render(const RenderParams& P, int n_blocks, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <bool NGP>
-static void launch_render_depth_mode(const RenderDepthParams& P, int n_blocks, hipStream_t s) {
-  const int nd = render_instance_dense_levels(P.r.field); // (P.r.cell_cache is not looked at: no cached depth instance)
-  if (P.r.field.n_features == 4) {
-    if (nd == 5) hipLaunchKernelGGL((render_depth_kernel<4, 5, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-    else if (nd == 3) hipLaunchKernelGGL((render_depth_kernel<4, 3, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-    else hipLaunchKernelGGL((render_depth_kernel<4, 0, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-  } else {
-    if (nd == 10) hipLaunchKernelGGL((render_depth_kernel<2, 10, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-    else if (nd == 6) hipLaunchKernelGGL((render_depth_kernel<2, 6, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-    else hipLaunchKernelGGL((render_depth_kernel<2, 0, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-  }
+template <int MODE>
+static void launch_render_planes_mode(const RenderPlanesParams& P, int n_blocks, hipStream_t s) {
+  with_field_instance(P.r.field, [&](auto f, auto nd) { // (P.r.cell_cache is not looked at: no cached planes instance)
+    constexpr int F = decltype(f)::value, ND = decltype(nd)::value;
+    if (P.r.step_mode == PRV_STEP_NGP) hipLaunchKernelGGL((render_planes_kernel<F, ND, true, MODE>), dim3(n_blocks), dim3(256), 0, s, P);
+    else hipLaunchKernelGGL((render_planes_kernel<F, ND, false, MODE>), dim3(n_blocks), dim3(256), 0, s, P);
+  });
 }
 
-hipError_t launch_render_depth(const RenderDepthParams& P, int n_blocks, hipStream_t s) {
-  if (P.r.step_mode == PRV_STEP_NGP) launch_render_depth_mode<true>(P, n_blocks, s);
-  else launch_render_depth_mode<false>(P, n_blocks, s);
-  return hipGetLastError();
-}
-
-template <bool NGP>
-static void launch_render_entropy_mode(const RenderEntropyParams& P, int n_blocks, hipStream_t s) {
-  const int nd = render_instance_dense_levels(P.r.field); // (no cached entropy instance either)
-  if (P.r.field.n_features == 4) {
-    if (nd == 5) hipLaunchKernelGGL((render_entropy_kernel<4, 5, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-    else if (nd == 3) hipLaunchKernelGGL((render_entropy_kernel<4, 3, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-    else hipLaunchKernelGGL((render_entropy_kernel<4, 0, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-  } else {
-    if (nd == 10) hipLaunchKernelGGL((render_entropy_kernel<2, 10, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-    else if (nd == 6) hipLaunchKernelGGL((render_entropy_kernel<2, 6, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-    else hipLaunchKernelGGL((render_entropy_kernel<2, 0, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-  }
-}
-
-hipError_t launch_render_entropy(const RenderEntropyParams& P, int n_blocks, hipStream_t s) {
-  if (P.r.step_mode == PRV_STEP_NGP) launch_render_entropy_mode<true>(P, n_blocks, s);
-  else launch_render_entropy_mode<false>(P, n_blocks, s);
-  return hipGetLastError();
-}
-
-template <bool NGP>
-static void launch_render_footprint_mode(const RenderFootprintParams& P, int n_blocks, hipStream_t s) {
-  const int nd = render_instance_dense_levels(P.z.r.field); // (no cached footprint instance either)
-  if (P.z.r.field.n_features == 4) {
-    if (nd == 5) hipLaunchKernelGGL((render_footprint_kernel<4, 5, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-    else if (nd == 3) hipLaunchKernelGGL((render_footprint_kernel<4, 3, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-    else hipLaunchKernelGGL((render_footprint_kernel<4, 0, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-  } else {
-    if (nd == 10) hipLaunchKernelGGL((render_footprint_kernel<2, 10, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-    else if (nd == 6) hipLaunchKernelGGL((render_footprint_kernel<2, 6, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-    else hipLaunchKernelGGL((render_footprint_kernel<2, 0, NGP>), dim3(n_blocks), dim3(256), 0, s, P);
-  }
-}
-
-hipError_t launch_render_footprint(const RenderFootprintParams& P, int n_blocks, hipStream_t s) {
-  if (P.z.r.step_mode == PRV_STEP_NGP) launch_render_footprint_mode<true>(P, n_blocks, s);
-  else launch_render_footprint_mode<false>(P, n_blocks, s);
+hipError_t launch_render_planes(const RenderPlanesParams& P, int mode, int n_blocks, hipStream_t s) {
+  if (mode == kRenderDepth) launch_render_planes_mode<kRenderDepth>(P, n_blocks, s);
+  else if (mode == kRenderEntropy) launch_render_planes_mode<kRenderEntropy>(P, n_blocks, s);
+  else if (mode == kRenderFootprint) launch_render_planes_mode<kRenderFootprint>(P, n_blocks, s);
+  else return hipErrorInvalidValue;
   return hipGetLastError();
 }
 
@@ -2049,16 +1964,9 @@ hipError_t launch_debug_raygen(const CamDev& cam, int W, int H, int spp_k, float
 hipError_t launch_debug_field(const FieldDev& fd, const float* pos, const float* dir, int n, uint16_t* feat,
                               float* out36, int32_t* occ, hipStream_t s) {
   const unsigned blocks64 = (unsigned)((n + 255) / 256);
-  const int nd = render_instance_dense_levels(fd);
-  if (fd.n_features == 4) {
-    if (nd == 5) hipLaunchKernelGGL((debug_field64_kernel<4, 5>), dim3(blocks64), dim3(256), 0, s, fd, pos, dir, n, feat, out36, occ);
-    else if (nd == 3) hipLaunchKernelGGL((debug_field64_kernel<4, 3>), dim3(blocks64), dim3(256), 0, s, fd, pos, dir, n, feat, out36, occ);
-    else hipLaunchKernelGGL((debug_field64_kernel<4, 0>), dim3(blocks64), dim3(256), 0, s, fd, pos, dir, n, feat, out36, occ);
-  } else {
-    if (nd == 10) hipLaunchKernelGGL((debug_field64_kernel<2, 10>), dim3(blocks64), dim3(256), 0, s, fd, pos, dir, n, feat, out36, occ);
-    else if (nd == 6) hipLaunchKernelGGL((debug_field64_kernel<2, 6>), dim3(blocks64), dim3(256), 0, s, fd, pos, dir, n, feat, out36, occ);
-    else hipLaunchKernelGGL((debug_field64_kernel<2, 0>), dim3(blocks64), dim3(256), 0, s, fd, pos, dir, n, feat, out36, occ);
-  }
+  with_field_instance(fd, [&](auto f, auto nd) {
+    hipLaunchKernelGGL((debug_field64_kernel<decltype(f)::value, decltype(nd)::value>), dim3(blocks64), dim3(256), 0, s, fd, pos, dir, n, feat, out36, occ);
+  });
   return hipGetLastError();
 }
 

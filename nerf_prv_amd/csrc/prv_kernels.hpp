@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/prv.h"
 #include "prv_device.hpp"
+#include <type_traits>
 
 namespace prv {
 
@@ -105,31 +106,26 @@ struct RenderParams {
   float bg[4];
 };
 
-// the depth render (prv_render_depth, render_depth_kernel): the colour launch's parameters, untouched, plus where the depth
-// goes and how a ray finds its view's camera
-struct RenderDepthParams {
+// what a launch renders: the colour image, or scalar planes (render_planes_kernel's MODE)
+enum : int { kRenderColour = 0, kRenderDepth = 1, kRenderEntropy = 2, kRenderFootprint = 3 };
+
+// the plane-writing renders (render_planes_kernel): the colour launch's parameters, untouched, plus one float per pixel of
+// the launch's images (r.out_f32 / 4) per plane.  A plane starts zeroed, which is what a dead ray contributes.
+//   kRenderDepth (prv_render_depth):         the colour image and out_depth
+//   kRenderEntropy (prv_render_entropy):     out_entropy and out_alpha; r.out_f32 / out_u8 are not touched
+//   kRenderFootprint (prv_render_footprint): all three planes from one density-only launch; r.out_f32 / out_u8 are not touched
+struct RenderPlanesParams {
   RenderParams r;
-  float* out_depth;     // one float per pixel of the launch's images (r.out_f32 / 4): premultiplied z-depth, engine units
-  const CamDev* cams;   // image i of the launch (i = pix / npix; sub-sample i / nb of view i % nb) is seen by cams[view_ids[i % nb]]
+  float* out_depth; // premultiplied z-depth, engine units           (null where the mode does not write the plane)
+  // depth / footprint, how a ray finds its view's camera: image i of the launch (i = pix / npix; sub-sample i / nb of view
+  // i % nb) is seen by cams[view_ids[i % nb]]
+  const CamDev* cams;
   const int* view_ids;
-  uint32_t npix;        // W * H
-  uint32_t nb;          // views in the launch
-};
-
-// the entropy render (prv_render_entropy, render_entropy_kernel): the colour launch's queue, field and policy (its images are
-// not touched) and the two planes a ray writes when it ends; both start zeroed, which is what a dead ray contributes
-struct RenderEntropyParams {
-  RenderParams r;
-  float* out_entropy; // one float per pixel of the launch's images: H, bits
+  uint32_t npix; // W * H
+  uint32_t nb;   // views in the launch
+  // the entropy planes come last: in front of the depth fields they cost the all-hashed footprint instance 7 more SGPR spills
+  float* out_entropy; // H, bits
   float* out_alpha;   // 1 - T_end
-};
-
-// the footprint render (prv_render_footprint, render_footprint_kernel): the entropy render's two planes and the depth render's
-// plane from one density-only launch; z.r.out_f32 / out_u8 are not touched.  All three planes start zeroed
-struct RenderFootprintParams {
-  RenderDepthParams z; // the launch's parameters, the depth plane, and how a ray finds its view's camera
-  float* out_entropy;  // as RenderEntropyParams
-  float* out_alpha;
 };
 
 struct EnsembleParams {
@@ -159,13 +155,35 @@ hipError_t launch_march(const MarchParams& P, int n_views, int n_spp, hipStream_
 hipError_t launch_spp_reduce(const float* stage, size_t n_pixels, int spp, const float bg[4], float* out, uint32_t* out_u8,
                              hipStream_t s);
 hipError_t launch_render(const RenderParams& P, int n_blocks, hipStream_t s);
-hipError_t launch_render_depth(const RenderDepthParams& P, int n_blocks, hipStream_t s);
+hipError_t launch_render_planes(const RenderPlanesParams& P, int mode, int n_blocks, hipStream_t s); // mode: kRenderDepth / Entropy / Footprint
 hipError_t launch_spp_reduce_depth(const float* stage, size_t n_pixels, int spp, float* out, hipStream_t s);
-hipError_t launch_render_entropy(const RenderEntropyParams& P, int n_blocks, hipStream_t s);
-hipError_t launch_render_footprint(const RenderFootprintParams& P, int n_blocks, hipStream_t s);
 hipError_t launch_score_entropy(const float* entropy, const float* alpha, size_t npix, int n_views, int n_blocks, double* partial,
                                 hipStream_t s);
-int render_instance_dense_levels(const FieldDev& fd); // NDENSE of the render_queue64_kernel<F, NDENSE> instance launch_render picks
+// compiled instances of the field-evaluating kernels (render, planes, mesh, field hook): NDENSE = the field's count of leading dense levels when an
+// instance for exactly that count exists (5 / 3 for F = 4, 10 / 6 for F = 2: api.FIELD_256 / FIELD_512 run <4,5> / <2,10>) and its hashed levels share their hash
+// constants; any other field -- util.SMALL (4 dense), SMALL_F2 (9), instant-ngp's base.json (F = 2, 5 dense), levels > 16 MiB -- runs <F, 0> (tests/instances.py)
+inline int render_instance_dense_levels(const FieldDev& fd) {
+  const int n = fd.n_dense_levels;
+  if (!fd.hash_shared) return 0;
+  if (fd.n_features == 4) return n == 5 ? 5 : n == 3 ? 3 : 0;
+  return n == 10 ? 10 : n == 6 ? 6 : 0;
+}
+// calls fn(std::integral_constant<int, F>{}, std::integral_constant<int, NDENSE>{}) for the one compiled instance fd runs on:
+// the only list of the six (F, NDENSE) pairs a kernel template is instantiated for
+template <class Fn>
+void with_field_instance(const FieldDev& fd, Fn&& fn) {
+  using std::integral_constant;
+  const int nd = render_instance_dense_levels(fd);
+  if (fd.n_features == 4) {
+    if (nd == 5) fn(integral_constant<int, 4>{}, integral_constant<int, 5>{});
+    else if (nd == 3) fn(integral_constant<int, 4>{}, integral_constant<int, 3>{});
+    else fn(integral_constant<int, 4>{}, integral_constant<int, 0>{});
+  } else {
+    if (nd == 10) fn(integral_constant<int, 2>{}, integral_constant<int, 10>{});
+    else if (nd == 6) fn(integral_constant<int, 2>{}, integral_constant<int, 6>{});
+    else fn(integral_constant<int, 2>{}, integral_constant<int, 0>{});
+  }
+}
 struct PreceptPose {
   double w2c[16], c2w[16];
 };

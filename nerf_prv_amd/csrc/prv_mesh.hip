@@ -281,18 +281,9 @@ size_t mesh_scan_scratch(size_t n) {
 hipError_t launch_mesh_density(const FieldDev& fd, const MeshGrid& g, int use_occ, int brick, float* sigma, hipStream_t s) {
   const uint32_t waves = brick ? (uint32_t)(((g.res[0] + 3) / 4) * ((g.res[1] + 3) / 4) * ((g.res[2] + 3) / 4)) : (uint32_t)mesh_waves(g);
   const unsigned blocks = (waves + 3) / 4;
-  const int nd = render_instance_dense_levels(fd);
-#define PRV_DENSITY(FF, ND) hipLaunchKernelGGL((mesh_density_kernel<FF, ND>), dim3(blocks), dim3(256), 0, s, fd, g, use_occ, brick, waves, sigma)
-  if (fd.n_features == 4) {
-    if (nd == 5) PRV_DENSITY(4, 5);
-    else if (nd == 3) PRV_DENSITY(4, 3);
-    else PRV_DENSITY(4, 0);
-  } else {
-    if (nd == 10) PRV_DENSITY(2, 10);
-    else if (nd == 6) PRV_DENSITY(2, 6);
-    else PRV_DENSITY(2, 0);
-  }
-#undef PRV_DENSITY
+  with_field_instance(fd, [&](auto f, auto nd) {
+    hipLaunchKernelGGL((mesh_density_kernel<decltype(f)::value, decltype(nd)::value>), dim3(blocks), dim3(256), 0, s, fd, g, use_occ, brick, waves, sigma);
+  });
   return hipGetLastError();
 }
 
@@ -337,18 +328,9 @@ hipError_t launch_mesh_triangles(const MeshGrid& g, const uint8_t* flags, const 
 hipError_t launch_mesh_colors(const FieldDev& fd, const float* xyz, const float* nrm, uint64_t nv, uint8_t* rgb, hipStream_t s) {
   if (nv == 0) return hipSuccess;
   const unsigned blocks = (unsigned)((nv + 255) / 256);
-  const int nd = render_instance_dense_levels(fd);
-#define PRV_COLORS(FF, ND) hipLaunchKernelGGL((mesh_color_kernel<FF, ND>), dim3(blocks), dim3(256), 0, s, fd, xyz, nrm, nv, rgb)
-  if (fd.n_features == 4) {
-    if (nd == 5) PRV_COLORS(4, 5);
-    else if (nd == 3) PRV_COLORS(4, 3);
-    else PRV_COLORS(4, 0);
-  } else {
-    if (nd == 10) PRV_COLORS(2, 10);
-    else if (nd == 6) PRV_COLORS(2, 6);
-    else PRV_COLORS(2, 0);
-  }
-#undef PRV_COLORS
+  with_field_instance(fd, [&](auto f, auto nd) {
+    hipLaunchKernelGGL((mesh_color_kernel<decltype(f)::value, decltype(nd)::value>), dim3(blocks), dim3(256), 0, s, fd, xyz, nrm, nv, rgb);
+  });
   return hipGetLastError();
 }
 

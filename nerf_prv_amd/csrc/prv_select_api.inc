@@ -114,7 +114,12 @@ int prv_select_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view
   float* ent = (float*)c->sel_planes.p;
   float* alp = ent + n;
   float* dep = alp + n;
-  if ((rc = render_views(c, slot, cs, view_ids, n_views, o, nullptr, nullptr, true, false, dep, ent, alp)) != PRV_OK) return rc;
+  RenderTargets t;
+  t.mode = kRenderFootprint;
+  t.entropy = ent;
+  t.alpha = alp;
+  t.depth = dep;
+  if ((rc = render_views(c, slot, cs, view_ids, n_views, o, t)) != PRV_OK) return rc;
   if ((rc = fetch_stats(c, o, n_views, 1, st)) != PRV_OK) return rc;
   return select_rounds(c, cs, view_ids, n_views, o->width, o->height, ent, alp, dep, so, chosen_out, gains_out, nullptr, nullptr);
 } catch (...) { return caught(c); }

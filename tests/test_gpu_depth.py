@@ -1,4 +1,4 @@
-"""Depth rendering (prv_render_depth, render_depth_kernel) on the GPU: parity with the CPU restatement of the oracle's march
+"""Depth rendering (prv_render_depth, render_planes_kernel in kRenderDepth mode) on the GPU: parity with the CPU restatement of the oracle's march
 (tests/depth_ref.py), bit-identity of its colour with prv_render, a known answer independent of the oracle, invariance under
 the render policies, errors, and the run.py surfaces (Testbed render_mode = Depth, the server's --screenshot_depth)."""
 import ctypes as C

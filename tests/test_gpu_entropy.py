@@ -1,4 +1,4 @@
-"""Ray entropy on the GPU (prv_render_entropy, render_entropy_kernel, PRV_SCORE_RAY_ENTROPY, prv_planner method 7): the opacity is
+"""Ray entropy on the GPU (prv_render_entropy, render_planes_kernel in kRenderEntropy mode, PRV_SCORE_RAY_ENTROPY, prv_planner method 7): the opacity is
 prv_render's bit for bit, the entropy is the CPU restatement's (tests/entropy_ref.py) on every compiled field instance, a fast
 instance equals the generic one, calls are deterministic, the fused scoring round is the mean of the image, and the planner
 picks the arg-max of those scores.

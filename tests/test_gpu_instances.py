@@ -1,5 +1,5 @@
 """Everything that is compiled once per (F, NDENSE) field instance -- the feature gather, the field hook
-(debug_field64_kernel), the colour and depth renders (render_queue64_kernel, render_depth_kernel) and the mesh kernels
+(debug_field64_kernel), the colour and depth renders (render_queue64_kernel, render_planes_kernel) and the mesh kernels
 (mesh_density_kernel, mesh_color_kernel) -- on every instance and on every reason for falling back to the generic one:
 the field matrix of tests/instances.py.  util.SMALL and util.SMALL_F2, which the other parity modules use, select the
 generic instances <4,0> and <2,0>; the fast instances <4,5>, <4,3>, <2,10>, <2,6> (paired dense loads, shared hash

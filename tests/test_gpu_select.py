@@ -1,4 +1,5 @@
-"""Several next views per round on the GPU: the footprint render (prv_render_footprint, render_footprint_kernel) is the entropy
+"""Several next views per round on the GPU: the footprint render (prv_render_footprint, render_planes_kernel in
+kRenderFootprint mode) is the entropy
 render's and the depth render's bytes on every compiled field instance; the selection stage (prv_select_from_images,
 prv_select_views: select_footprint_kernel, select_gain_kernel, select_mark_kernel) equals the float32 / exact-integer
 restatement of tests/select_ref.py word for word; prv_planner with views_per_iteration > 1 takes several views per training
@@ -61,6 +62,35 @@ def test_footprint_is_the_entropy_and_depth_renders_bit_for_bit(ctx, inst, cams3
     for k in STAT_KEYS:
         assert getattr(st, k) == getattr(st_e, k) == getattr(st_d, k), k
     assert (ent0.cpu().numpy() > 0).any() and (depth0.cpu().numpy() > 0).any()
+
+
+@pytest.mark.parametrize("mode", [0, 1], ids=["fixed", "ngp"])
+def test_footprint_batches_equal_one_batch(oracle, monkeypatch, mode):
+    """A 1 MiB queue budget deals the three views to the queue in several batches: the engine's rule needs 1320 px x 3 x 208 B =
+    823,680 B per view (one view per batch), the fixed rule 380,160 B (two views, then one).  Every plane then crosses a batch
+    boundary at a non-zero first view, through its staging and its reduce: same bytes, same statistics."""
+    opts = api.render_opts(FW, FH, 96 if mode == 0 else 0, 3, 1e-4, step_mode=mode)
+    tms, scale, offset = util.hemisphere_transforms(oracle, util.fibonacci_hemisphere(6))
+
+    def footprint():
+        c = api.Context(0)
+        try:
+            c.synthetic_model(0, api.field_desc(**util.SMALL), util.SEED_A)
+            cs = c.cameras_from_matrices(tms[[0, 2, 5]], util.FOV_X, FW, FH, scale, offset)
+            ent, alpha, depth, st = c.render_footprint(0, cs, None, opts)
+            cs.close()
+            return [_u32(t).tobytes() for t in (ent, alpha, depth)], [getattr(st, k) for k in STAT_KEYS], ent.cpu().numpy(), depth.cpu().numpy()
+        finally:
+            c.close()
+
+    monkeypatch.delenv("PRV_QUEUE_MB", raising=False)
+    planes, stats, ent, depth = footprint()
+    monkeypatch.setenv("PRV_QUEUE_MB", "1")
+    planes1, stats1, _, _ = footprint()
+    for name, a, b in zip(("entropy", "alpha", "depth"), planes, planes1):
+        assert a == b, name
+    assert stats == stats1
+    assert all((ent[v] > 0).any() and (depth[v] > 0).any() for v in range(3))  # every batch rendered something
 
 
 # ---- select_from_images on synthetic planes, no render
