@@ -279,6 +279,23 @@ int prv_quantize_rgba8(prv_ctx* ctx, const float* rgba_dev, size_t n_pixels, con
 int prv_render_footprint(prv_ctx* ctx, int model_slot, const prv_camset* cs, const int* view_ids, int n_views,
                          const prv_render_opts* opts, float* out_entropy_dev, float* out_alpha_dev, float* out_depth_dev,
                          prv_stats* stats);
+/* Entropy, opacity and a FIRST-CROSSING depth of the same views from one density-only launch (this build's own; the opt-in
+ * locator of the selection stage below, the "median depth" of the NeRF toolkits at level 0.5).  Per ray (every spp sub-sample),
+ * over exactly the samples and early termination prv_render_entropy walks, with T_i' = T after sample i (T * (1 - alpha_i)):
+ *   Dm = t_i of the first sample with T_i' <= 1.0f - level (one float32 subtraction on the host, one compare per sample),
+ *        or 0 when the ray ends above that; t_i > 0 for every sample, so Dm > 0 says the level was reached;
+ *   z = Dm * dot(d, f), the forward cosine exactly as prv_render_depth forms it;  hit = Dm > 0 ? 1 : 0.
+ * Unlike the expected depth, z always lies on a sample at which the ray really stops.  All four planes are n_views*h*w
+ * float32 and all four are required.  The pixel of each plane is the sum of its sub-samples in order, times 1/spp: out_depth_dev
+ * is the mean over ALL sub-samples of z (0 where the sub-sample did not hit), out_hit_dev the share of sub-samples that hit, so
+ * depth / hit is the mean z over those that did.  Rays that miss the box or have no live sample give exactly 0 in all four.
+ * CONTRACT: out_entropy_dev and out_alpha_dev are bit-identical to prv_render_entropy's and stats are identical to its stats,
+ * for the same views and options; out_depth_dev and out_hit_dev are as defined above for either stepping rule and any spp.
+ * Errors (PRV_E_INVALID with a message): level not in (0, 1) or NaN; 1.0f - level < opts->min_transmittance (the ray could be
+ * cut before it can cross); a NULL or host plane. */
+int prv_render_surface(prv_ctx* ctx, int model_slot, const prv_camset* cs, const int* view_ids, int n_views,
+                       const prv_render_opts* opts, float level, float* out_entropy_dev, float* out_alpha_dev,
+                       float* out_depth_dev, float* out_hit_dev, prv_stats* stats);
 
 /* replaces: Perception_3D::precept / precept_thread_process, the reference's CPU render path
  * (main.cpp:98-284: project -> ray -> OctoMap castRay, max range main.cpp:258).  Per pixel the
@@ -375,8 +392,14 @@ int prv_argmax(const prv_score_record* records, const int* view_ids, int n);
  * per-pixel words.  The sums are integer atomics (order-independent) and the arg-max is taken on the host from a read-back of
  * the n_views sums per round: two calls return identical bytes.  Synchronises.
  * Errors: k < 1, k > n_views, grid_res not a power of two in [16, 256], a NULL or host plane: PRV_E_INVALID with a message.
+ * WITH THE SURFACE LOCATOR (prv_select_views_surface, or prv_render_surface's hit plane handed in as alpha_dev and its depth as
+ * depth_dev) nothing above changes but what the words mean: "located" is then: the hit fraction is at least alpha_min and
+ * z > 0, and the point is at t = (z / hit) / c, the mean first-crossing depth of the sub-samples that reached the level.  At
+ * 1 spp with level 0.5 and the default alpha_min the located pixels are the ones the expected-depth locator locates
+ * (1 - T_end >= 0.5), up to rays whose final T rounds onto 1/2; only WHERE they are located changes.
  * LIMITS: the expected depth z / alpha is a poor locator on rays whose weights are spread widely (exactly the high-entropy rays:
- * the point then lies between the surfaces the ray may stop at); coverage is binary (a voxel seen once counts as seen, from
+ * the point then lies between the surfaces the ray may stop at) -- the surface locator is the opt-in answer to that, the
+ * default stays the expected depth; coverage is binary (a voxel seen once counts as seen, from
  * whatever angle); the stage is SINGLE-RANK: it needs every candidate's planes on one device, a sharded variant (all-gather of
  * voxel / q words, or of bitsets) is out of scope here. */
 typedef struct prv_select_opts {
@@ -394,6 +417,11 @@ int prv_select_from_images(prv_ctx* ctx, const prv_camset* cs, const int* view_i
 int prv_select_views(prv_ctx* ctx, int model_slot, const prv_camset* cs, const int* view_ids, int n_views,
                      const prv_render_opts* render_opts, const prv_select_opts* opts, int* chosen_out, uint64_t* gains_out,
                      prv_stats* stats);
+/* prv_render_surface of the views at `level` into context scratch, then prv_select_from_images with its hit plane as alpha_dev
+ * and its depth plane as depth_dev; stats: the render's.  Errors: prv_select_views' and prv_render_surface's. */
+int prv_select_views_surface(prv_ctx* ctx, int model_slot, const prv_camset* cs, const int* view_ids, int n_views,
+                             const prv_render_opts* render_opts, float level, const prv_select_opts* opts, int* chosen_out,
+                             uint64_t* gains_out, prv_stats* stats);
 
 /* replaces: Perception_3D::render (the PCL screenshot of the coloured ground-truth cloud with
  * points_size_cloud-pixel points on white, main.cpp:68-96) + convertToAlpha (Share_Data.hpp:771-784) +

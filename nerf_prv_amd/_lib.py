@@ -156,9 +156,11 @@ SIGNATURES = {
     "prv_render_depth": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), _vp, _vp, _P(Stats)]),
     "prv_render_entropy": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), _vp, _vp, _P(Stats)]),
     "prv_render_footprint": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), _vp, _vp, _vp, _P(Stats)]),
+    "prv_render_surface": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), C.c_float, _vp, _vp, _vp, _vp, _P(Stats)]),
     "prv_select_default_opts": (_i, [_P(SelectOpts)]),
     "prv_select_from_images": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _P(SelectOpts), _vp, _vp, _vp, _vp]),
     "prv_select_views": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), _P(SelectOpts), _vp, _vp, _P(Stats)]),
+    "prv_select_views_surface": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), C.c_float, _P(SelectOpts), _vp, _vp, _P(Stats)]),
     "prv_first_hit": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, C.c_float, _vp]),
     "prv_precept": (_i, [_vp, _i, _vp, _i, _vp, _P(Rs2Intrinsics), C.c_float, _vp]),
     "prv_quantize_rgba8": (_i, [_vp, _vp, C.c_size_t, _vp, _vp]),

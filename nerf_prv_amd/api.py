@@ -349,6 +349,18 @@ class Context:
                                                 _ptr(alpha), _ptr(depth), C.byref(st) if want_stats else None))
         return ent, alpha, depth, st
 
+    def render_surface(self, slot, camset, view_ids, opts, level=0.5, want_stats=True):
+        """prv_render_surface -> (entropy, alpha, depth, hit: [n, h, w] float32 each, stats): `render_entropy`'s two planes bit
+        for bit; depth = the premultiplied z-depth of the first sample at which the ray's accumulated opacity reaches `level`,
+        hit = the share of the pixel's sub-samples that get there (depth / hit: the mean z of those that do)"""
+        ids = self._ids(camset, view_ids)
+        ent, alpha, depth, hit = (self.torch.empty((len(ids), opts.height, opts.width), dtype=self.torch.float32, device=self.device)
+                                  for _ in range(4))
+        st = L.Stats()
+        self._chk(self.lib.prv_render_surface(self.handle, slot, camset.handle, _ptr(ids), len(ids), C.byref(opts), float(level),
+                                              _ptr(ent), _ptr(alpha), _ptr(depth), _ptr(hit), C.byref(st) if want_stats else None))
+        return ent, alpha, depth, hit, st
+
     def select_from_images(self, camset, view_ids, entropy, alpha, depth, opts, want_words=False):
         """prv_select_from_images on device planes [n, h, w] -> (chosen view ids [k] int32, gains [k] uint64) and, with
         want_words, the per-pixel (voxel, q) words as int32-typed device tensors [n, h, w] holding uint32 bit patterns"""
@@ -364,14 +376,22 @@ class Context:
                                                   _ptr(depth), C.byref(opts), _ptr(chosen), _ptr(gains), _ptr(voxel), _ptr(q)))
         return (chosen, gains, voxel, q) if want_words else (chosen, gains)
 
-    def select_views(self, slot, camset, view_ids, render_opts, opts, want_stats=False):
-        """prv_select_views: the footprint render of the candidates, then the greedy rounds -> (chosen [k], gains [k], stats)"""
+    def select_views(self, slot, camset, view_ids, render_opts, opts, want_stats=False, locator="expected", level=0.5):
+        """prv_select_views: the footprint render of the candidates, then the greedy rounds -> (chosen [k], gains [k], stats).
+        locator="surface": prv_select_views_surface -- the candidates' pixels are located at the first sample at which the
+        accumulated opacity reaches `level` (`render_surface`) instead of at the expected depth"""
+        if locator not in ("expected", "surface"):
+            raise ValueError(f"locator must be 'expected' or 'surface', got {locator!r}")
         ids = self._ids(camset, view_ids)
         k = max(int(opts.k), 0)
         chosen, gains = np.zeros(k, np.int32), np.zeros(k, np.uint64)
         st = L.Stats()
-        self._chk(self.lib.prv_select_views(self.handle, slot, camset.handle, _ptr(ids), len(ids), C.byref(render_opts), C.byref(opts),
-                                            _ptr(chosen), _ptr(gains), C.byref(st) if want_stats else None))
+        tail = (C.byref(opts), _ptr(chosen), _ptr(gains), C.byref(st) if want_stats else None)
+        if locator == "surface":
+            self._chk(self.lib.prv_select_views_surface(self.handle, slot, camset.handle, _ptr(ids), len(ids), C.byref(render_opts),
+                                                        float(level), *tail))
+        else:
+            self._chk(self.lib.prv_select_views(self.handle, slot, camset.handle, _ptr(ids), len(ids), C.byref(render_opts), *tail))
         return chosen, gains, st
 
     def first_hit(self, slot, camset, view_ids, width, height, max_range=1e30):

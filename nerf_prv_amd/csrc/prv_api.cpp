@@ -84,6 +84,7 @@ struct prv_ctx {
   Buffer queue, queue_ext, stage, counters, view_ids, img_f32, partial, records, dbg[6];
   Buffer stage_depth; // prv_render_depth with spp > 1: the sub-samples' depth images (spp x batch x image floats)
   Buffer stage_foot;  // prv_render_footprint with spp > 1: the sub-samples' depth images (stage_depth holds their entropy)
+  Buffer stage_hit;   // prv_render_surface with spp > 1: the sub-samples' hit flags (its depth images go to stage_foot)
   Buffer sel_planes, sel_voxel, sel_q, sel_bits, sel_sums; // prv_select_*: the footprint planes of prv_select_views, voxel and gain per pixel, the covered bitset, the views' sums
   Buffer counters_multi, occ_multi; // the ensemble's one-launch march: queue heads + counts per member, the interleaved occupancy bytes
   int march_multi = -1;             // PRV_MARCH_MULTI=0/1 (-1: on where an instance exists, render_ensemble_ngp)
@@ -497,6 +498,16 @@ int check_opts(prv_ctx* c, const prv_render_opts* o) {
   return PRV_OK;
 }
 
+// prv_render_surface / prv_select_views_surface: the level must lie in (0, 1), and the threshold it gives must not lie under the
+// cut that ends a ray early -- a ray could then be cut before it can cross
+int check_surface_level(prv_ctx* c, const prv_render_opts* o, float level) {
+  if (!(level > 0.0f && level < 1.0f)) return fail(c, PRV_E_INVALID, "level must be in (0, 1), got %g", (double)level);
+  if (1.0f - level < o->min_transmittance)
+    return fail(c, PRV_E_INVALID, "level %g: 1 - level = %g is below min_transmittance %g, rays would be cut before they can cross", (double)level,
+                (double)(1.0f - level), (double)o->min_transmittance);
+  return PRV_OK;
+}
+
 // "device pointer" arguments are validated instead of trusted: a host pointer handed to a kernel is a GPU page
 // fault that takes the process down; here it is an error code and a message
 int check_device_ptr(prv_ctx* c, const void* p, const char* what) {
@@ -804,11 +815,14 @@ RenderParams render_params(prv_ctx* c, const Model& m, const prv_render_opts* o,
 //   kRenderDepth     (prv_render_depth):     rgba and depth, through the depth instances of the planes kernel
 //   kRenderEntropy   (prv_render_entropy, PRV_SCORE_RAY_ENTROPY): no colour at all -- the march and the planes kernel, which writes entropy and alpha
 //   kRenderFootprint (prv_render_footprint): as kRenderEntropy, and depth from the same launch
+//   kRenderSurface   (prv_render_surface):   as kRenderEntropy, and the first-crossing depth and its hit flag from the same launch
 struct RenderTargets {
   int mode = kRenderColour;
   float* rgba = nullptr;    // H * W * 4 floats per view
   uint8_t* rgba8 = nullptr; // H * W * 4 bytes per view
   float *depth = nullptr, *entropy = nullptr, *alpha = nullptr; // H * W floats per view
+  float* hit = nullptr;                                         // kRenderSurface: H * W floats per view
+  float level = 0.5f;                                           // kRenderSurface: the accumulated opacity a ray is located at
   bool zero_stats = true;      // the call starts a new statistics window
   bool private_output = false; // the caller consumes rgba / the planes through the views' cull rectangles only
 };
@@ -817,7 +831,8 @@ struct RenderTargets {
 int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, const prv_render_opts* o,
                  const RenderTargets& t) {
   const bool colour = t.mode == kRenderColour || t.mode == kRenderDepth; // the launch writes an RGBA image
-  const bool depth = t.mode == kRenderDepth || t.mode == kRenderFootprint;
+  const bool surface = t.mode == kRenderSurface;
+  const bool depth = t.mode == kRenderDepth || t.mode == kRenderFootprint || surface;
   const bool private_output = t.private_output && o->spp == 1 && !t.rgba8 && !depth; // sub-sample staging, byte and depth images are written in full
   const Model& m = c->models[slot];
   const int W = o->width, H = o->height, spp = o->spp;
@@ -848,13 +863,14 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
     float* out;
     Buffer* stage;
     float* RenderPlanesParams::*slot;
-  } planes[3];
+  } planes[4];
   int n_planes = 0;
   if (!colour) { // H where the depth render's depth would go, the opacity where the colour would
     planes[n_planes++] = {t.entropy, &c->stage_depth, &RenderPlanesParams::out_entropy};
     planes[n_planes++] = {t.alpha, &c->stage, &RenderPlanesParams::out_alpha};
   }
   if (depth) planes[n_planes++] = {t.depth, colour ? &c->stage_depth : &c->stage_foot, &RenderPlanesParams::out_depth};
+  if (surface) planes[n_planes++] = {t.hit, &c->stage_hit, &RenderPlanesParams::out_hit};
   const size_t stage_px = (colour ? 16 : 0) + 4 * (size_t)n_planes; // staging bytes per sub-sample pixel
   if (spp > 1) batch = std::min<size_t>(batch, std::max<size_t>(1, c->stage_budget / (npix * stage_px * (size_t)spp)));
   if (batch * npix * (size_t)spp >= (1ull << 32)) batch = ((1ull << 32) - 1) / (npix * (size_t)spp); // 32-bit pixel ids
@@ -873,7 +889,7 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
     const int nb = (int)std::min(batch, (size_t)n_views - b0);
     float* dst_f32 = t.rgba ? t.rgba + b0 * npix * 4 : nullptr;
     uint32_t* dst_u8 = t.rgba8 ? (uint32_t*)t.rgba8 + b0 * npix : nullptr;
-    float *dst[3], *target[3]; // the batch's part of each plane, and what the kernel writes: that, or the sub-samples' staging
+    float *dst[4], *target[4]; // the batch's part of each plane, and what the kernel writes: that, or the sub-samples' staging
     for (int i = 0; i < n_planes; i++) {
       dst[i] = planes[i].out + b0 * npix;
       target[i] = spp > 1 ? (float*)planes[i].stage->p : dst[i];
@@ -921,6 +937,7 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
     pp.view_ids = mp.view_ids;
     pp.npix = (uint32_t)npix;
     pp.nb = (uint32_t)nb;
+    pp.T_cross = 1.0f - t.level;
     if ((rc = timed(c, c->ev_render, [&] {
            HIPCHK(c, n_planes ? launch_render_planes(pp, t.mode, n_blocks, c->stream) : launch_render(pp.r, n_blocks, c->stream));
            return PRV_OK;
@@ -1057,7 +1074,7 @@ int fetch_stats(prv_ctx* c, const prv_render_opts* o, int n_views, int n_models,
   return PRV_OK;
 }
 
-// What the five prv_render* entry points share: the argument checks in their order, then render_views and the statistics.
+// What the six prv_render* entry points share: the argument checks in their order, then render_views and the statistics.
 // outs: the output pointers to verify, in order; missing: a required one is null (bad: that error's text);
 // scratch: the image the mode writes whether or not the caller wants it -- null: the context's scratch, scratch_px bytes a pixel
 struct NamedPtr {
@@ -1161,6 +1178,7 @@ void prv_destroy(prv_ctx* c) {
   release(c->stage);
   release(c->stage_depth);
   release(c->stage_foot);
+  release(c->stage_hit);
   for (Buffer* b : {&c->sel_planes, &c->sel_voxel, &c->sel_q, &c->sel_bits, &c->sel_sums}) release(*b);
   release(c->counters);
   if (c->pin) (void)hipHostFree(c->pin);
@@ -1672,6 +1690,24 @@ int prv_render_footprint(prv_ctx* c, int slot, const prv_camset* cs, const int* 
                       {{out_entropy, "out_entropy_dev"}, {out_alpha, "out_alpha_dev"}, {out_depth, "out_depth_dev"}},
                       !out_entropy || !out_alpha || !out_depth,
                       "bad camset / view count / footprint output (entropy, alpha and depth planes are all required)");
+} catch (...) { return caught(c); }
+
+int prv_render_surface(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, const prv_render_opts* o, float level,
+                       float* out_entropy, float* out_alpha, float* out_depth, float* out_hit, prv_stats* st) try {
+  if (!c) return PRV_E_INVALID;
+  int rc;
+  if ((rc = check_opts(c, o)) != PRV_OK || (rc = check_surface_level(c, o, level)) != PRV_OK) return rc;
+  RenderTargets t;
+  t.mode = kRenderSurface;
+  t.entropy = out_entropy;
+  t.alpha = out_alpha;
+  t.depth = out_depth;
+  t.hit = out_hit;
+  t.level = level;
+  return render_entry(c, slot, cs, view_ids, n_views, o, st, t,
+                      {{out_entropy, "out_entropy_dev"}, {out_alpha, "out_alpha_dev"}, {out_depth, "out_depth_dev"}, {out_hit, "out_hit_dev"}},
+                      !out_entropy || !out_alpha || !out_depth || !out_hit,
+                      "bad camset / view count / surface output (entropy, alpha, depth and hit planes are all required)");
 } catch (...) { return caught(c); }
 
 int prv_first_hit(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, int W, int H,

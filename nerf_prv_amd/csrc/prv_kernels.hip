@@ -738,12 +738,18 @@ __device__ __forceinline__ float entropy_add(float p, float H) { return p >= 1.1
 // depth mode's place, t kept live across mlp_density2 -- and z = D * dot(d, f) to X->out_depth[pix] at ray end, formed as
 // kRenderDepth forms it.  sigma, alpha and T are the colour kernel's bits in density-only mode already, so H and 1 - T are
 // the entropy mode's bits and z is the depth mode's.  Movable state: five words, {record, next sample, T, H, D}.
+// kRenderSurface (prv_render_surface): the entropy mode plus a first-crossing locator -- Dm = the ray parameter of the first
+// sample after which T <= X->T_cross (0 while the ray has not got there: t > 0 for every sample), one compare-and-select where
+// the footprint mode has its FMA, t kept live across mlp_density2 as there -- and at ray end z = Dm * dot(d, f) to
+// X->out_depth[pix], with the depth mode's cosine, and Dm > 0 as 1.0 / 0.0 to X->out_hit[pix].  H and 1 - T are the entropy
+// mode's bits.  Movable state: five words, {record, next sample, T, H, Dm}; Dm lives in the footprint mode's D.
 template <int F, int NDENSE, bool NGP, bool CACHE, int MODE>
 __device__ __forceinline__ void render_queue64_body(RenderParams P, const RenderPlanesParams* X) {
-  constexpr bool FOOT = MODE == kRenderFootprint;
-  constexpr bool DEPTH = MODE == kRenderDepth || FOOT, ENTROPY = MODE == kRenderEntropy || FOOT; // DEPTH: the D sum; ENTROPY: density layers only, the H sum
-  constexpr int kDWord = FOOT ? 4 : 6;                          // where D sits in the movable state
-  constexpr int kMoveWords = FOOT ? 5 : ENTROPY ? 4 : DEPTH ? 7 : 6; // {record, next sample, T, r, g, b (, D)} or {record, next sample, T, H (, D)}
+  constexpr bool FOOT = MODE == kRenderFootprint, SURF = MODE == kRenderSurface;
+  constexpr bool DEPTH = MODE == kRenderDepth || FOOT, ENTROPY = MODE == kRenderEntropy || FOOT || SURF; // DEPTH: the D sum; ENTROPY: density layers only, the H sum
+  constexpr bool DSTATE = DEPTH || SURF;                        // the ray carries D (SURF: Dm) and keeps its sample's t across the MLP
+  constexpr int kDWord = ENTROPY ? 4 : 6;                       // where D sits in the movable state
+  constexpr int kMoveWords = (ENTROPY ? 4 : 6) + (DSTATE ? 1 : 0); // {record, next sample, T, r, g, b (, D)} or {record, next sample, T, H (, D)}
   constexpr int kFrags = ENTROPY ? 8 : kNumFrags;       // fragment sets staged in LDS: the density layers', or both MLPs'
   __shared__ half8 wl[kFrags * 64];
   __shared__ uint32_t mv[4][32][kMoveWords]; // tail merges: {record, next sample, T, r, g, b (, D)} of the rays that change slots, per wave
@@ -782,7 +788,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
   // when this one is spent (next_chunk below); nothing about them lives in registers.
   uint32_t cur = 0, m1 = 0, m2 = 0, m3 = 0, base = 0;
   float T = 1.f, cr = 0.f, cg = 0.f, cb = 0.f;
-  float D = 0.f; // DEPTH: sum of w_i t_i so far
+  float D = 0.f; // DEPTH: sum of w_i t_i so far; SURF: Dm, the t of the first crossing, 0 before it
   float Hs = 0.f; // ENTROPY: sum of h(w_i) so far
   half8 shA = {0, 0, 0, 0, 0, 0, 0, 0}, shB = {0, 0, 0, 0, 0, 0, 0, 0}; // SH rows [8g, 8g+8) of the rays in slots (r, A) and (r, B)
   bool drained = false;
@@ -888,7 +894,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
             e[4] = __float_as_uint(cg);
             e[5] = __float_as_uint(cb);
           }
-          if constexpr (DEPTH) e[kDWord] = __float_as_uint(D);
+          if constexpr (DSTATE) e[kDWord] = __float_as_uint(D);
           active = false;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -910,7 +916,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
             } else {
               cr = __uint_as_float(e[3]); cg = __uint_as_float(e[4]); cb = __uint_as_float(e[5]);
             }
-            if constexpr (DEPTH) D = __uint_as_float(e[kDWord]);
+            if constexpr (DSTATE) D = __uint_as_float(e[kDWord]);
             take_ray(ri, e[1]);
           }
         }
@@ -944,7 +950,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
               e[4] = __float_as_uint(cg);
               e[5] = __float_as_uint(cb);
             }
-            if constexpr (DEPTH) e[kDWord] = __float_as_uint(D);
+            if constexpr (DSTATE) e[kDWord] = __float_as_uint(D);
             active = false;
           }
           if (fits && lane == 0) *(volatile uint32_t*)&pool_n = at + n_g;
@@ -983,7 +989,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
             } else {
               cr = __uint_as_float(ent[3]); cg = __uint_as_float(ent[4]); cb = __uint_as_float(ent[5]);
             }
-            if constexpr (DEPTH) D = __uint_as_float(ent[kDWord]);
+            if constexpr (DSTATE) D = __uint_as_float(ent[kDWord]);
             take_ray(ent[0], ent[1]);
           }
         }
@@ -1020,7 +1026,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
           }
           if (g == grp) {
             T = 1.f; cr = 0.f; cg = 0.f; cb = 0.f;
-            if constexpr (DEPTH) D = 0.f;
+            if constexpr (DSTATE) D = 0.f;
             if constexpr (ENTROPY) Hs = 0.f;
             take_ray(q_cur + (uint32_t)r, 0u);
           }
@@ -1045,7 +1051,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
 #pragma unroll
     for (int s = 0; s < 4; s++) asm volatile("" : "=v"(f[s]));
     bool last = false;
-    float ts = 0.f; // DEPTH: the sample's ray parameter, kept across the MLP
+    float ts = 0.f; // DSTATE: the sample's ray parameter, kept across the MLP
     if (active) {
       const uint32_t i = base + (uint32_t)__builtin_ctz(cur);
       cur &= cur - 1u;
@@ -1060,7 +1066,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
         }
       }
       const float t = fmaf((float)i + 0.5f, dt, t0);
-      if constexpr (DEPTH) ts = t;
+      if constexpr (DSTATE) ts = t;
       encode_sample<F, NDENSE, CACHE>(P.field.table, lvl, hc, fmaf(t, d[0], o[0]), fmaf(t, d[1], o[1]), fmaf(t, d[2], o[2]), f, cc);
     }
     // f[2s] | f[2s+1] = k rows [16s, 16s+8) | [16s+8, 16s+16) of the lane's own sample -> B operands of the two groups
@@ -1094,6 +1100,9 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
       }
       if constexpr (DEPTH) D = fmaf(wgt, ts, D);
       T = T * (1.0f - alpha);
+      if constexpr (SURF) {
+        if (D == 0.f && T <= X->T_cross) D = ts;
+      }
       done = last || T < P.min_T;
     }
     if (done) {
@@ -1106,12 +1115,13 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
         X->out_entropy[pix] = entropy_add(T, Hs); // + h(T_end): the ray escapes with what is left
         X->out_alpha[pix] = 1.0f - T;
       }
-      if constexpr (DEPTH) {
+      if constexpr (DSTATE) {
         // image pix / npix of the launch is a sub-sample of view (pix / npix) % nb
         const CamDev& cam = X->cams[X->view_ids[(pix / X->npix) % X->nb]];
         const float fx = cam.c2w[2], fy = cam.c2w[6], fz = cam.c2w[10];
         const float inv = 1.0f / sqrtf(fmaf(fx, fx, fmaf(fy, fy, fz * fz)));
         X->out_depth[pix] = D * (fmaf(d[0], fx, fmaf(d[1], fy, d[2] * fz)) * inv);
+        if constexpr (SURF) X->out_hit[pix] = D > 0.f ? 1.0f : 0.0f;
       }
       active = false;
     }
@@ -1132,14 +1142,19 @@ void render_queue64_kernel(RenderParams P) {
   render_queue64_body<F, NDENSE, NGP, CACHE, kRenderColour>(P, nullptr);
 }
 
-// prv_render_depth / prv_render_entropy / prv_render_footprint: the render that writes scalar planes (render_queue64_body,
-// MODE = kRenderDepth / kRenderEntropy / kRenderFootprint), for the (F, NDENSE) set of the colour instances; no corner-cache
+// prv_render_depth / prv_render_entropy / prv_render_footprint / prv_render_surface: the render that writes scalar planes (render_queue64_body,
+// MODE = kRenderDepth / kRenderEntropy / kRenderFootprint / kRenderSurface), for the (F, NDENSE) set of the colour instances; no corner-cache
 // instance.  Waves per SIMD as the colour instances ask for.  Depth: no spills at either.  Entropy and footprint: without the
 // colour MLP's accumulators, SH rows and colour sums the dense-level instances take 122-130 registers (colour: 160-168; three
 // waves, the F = 2 ones under the engine's rule four), the all-hashed ones 183-218 (two waves), none spills a VGPR
-// (scripts/kernel_resources.py prv_kernels.hip render_planes)
+// (scripts/kernel_resources.py prv_kernels.hip render_planes).  Surface: register for register the footprint
+// instances', but for the F = 4 dense-level ones under the fixed rule: asked for three waves they take 134 registers where the
+// footprint twins take 126 (the fourth plane's store; no placement or form of it changes that), so those two are asked for the
+// four waves their twins have, and take 126 with no spill of either kind.  The predicate follows what this compiler does:
+// look at scripts/kernel_resources.py's rows of the surface instances again whenever the compiler changes
 template <int F, int NDENSE, bool NGP, int MODE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NDENSE == 0 ? 1 : 3)))
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(NDENSE == 0 ? 1 : MODE == kRenderSurface && F == 4 && !NGP ? 4 : 3)))
 void render_planes_kernel(RenderPlanesParams P) {
   render_queue64_body<F, NDENSE, NGP, false, MODE>(P.r, &P);
 }
@@ -1868,6 +1883,7 @@ hipError_t launch_render_planes(const RenderPlanesParams& P, int mode, int n_blo
   if (mode == kRenderDepth) launch_render_planes_mode<kRenderDepth>(P, n_blocks, s);
   else if (mode == kRenderEntropy) launch_render_planes_mode<kRenderEntropy>(P, n_blocks, s);
   else if (mode == kRenderFootprint) launch_render_planes_mode<kRenderFootprint>(P, n_blocks, s);
+  else if (mode == kRenderSurface) launch_render_planes_mode<kRenderSurface>(P, n_blocks, s);
   else return hipErrorInvalidValue;
   return hipGetLastError();
 }

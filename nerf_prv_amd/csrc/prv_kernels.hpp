@@ -107,13 +107,15 @@ struct RenderParams {
 };
 
 // what a launch renders: the colour image, or scalar planes (render_planes_kernel's MODE)
-enum : int { kRenderColour = 0, kRenderDepth = 1, kRenderEntropy = 2, kRenderFootprint = 3 };
+enum : int { kRenderColour = 0, kRenderDepth = 1, kRenderEntropy = 2, kRenderFootprint = 3, kRenderSurface = 4 };
 
 // the plane-writing renders (render_planes_kernel): the colour launch's parameters, untouched, plus one float per pixel of
 // the launch's images (r.out_f32 / 4) per plane.  A plane starts zeroed, which is what a dead ray contributes.
 //   kRenderDepth (prv_render_depth):         the colour image and out_depth
 //   kRenderEntropy (prv_render_entropy):     out_entropy and out_alpha; r.out_f32 / out_u8 are not touched
 //   kRenderFootprint (prv_render_footprint): all three planes from one density-only launch; r.out_f32 / out_u8 are not touched
+//   kRenderSurface (prv_render_surface):     out_entropy and out_alpha as kRenderEntropy; out_depth = the premultiplied z-depth of the first
+//                                            sample after which T <= T_cross, out_hit = 1 where there is one; r.out_f32 / out_u8 are not touched
 struct RenderPlanesParams {
   RenderParams r;
   float* out_depth; // premultiplied z-depth, engine units           (null where the mode does not write the plane)
@@ -126,6 +128,9 @@ struct RenderPlanesParams {
   // the entropy planes come last: in front of the depth fields they cost the all-hashed footprint instance 7 more SGPR spills
   float* out_entropy; // H, bits
   float* out_alpha;   // 1 - T_end
+  // the surface mode's own come behind everything the older instances read, so their argument offsets stay what they were
+  float T_cross;  // the ray is located at its first sample after which T <= T_cross (the host: 1.0f - level)
+  float* out_hit; // 1.0 where the ray got there, else 0.0
 };
 
 struct EnsembleParams {
@@ -155,7 +160,7 @@ hipError_t launch_march(const MarchParams& P, int n_views, int n_spp, hipStream_
 hipError_t launch_spp_reduce(const float* stage, size_t n_pixels, int spp, const float bg[4], float* out, uint32_t* out_u8,
                              hipStream_t s);
 hipError_t launch_render(const RenderParams& P, int n_blocks, hipStream_t s);
-hipError_t launch_render_planes(const RenderPlanesParams& P, int mode, int n_blocks, hipStream_t s); // mode: kRenderDepth / Entropy / Footprint
+hipError_t launch_render_planes(const RenderPlanesParams& P, int mode, int n_blocks, hipStream_t s); // mode: kRenderDepth / Entropy / Footprint / Surface
 hipError_t launch_spp_reduce_depth(const float* stage, size_t n_pixels, int spp, float* out, hipStream_t s);
 hipError_t launch_score_entropy(const float* entropy, const float* alpha, size_t npix, int n_views, int n_blocks, double* partial,
                                 hipStream_t s);

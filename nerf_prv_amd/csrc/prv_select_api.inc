@@ -100,28 +100,53 @@ int prv_select_from_images(prv_ctx* c, const prv_camset* cs, const int* view_ids
   return select_rounds(c, cs, view_ids, n_views, width, height, entropy_dev, alpha_dev, depth_dev, so, chosen_out, gains_out, voxel_dev, q_dev);
 } catch (...) { return caught(c); }
 
-int prv_select_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, const prv_render_opts* o,
-                     const prv_select_opts* so, int* chosen_out, uint64_t* gains_out, prv_stats* st) try {
+} // extern "C"
+
+namespace {
+
+// prv_select_views / prv_select_views_surface: the planes of the views into context scratch, then the rounds on them.  surface:
+// the first-crossing render at `level`; its hit plane is the rounds' alpha and its depth their depth
+int select_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, const prv_render_opts* o, bool surface,
+                 float level, const prv_select_opts* so, int* chosen_out, uint64_t* gains_out, prv_stats* st) {
   int rc;
   if ((rc = select_check_opts(c, so, n_views)) != PRV_OK) return rc;
   if (!c) return fail(nullptr, PRV_E_INVALID, "the context is NULL");
   if ((rc = check_model(c, slot)) != PRV_OK || (rc = check_opts(c, o)) != PRV_OK) return rc;
+  if (surface && (rc = check_surface_level(c, o, level)) != PRV_OK) return rc;
   if (!cs || n_views < 0) return fail(c, PRV_E_INVALID, "bad camset / view count");
   if (!chosen_out) return fail(c, PRV_E_INVALID, "chosen_out is required");
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = (size_t)n_views * o->width * o->height;
-  if ((rc = ensure(c, c->sel_planes, n * 12)) != PRV_OK) return rc;
+  if ((rc = ensure(c, c->sel_planes, n * (surface ? 16 : 12))) != PRV_OK) return rc;
   float* ent = (float*)c->sel_planes.p;
   float* alp = ent + n;
   float* dep = alp + n;
   RenderTargets t;
-  t.mode = kRenderFootprint;
+  t.mode = surface ? kRenderSurface : kRenderFootprint;
   t.entropy = ent;
   t.alpha = alp;
   t.depth = dep;
+  if (surface) {
+    t.hit = dep + n;
+    t.level = level;
+  }
   if ((rc = render_views(c, slot, cs, view_ids, n_views, o, t)) != PRV_OK) return rc;
   if ((rc = fetch_stats(c, o, n_views, 1, st)) != PRV_OK) return rc;
-  return select_rounds(c, cs, view_ids, n_views, o->width, o->height, ent, alp, dep, so, chosen_out, gains_out, nullptr, nullptr);
+  return select_rounds(c, cs, view_ids, n_views, o->width, o->height, ent, surface ? t.hit : alp, dep, so, chosen_out, gains_out, nullptr, nullptr);
+}
+
+} // namespace
+
+extern "C" {
+
+int prv_select_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, const prv_render_opts* o,
+                     const prv_select_opts* so, int* chosen_out, uint64_t* gains_out, prv_stats* st) try {
+  return select_views(c, slot, cs, view_ids, n_views, o, false, 0.f, so, chosen_out, gains_out, st);
+} catch (...) { return caught(c); }
+
+int prv_select_views_surface(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, const prv_render_opts* o, float level,
+                             const prv_select_opts* so, int* chosen_out, uint64_t* gains_out, prv_stats* st) try {
+  return select_views(c, slot, cs, view_ids, n_views, o, true, level, so, chosen_out, gains_out, st);
 } catch (...) { return caught(c); }
 
 } // extern "C"

@@ -98,6 +98,11 @@ public:
   // views_per_iteration: 1 (default) = the reference's loop, one view per training round.  k > 1 = k views per round, chosen by
   //             the selection stage (prv_select_views: greedy, redundancy-aware); method_of_IG 7 with score_path: fused only
   int views_per_iteration = 1;
+  // select_locator: expected (default) = the selection stage locates a pixel at its expected depth z / alpha (prv_select_views);
+  //             surface = at the first sample at which the ray's accumulated opacity reaches select_level, default 0.5
+  //             (prv_select_views_surface).  Read whatever views_per_iteration is; used when it is above 1
+  bool select_surface = false;
+  double select_level = 0.5;
   // state
   std::vector<std::vector<double>> pt_sphere;
   double pt_norm = 0;
@@ -176,6 +181,20 @@ public:
         error = "views_per_iteration must be at least 1";
         return;
       }
+    }
+    if (fs.has("select_locator")) {
+      const std::string how = fs.str("select_locator");
+      if (how != "expected" && how != "surface") {
+        error = "select_locator must be 'expected' or 'surface', not '" + how + "'";
+        return;
+      }
+      select_surface = how == "surface";
+    }
+    if (fs.has("select_level")) select_level = fs.num("select_level");
+    // (policed under either locator: a bad level is refused where it is written, not when the locator is switched on later)
+    if (!(select_level > 0.0 && select_level < 1.0 && 1.0f - (float)select_level >= (float)min_transmittance)) {
+      error = "select_level must lie in (0, 1) with 1 - select_level >= min_transmittance";
+      return;
     }
     // constructor overrides (Share_Data.hpp:402-409)
     if (test_name != "") name_of_pcd = test_name;

@@ -569,6 +569,8 @@ struct HipScorer {
   // json -- the footprint render and the greedy rounds; chosen = k candidate ids in selection order
   int select_grid_res = 0; // yaml select_grid_res / select_alpha_min (0 / negative: prv_select_default_opts')
   float select_alpha_min = -1.f;
+  bool select_surface = false; // yaml select_locator: surface -- prv_select_views_surface at select_level instead of prv_select_views
+  float select_level = 0.5f;
   int select(int iteration, const std::string& scene_json, const std::string& render_json, const std::vector<int>& ids, int k,
              std::vector<int>& chosen) {
     int rc = prepare_members(iteration, scene_json);
@@ -587,7 +589,9 @@ struct HipScorer {
     if (select_alpha_min >= 0.f) so.alpha_min = select_alpha_min;
     std::vector<int> frames((size_t)std::max(k, 1));
     std::vector<uint64_t> gains((size_t)std::max(k, 1));
-    rc = n == (int)ids.size() ? prv_select_views(ctx, slot_of(0), cams, nullptr, n, &o, &so, frames.data(), gains.data(), nullptr) : PRV_E_INVALID;
+    if (n != (int)ids.size()) rc = PRV_E_INVALID;
+    else if (select_surface) rc = prv_select_views_surface(ctx, slot_of(0), cams, nullptr, n, &o, select_level, &so, frames.data(), gains.data(), nullptr);
+    else rc = prv_select_views(ctx, slot_of(0), cams, nullptr, n, &o, &so, frames.data(), gains.data(), nullptr);
     prv_camset_destroy(cams);
     if (rc != PRV_OK) {
       std::cerr << "prv: " << (n == (int)ids.size() ? prv_last_error(ctx) : "the render json does not hold the candidates") << std::endl;
@@ -875,6 +879,8 @@ int PlanningJob::setup(prv_ctx* ctx_, const std::string& cfg, const std::string&
   if (engine_state && sd->views_per_iteration > 1) {
     if (fs.has("select_grid_res")) engine_state->select_grid_res = (int)fs.num("select_grid_res");
     if (fs.has("select_alpha_min")) engine_state->select_alpha_min = (float)fs.num("select_alpha_min");
+    engine_state->select_surface = sd->select_surface; // yaml select_locator / select_level: read and policed by Share_Data
+    engine_state->select_level = (float)sd->select_level;
     labeler.selector = [engine_state](int iteration, const std::string& scene, const std::string& render, const std::vector<int>& ids, int k,
                                       std::vector<int>& chosen) { return engine_state->select(iteration, scene, render, ids, k, chosen); };
   }

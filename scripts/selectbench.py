@@ -9,7 +9,10 @@
   2. selection stage alone: prv_select_from_images at k = 4 on the planes of those two renders (host clock around the call,
      which ends in a device synchronise: it includes the per-round read-back of the views' sums).
 
-    python scripts/selectbench.py [--reps 5] [--json out.json]
+  --locator surface|both adds prv_render_surface (level 0.5) to the interleaved launches of step 1, so one run times the
+  footprint and the surface launch side by side on the same box (surface_over_footprint), and step 2 is run on its planes too.
+
+    python scripts/selectbench.py [--reps 5] [--json out.json] [--locator expected|surface|both]
 """
 import argparse
 import json
@@ -23,6 +26,7 @@ import numpy as np
 ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--json", default="")
+ap.add_argument("--locator", choices=["expected", "surface", "both"], default="expected")
 args = ap.parse_args()
 
 import torch
@@ -42,6 +46,8 @@ for name, (n, w, h, opts) in cases.items():
     alpha = torch.empty((n, h, w), dtype=torch.float32, device=ctx.device)
     runs = {"entropy": lambda: ctx.render_entropy(0, cams, None, opts, out=ent, out_alpha=alpha, want_stats=False),
             "footprint": lambda: ctx.render_footprint(0, cams, None, opts, want_stats=False)}
+    if args.locator != "expected":
+        runs["surface"] = lambda: ctx.render_surface(0, cams, None, opts, 0.5, want_stats=False)
     ms = {k: [] for k in runs}
     for r in range(args.reps + 1):  # the first round is a warm-up
         for k, fn in runs.items():  # interleaved, so clock drift hits both alike
@@ -56,6 +62,10 @@ for name, (n, w, h, opts) in cases.items():
     med = {k: float(np.median(v)) for k, v in ms.items()}
     row = dict(case=name, samples_evaluated=st.samples_evaluated, render_ms_median=med, render_ms_best={k: min(v) for k, v in ms.items()},
                render_ms_all=ms, footprint_over_entropy=med["footprint"] / med["entropy"])
+    if "surface" in med:
+        s_ent, s_alpha, s_depth, s_hit, _ = ctx.render_surface(0, cams, None, opts, 0.5)
+        assert torch.equal(s_ent, ent) and torch.equal(s_alpha, alpha)
+        row.update(surface_over_footprint=med["surface"] / med["footprint"], surface_over_entropy=med["surface"] / med["entropy"])
     so = api.select_opts(k=4)
     sel = []
     for r in range(args.reps + 1):
@@ -66,6 +76,15 @@ for name, (n, w, h, opts) in cases.items():
             sel.append((time.perf_counter() - t0) * 1e3)
     row.update(select_k4_ms_median=float(np.median(sel)), select_k4_ms_best=min(sel), select_k4_ms_all=sel, chosen=chosen.tolist(),
                gains=[int(g) for g in gains])
+    if "surface" in med:
+        sel = []
+        for r in range(args.reps + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            chosen, gains = ctx.select_from_images(cams, None, s_ent, s_hit, s_depth, so)
+            if r:
+                sel.append((time.perf_counter() - t0) * 1e3)
+        row.update(surface_select_k4_ms_median=float(np.median(sel)), surface_chosen=chosen.tolist(), surface_gains=[int(g) for g in gains])
     rows.append(row)
     print(json.dumps(row), flush=True)
     cams.close()
