@@ -437,10 +437,13 @@ int prv_splat_points(prv_ctx* ctx, const float* xyz_dev, const uint8_t* rgb_dev,
 /* replaces: testbed.compute_and_save_marching_cubes_mesh(path, [res, res, res]) (run.py:59-60, 279-282).
  * A grid of res[0] x res[1] x res[2] points over [aabb_lo, aabb_hi] (engine frame), x fastest: point i on axis a at
  * lo[a] + (float)i * step[a], step[a] = (hi[a] - lo[a]) / (float)(res[a] - 1).  sigma = the field's density at each point;
- * a corner is inside iff sigma > threshold (strict; NaN is outside).  Vertices come in edge-id order (3 * point + axis),
- * triangles in cell order, counter-clockwise seen from outside (lower sigma); normals = -grad sigma, normalised; colours =
- * the full field at the vertex seen from outside (direction -normal), quantised as an opaque pixel (prv_quantize_rgba8).
- * Everything is deterministic: two runs give identical bytes.  A grid without a surface is not an error (0 vertices). */
+ * a corner is inside iff sigma > threshold (strict; NaN is outside).  sigma may hold infinities and NaNs: a vertex sits at
+ * pa + t * (pb - pa), t = (threshold - sa) / (sb - sa), and a NaN t (an infinite or NaN end, or a difference that overflows;
+ * on a crossing edge nothing else leaves [0, 1]) is replaced by 0.5; a normal whose squared length is 0, infinite or NaN is
+ * (0, 0, 0).  Every vertex and normal is therefore finite, and every vertex lies on its grid edge.
+ * Vertices come in edge-id order (3 * point + axis), triangles in cell order, counter-clockwise seen from outside (lower
+ * sigma); normals = -grad sigma, normalised; colours = the full field at the vertex seen from outside (direction -normal),
+ * quantised as an opaque pixel (prv_quantize_rgba8).  Everything is deterministic: two runs give identical bytes.  A grid without a surface is not an error (0 vertices). */
 typedef struct prv_mesh prv_mesh; /* owns its device buffers; inert (PRV_E_STATE, not a crash) if it outlives its context */
 typedef struct prv_mesh_opts {
   int32_t res[3];               /* grid points per axis, 2..1024 each, product <= 2^30 */

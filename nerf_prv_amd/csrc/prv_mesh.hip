@@ -170,7 +170,8 @@ __global__ __launch_bounds__(256) void mesh_vertices_kernel(const float* __restr
     int ib[3] = {ia[0], ia[1], ia[2]};
     ib[a] += 1;
     const float sb = sigma[idx + stride[a]];
-    const float t = (thr - sa) / (sb - sa);
+    float t = (thr - sa) / (sb - sa);
+    if (t != t) t = 0.5f; // an infinite or NaN end, or an overflowed difference; nothing else leaves [0, 1] on a crossing edge
     float gb[3], n[3];
     grid_gradient(sigma, g, ib, gb);
 #pragma unroll
@@ -181,8 +182,9 @@ __global__ __launch_bounds__(256) void mesh_vertices_kernel(const float* __restr
     }
     const float n2 = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
     const float inv = n2 > 0.0f ? 1.0f / sqrtf(n2) : 0.0f;
+    const bool finite = fabsf(n2) < __builtin_inff(); // inf or NaN (inf - inf gradients): no direction, (0, 0, 0)
 #pragma unroll
-    for (int c = 0; c < 3; c++) nrm[3 * v + c] = n[c] * inv;
+    for (int c = 0; c < 3; c++) nrm[3 * v + c] = finite ? n[c] * inv : 0.0f;
     v++;
   }
 }

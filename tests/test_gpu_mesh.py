@@ -100,6 +100,86 @@ def test_marching_cubes_on_a_field_equals_the_reference(ctx, field):
     m2.close()
 
 
+# ---------------------------------------------------------------- adversarial and edge grids (tests/mesh_ref.py)
+CLOSED_GRIDS = {"closed_%02d" % k: g for k, g in enumerate(mesh_ref.adversarial_grids())}
+EDGE_GRIDS = {name: (sigma, thr) for name, sigma, thr in mesh_ref.edge_grids()}
+_want = {}
+
+
+def _reference(name):
+    """the grid, its threshold and the reference's mesh, computed once"""
+    if name not in _want:
+        sigma, thr = (CLOSED_GRIDS.get(name) or EDGE_GRIDS[name])
+        _want[name] = (sigma, thr) + mesh_ref.marching_cubes(sigma, threshold=thr)
+    return _want[name]
+
+
+def _extract_and_compare(ctx, name):
+    """the mesh of a grid, equal to the reference's (ids and positions exactly, normals at the file's 1e-5), twice"""
+    sigma, thr, v, n, t = _reference(name)
+    dev = ctx.torch.from_numpy(sigma).to(ctx.device)
+    m, again = ctx.marching_cubes_grid(dev, threshold=thr), ctx.marching_cubes_grid(dev, threshold=thr)
+    try:
+        assert m.counts() == (len(v), len(t))
+        assert np.array_equal(m.triangles, t)
+        assert np.array_equal(m.vertices.view(np.uint32), v.view(np.uint32))
+        dev_n = float(np.abs(m.normals.astype(np.float64) - n).max()) if len(n) else 0.0
+        print(f"{name}: {len(v)} vertices, {len(t)} triangles, normals off by at most {dev_n:.3g}")
+        np.testing.assert_allclose(m.normals, n, atol=1e-5)
+        for a in ("vertices", "normals", "colors", "triangles"):  # deterministic: identical bytes
+            assert getattr(m, a).tobytes() == getattr(again, a).tobytes(), a
+    except BaseException:
+        m.close()
+        raise
+    finally:
+        again.close()
+    return m
+
+
+@pytest.mark.parametrize("name", list(CLOSED_GRIDS))
+def test_marching_cubes_grid_on_closed_adversarial_grids(ctx, name):
+    m = _extract_and_compare(ctx, name)
+    assert len(m.triangles) > 0 and mesh_ref.is_closed_manifold(m.triangles)
+    m.close()
+
+
+@pytest.mark.parametrize("name", list(EDGE_GRIDS))
+def test_marching_cubes_grid_on_edge_grids(ctx, name, tmp_path):
+    sigma = EDGE_GRIDS[name][0]
+    if name == "noise_4097_waves":
+        assert -(-sigma.size // 64) == 4097 and sigma.size % 64 != 0
+    m = _extract_and_compare(ctx, name)
+    assert np.isfinite(m.vertices).all() and np.isfinite(m.normals).all()
+    if name.startswith("nonfinite"):
+        assert not np.isfinite(sigma).all()
+        pts = m.sample(1000, 5).cpu().numpy()
+        assert pts.shape == (1000, 3) and np.isfinite(pts).all()
+        m.save(tmp_path / "m.ply", 1.0, (0, 0, 0))
+        pv, pn, _, pt = parse_ply(tmp_path / "m.ply")
+        assert np.isfinite(pv).all() and np.isfinite(pn).all() and np.array_equal(pt, m.triangles.astype(np.int64))
+        m.save(tmp_path / "m.obj", 1.0, (0, 0, 0))
+        text = (tmp_path / "m.obj").read_text().lower()
+        assert "nan" not in text and "inf" not in text
+        assert len(parse_obj(tmp_path / "m.obj")[0]) == len(m.vertices)
+    m.close()
+
+
+def test_marching_cubes_with_occupancy_on_unequal_axes(ctx):
+    """the field path: the occupancy mask makes exact-zero plateaus in a real field"""
+    ctx.synthetic_model(SLOT + 5, api.field_desc(**util.SMALL), util.SEED_A)
+    res = (17, 23, 30)
+    grid = ctx.density_grid(SLOT + 5, res, use_occupancy=True).cpu().numpy()
+    assert grid.shape == (30, 23, 17) and (grid == 0).any() and (grid > 0).any()
+    thr = float(np.median(grid))
+    m = ctx.marching_cubes(SLOT + 5, res, threshold=thr, use_occupancy=True)
+    v, n, t = mesh_ref.marching_cubes(grid, threshold=thr)
+    assert len(t) > 0 and m.counts() == (len(v), len(t))
+    assert np.array_equal(m.triangles, t)
+    assert np.array_equal(m.vertices.view(np.uint32), v.view(np.uint32))
+    np.testing.assert_allclose(m.normals, n, atol=1e-5)
+    m.close()
+
+
 def test_empty_grid_bad_arguments_and_inert_meshes(ctx, tmp_path):
     m = ctx.marching_cubes_grid(ctx.torch.zeros((9, 8, 7), dtype=ctx.torch.float32, device=ctx.device))
     assert m.vertices.shape == (0, 3) and m.triangles.shape == (0, 3) and m.counts() == (0, 0)

@@ -40,36 +40,86 @@ def test_every_case_uses_its_crossing_edges_once_per_loop():
     assert max(ntri) == tri.shape[1]
 
 
-def _grids():
-    """20 seeded sigma grids up to 24^3 whose surface stays off the border"""
-    rng = np.random.default_rng(20261016)
-    out = []
-    for k in range(14):
-        shape = tuple(int(x) for x in rng.integers(5, 25, size=3))
-        out.append((rng.random(shape).astype(np.float32), 0.5))
-    for n in (6, 11, 17):  # checkerboards: every face of every interior cell ambiguous
-        z, y, x = np.indices((n, n + 1, n + 2))
-        out.append((((x + y + z) % 2).astype(np.float32), 0.5))
-    for n in (8, 13, 24):  # all-ambiguous faces in two directions, random values
-        z, y, x = np.indices((n, n, n))
-        s = np.where((x + y) % 2 == 0, 1.0 + rng.random((n, n, n)), rng.random((n, n, n)) * 0.5)
-        out.append((s.astype(np.float32), 0.75))
-    grids = []
-    for s, thr in out:
-        s = s.copy()
-        s[0], s[-1], s[:, 0], s[:, -1], s[:, :, 0], s[:, :, -1] = 0, 0, 0, 0, 0, 0
-        grids.append((s, thr))
-    return grids
-
-
 @pytest.mark.parametrize("k", range(20))
 def test_reference_meshes_are_closed_manifolds(k):
-    sigma, thr = _grids()[k]
+    sigma, thr = mesh_ref.adversarial_grids()[k]
     v, n, t = mesh_ref.marching_cubes(sigma, threshold=thr)
     assert len(t) > 0
     assert mesh_ref.is_closed_manifold(t)  # every edge in two triangles, with opposite winding
     assert np.isfinite(v).all() and (v >= 0).all() and (v <= 1).all()
     assert len(np.unique(t)) == len(v)  # every vertex is used
+
+
+EDGE_GRIDS = {name: (sigma, thr) for name, sigma, thr in mesh_ref.edge_grids()}
+
+
+@pytest.mark.parametrize("name", list(EDGE_GRIDS))
+def test_reference_on_the_edge_grids_is_finite_and_on_its_edges(name):
+    sigma, thr = EDGE_GRIDS[name]
+    assert sigma.dtype == np.float32 and sigma.size <= 266240
+    v, n, t = mesh_ref.marching_cubes(sigma, threshold=thr)
+    rz, ry, rx = sigma.shape
+    _, _, ia, ib = mesh_ref.crossing_edges(sigma, thr)
+    axes = mesh_ref.grid_axes((rx, ry, rz), (0, 0, 0), (1, 1, 1))
+    pa = np.stack([axes[a][ia[:, a]] for a in range(3)], 1)
+    pb = np.stack([axes[a][ib[:, a]] for a in range(3)], 1)
+    assert len(v) == len(pa) and (len(v) > 0 or name == "huge_thr3e38")  # nothing is above 3e38: the one empty mesh
+    assert np.isfinite(v).all()
+    assert ((v >= pa) & (v <= pb)).all()  # exactly: pa <= pb, equal off the edge's axis, and fp32 rounding is monotonic
+    assert np.isfinite(n).all()
+    length = np.linalg.norm(n.astype(np.float64), axis=1)
+    assert ((length == 0) | (np.abs(length - 1) <= 1e-5)).all()
+    assert t.dtype == np.uint32 and (len(t) == 0 or int(t.max()) < len(v))
+    # every vertex is used, with no exception for thin grids: res >= 2 on every axis, so every grid edge belongs to a cell,
+    # and a cell's triangles use all of its crossing edges (test_every_case_uses_its_crossing_edges_once_per_loop)
+    assert len(np.unique(t)) == len(v)
+
+
+def test_edge_grids_hold_what_they_are_for():
+    """so that the GPU tests on these grids cannot be hollow"""
+    _, _, ntri = mesh_ref.tables()
+    sigma, thr = EDGE_GRIDS["noise_ragged_scan"]
+    inside, vid, _, _ = mesh_ref.crossing_edges(sigma, thr)
+    hist = np.bincount(mesh_ref.cell_cases(inside).ravel(), minlength=256)
+    assert (hist > 0).all()  # all 256 cases
+    assert ntri.max() == 5 and (hist[ntri >= 4] >= 10).all()
+    assert sigma.size == 4160 * 64  # waves of 64 points: one scan chunk of 4096 and a ragged one of 64
+    per_wave = np.diff(vid.reshape(-1, 3 * 64)[:, -1], prepend=-1)  # crossings per wave
+    assert per_wave.min() > 0 and per_wave.mean() > 90
+    sigma, thr = EDGE_GRIDS["noise_4097_waves"]
+    assert 4096 * 64 < sigma.size <= 4097 * 64 and sigma.size % 64 == 63  # 4097 waves, the last one lane short
+    sigma, thr = EDGE_GRIDS["noise_ragged_cells"]
+    rz, ry, rx = sigma.shape
+    assert (rz - 2) * ry * rx > 4096 * 64 + 64  # cells (and their triangles) in waves past the first scan chunk
+    assert EDGE_GRIDS["thin_2x2x15"][0].size < 64 < EDGE_GRIDS["thin_2x2x31"][0].size < 128 and EDGE_GRIDS["thin_9x9x2"][0].shape[2] == 2
+    for name in ("plateau_thr1", "plateau_thr2"):
+        sigma, thr = EDGE_GRIDS[name]
+        v, _, t = mesh_ref.marching_cubes(sigma, threshold=thr)
+        assert (sigma == thr).mean() > 0.2
+        assert len(np.unique(v, axis=0)) < len(v)  # coincident vertices (t = 0 on every edge of an on-threshold corner)
+        a, b, c = (v[t[:, k]].astype(np.float64) for k in range(3))
+        assert (np.linalg.norm(np.cross(b - a, c - a), axis=1) == 0).any()  # zero-area triangles
+    sigma = EDGE_GRIDS["signed_thr0"][0]
+    assert (np.signbit(sigma) & (sigma == 0)).any() and (sigma < 0).any() and (sigma > 0).any()
+    sigma = EDGE_GRIDS["subnormal"][0]
+    assert (sigma == 0).mean() > 0.2 and sigma.max() < np.finfo(np.float32).tiny and (sigma > 0).mean() > 0.7
+    sigma = EDGE_GRIDS["huge_thr0"][0]
+    with np.errstate(over="ignore"):
+        assert np.isinf(sigma.max() - sigma.min()) and np.isinf(np.float32(1e38) - sigma.min())
+    for name in ("nonfinite", "nonfinite_block"):
+        sigma = EDGE_GRIDS[name][0]
+        for kind in (np.isposinf, np.isneginf, np.isnan):
+            assert 0.02 < kind(sigma).mean() < 0.05
+        for ax in range(3):
+            lo, hi = np.moveaxis(sigma, ax, 0)[:-1], np.moveaxis(sigma, ax, 0)[1:]
+            fin_lo, fin_hi = np.isfinite(lo), np.isfinite(hi)
+            assert (np.isposinf(lo) & fin_hi & (hi <= 0.5)).any()  # (+inf, finite outside)
+            assert (fin_lo & (lo > 0.5) & np.isneginf(hi)).any()   # (finite inside, -inf)
+            assert (np.isnan(lo) & fin_hi & (hi > 0.5)).any()      # (NaN, finite inside)
+            assert (np.isposinf(lo) & np.isnan(hi)).any()          # (+inf, NaN)
+            assert (np.isposinf(lo) & np.isneginf(hi)).any()       # (+inf, -inf)
+    block = np.isposinf(EDGE_GRIDS["nonfinite_block"][0][5:8, 6:9, 9:12])
+    assert block.all()
 
 
 def test_reference_sphere_is_oriented_outwards():
