@@ -472,6 +472,43 @@ int prv_mesh_write_file(const char* path, uint64_t n_vertices, const float* xyz,
                         uint64_t n_triangles, const uint32_t* tri, double scale, const double offset[3]);
 void prv_mesh_destroy(prv_mesh* m);
 
+/* Connected components and floater removal.  Two vertices are connected if a triangle uses both; a component is a connected
+ * set of vertices, and a vertex that no triangle uses is a component of its own with 0 triangles.  Components are numbered
+ * by their smallest vertex id: component c is the one whose smallest vertex is the c-th smallest among them.  A triangle
+ * belongs to the component of its first vertex.  The table's counts are integer sums and its box the per-axis minimum /
+ * maximum of the component's vertices under the float order with -0 below +0 (every vertex of a mesh is finite), so labels
+ * and table are bit-reproducible.  No area: a float sum over atomics would not be.
+ * On the device: a union-find over 32-bit parents that are only ever lowered, hooked by one lane per triangle and compressed
+ * by one lane per vertex, repeated until a hook pass changes nothing -- at most 64 rounds (PRV_E_INTERNAL beyond, never a
+ * longer loop; a mesh takes 2).  No workgroup waits for another.
+ * prv_mesh_filter keeps whole components and preserves the order of vertices and of triangles (ids remapped): the result
+ * is what boolean-mask compaction of the arrays gives.  The rule, in this order:
+ *   1. min_triangles > 0: only components with n_triangles >= min_triangles stay;
+ *   2. keep_largest > 0: of those, only the keep_largest with the most triangles stay, equal counts to the lower id;
+ *   3. min_diagonal > 0: of those, a component stays if its box's diagonal >= min_diagonal, the diagonal being
+ *      sqrt((dx*dx + dy*dy) + dz*dz) in double, d = (double)hi - (double)lo, engine units.
+ * Errors: NULL arguments, a negative or non-finite min_diagonal, a capacity below the count: PRV_E_INVALID; a mesh whose
+ * context is gone: PRV_E_STATE.  An empty mesh has 0 components and filters to an empty mesh. */
+typedef struct prv_mesh_component { /* 48 bytes */
+  uint32_t first_vertex, reserved;  /* the component's smallest vertex id; 0 */
+  uint64_t n_vertices, n_triangles;
+  float lo[3], hi[3];               /* bounding box, engine frame */
+} prv_mesh_component;
+typedef struct prv_mesh_filter_opts {
+  uint64_t min_triangles; /* keep components with at least this many; 0: no limit */
+  uint32_t keep_largest;  /* then keep the k with the most triangles, ties to the lower component id; 0: all */
+  float min_diagonal;     /* and drop boxes whose diagonal (engine units, computed in double from lo/hi) is below this */
+} prv_mesh_filter_opts;
+int prv_mesh_filter_default_opts(prv_mesh_filter_opts* o); /* all zero: the identity */
+/* labels the mesh once; labels and table are cached on the handle and released with it */
+int prv_mesh_components(prv_mesh* m, uint64_t* n_components);
+/* the table in component order; capacity = entries out_host can take, at least the component count */
+int prv_mesh_component_info(prv_mesh* m, uint64_t capacity, prv_mesh_component* out_host);
+/* host arrays: one component id per vertex, one per triangle; either may be NULL */
+int prv_mesh_labels(prv_mesh* m, uint32_t* vertex_component_host, uint32_t* triangle_component_host);
+/* a new mesh of the same context (colours kept if the mesh has them); the input is unchanged */
+int prv_mesh_filter(prv_mesh* m, const prv_mesh_filter_opts* o, prv_mesh** out);
+
 /* ---- geometric evaluation: surface samples, nearest neighbours, Chamfer ----- */
 /* replaces: nothing in the reference -- it judges a reconstruction through images only (run.py:257-272).  This build's
  * own: how close the reconstructed surface is to the real one, and how much of it is covered.
@@ -690,6 +727,8 @@ int prv_debug_raygen(prv_ctx* ctx, const prv_camset* cs, int view, int width, in
                      int spp_index, float* o, float* d, float* t);
 /* milliseconds of the last mesh extraction's stages: density grid, classify + scans, emit, colours (HIP events) */
 int prv_debug_mesh_stages(prv_ctx* ctx, float ms[4]);
+/* hook + compress rounds the mesh's labelling took (0: no triangles); PRV_E_STATE before prv_mesh_components has run */
+int prv_debug_mesh_component_rounds(const prv_mesh* m, int* rounds);
 /* 32 fp16 features per position (bit patterns) */
 int prv_debug_encode(prv_ctx* ctx, int model_slot, const float* pos, int n, uint16_t* feat);
 /* per point: out[0]=sigma, out[1..3]=rgb, out[4..19]=density MLP outputs, out[20..35]=rgb MLP

@@ -75,6 +75,15 @@ class MeshOpts(C.Structure):
                 ("use_occupancy", C.c_int32), ("colors", C.c_int32)]
 
 
+class MeshComponent(C.Structure):
+    _fields_ = [("first_vertex", C.c_uint32), ("reserved", C.c_uint32), ("n_vertices", C.c_uint64), ("n_triangles", C.c_uint64),
+                ("lo", C.c_float * 3), ("hi", C.c_float * 3)]
+
+
+class MeshFilterOpts(C.Structure):
+    _fields_ = [("min_triangles", C.c_uint64), ("keep_largest", C.c_uint32), ("min_diagonal", C.c_float)]
+
+
 class NNOpts(C.Structure):
     _fields_ = [("algorithm", C.c_int32), ("reserved", C.c_int32)]
 
@@ -173,6 +182,11 @@ SIGNATURES = {
     "prv_mesh_save": (_i, [_vp, C.c_char_p, C.c_double, _vp]),
     "prv_mesh_write_file": (_i, [C.c_char_p, C.c_uint64, _vp, _vp, _vp, C.c_uint64, _vp, C.c_double, _vp]),
     "prv_mesh_destroy": (None, [_vp]),
+    "prv_mesh_filter_default_opts": (_i, [_P(MeshFilterOpts)]),
+    "prv_mesh_components": (_i, [_vp, _P(C.c_uint64)]),
+    "prv_mesh_component_info": (_i, [_vp, C.c_uint64, _vp]),
+    "prv_mesh_labels": (_i, [_vp, _vp, _vp]),
+    "prv_mesh_filter": (_i, [_vp, _P(MeshFilterOpts), _P(_vp)]),
     "prv_mesh_sample": (_i, [_vp, C.c_uint64, C.c_uint64, _vp, _vp]),
     "prv_nn_default_opts": (_i, [_P(NNOpts)]),
     "prv_nn_index_create": (_i, [_vp, _vp, C.c_uint64, _P(NNOpts), _P(_vp)]),
@@ -217,6 +231,7 @@ SIGNATURES = {
     "prv_debug_render_clock": (_i, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "prv_debug_raygen": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "prv_debug_mesh_stages": (_i, [_vp, _P(C.c_float)]),
+    "prv_debug_mesh_component_rounds": (_i, [_vp, _P(C.c_int)]),
     "prv_debug_encode": (_i, [_vp, _i, _vp, _i, _vp]),
     "prv_debug_field": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp]),
 }

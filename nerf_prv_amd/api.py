@@ -649,6 +649,46 @@ class Mesh:
             raise PrvError(rc, (self.ctx.lib.prv_last_error(self.ctx.handle if self.ctx.handle else None) or b"").decode())
         return (xyz, tri) if want_triangles else xyz
 
+    def _chk(self, rc):
+        """a mesh call's error: the message is the context's, or the thread's if the handle or its context is gone"""
+        if rc != 0:
+            own = self.handle and self.ctx.handle and rc != L.PRV_E_STATE
+            raise PrvError(rc, (self.ctx.lib.prv_last_error(self.ctx.handle if own else None) or b"").decode())
+
+    def components(self):
+        """the mesh's connected components (prv_mesh_components; labelled once, cached by the library) -> dict of numpy
+        arrays: per component first_vertex uint32, n_vertices / n_triangles uint64, lo / hi (n, 3) float32 (engine frame);
+        vertex_component / triangle_component uint32, one id per vertex / triangle"""
+        lib = self.ctx.lib
+        nc = C.c_uint64()
+        self._chk(lib.prv_mesh_components(self.handle, C.byref(nc)))
+        table = (L.MeshComponent * max(1, nc.value))()
+        self._chk(lib.prv_mesh_component_info(self.handle, nc.value, table))
+        t = np.frombuffer(table, dtype=np.dtype([("first_vertex", "<u4"), ("reserved", "<u4"), ("n_vertices", "<u8"), ("n_triangles", "<u8"),
+                                                 ("lo", "<f4", (3,)), ("hi", "<f4", (3,))]))[:nc.value]
+        out = {k: t[k].copy() for k in ("first_vertex", "n_vertices", "n_triangles", "lo", "hi")}
+        out["vertex_component"] = np.zeros(len(self.vertices), np.uint32)
+        out["triangle_component"] = np.zeros(len(self.triangles), np.uint32)
+        self._chk(lib.prv_mesh_labels(self.handle, _ptr(out["vertex_component"]), _ptr(out["triangle_component"])))
+        return out
+
+    def component_rounds(self):
+        """hook + compress rounds the labelling took (prv_debug_mesh_component_rounds)"""
+        r = C.c_int()
+        self._chk(self.ctx.lib.prv_debug_mesh_component_rounds(self.handle, C.byref(r)))
+        return r.value
+
+    def filter(self, min_triangles=0, keep_largest=0, min_diagonal=0.0):
+        """whole components kept, vertex and triangle order preserved (prv_mesh_filter) -> a new Mesh: components with at
+        least min_triangles triangles, of those the keep_largest with the most triangles (ties to the lower id), of those
+        the ones whose box diagonal (engine units) is at least min_diagonal; 0 switches a rule off"""
+        o = L.MeshFilterOpts()
+        self.ctx.lib.prv_mesh_filter_default_opts(C.byref(o))
+        o.min_triangles, o.keep_largest, o.min_diagonal = int(min_triangles), int(keep_largest), float(min_diagonal)
+        h = C.c_void_p()
+        self._chk(self.ctx.lib.prv_mesh_filter(self.handle, C.byref(o), C.byref(h)))
+        return Mesh(self.ctx, h)
+
     def close(self):
         if self.handle:
             self.ctx.lib.prv_mesh_destroy(self.handle)
@@ -1141,25 +1181,38 @@ class Testbed:
         finally:
             m.close()
 
-    def compute_and_save_marching_cubes_mesh(self, filename, resolution=(256, 256, 256), aabb=None, thresh=2.5):  # run.py:282
+    def _without_floaters(self, m, keep_largest, min_triangles):
+        """m, or with a rule set the filtered mesh (m is closed then)"""
+        if not keep_largest and not min_triangles:
+            return m
+        try:
+            return m.filter(min_triangles=min_triangles, keep_largest=keep_largest)
+        finally:
+            m.close()
+
+    def compute_and_save_marching_cubes_mesh(self, filename, resolution=(256, 256, 256), aabb=None, thresh=2.5, keep_largest=0,
+                                             min_triangles=0):  # run.py:282
+        """keep_largest / min_triangles (this build's own; 0: off): drop density floaters before saving (Mesh.filter)"""
         if not self._have_model:
             raise PrvError(L.PRV_E_STATE, "no model loaded")
-        m = self.ctx.marching_cubes(self._slot, resolution, aabb, thresh)
+        m = self._without_floaters(self.ctx.marching_cubes(self._slot, resolution, aabb, thresh), keep_largest, min_triangles)
         try:
             m.save(filename, self.scale, self.offset)
         finally:
             m.close()
 
-    def compute_geometry_metrics(self, reference_points, resolution=(256, 256, 256), n_samples=1 << 20, tau=None, thresh=2.5, seed=0):
+    def compute_geometry_metrics(self, reference_points, resolution=(256, 256, 256), n_samples=1 << 20, tau=None, thresh=2.5, seed=0,
+                                 keep_largest=0, min_triangles=0):
         """mesh the current model (marching cubes at `resolution`, iso-level `thresh`), sample n_samples surface points and
         compare them with reference_points ((n, 3), dataset frame) -> dict of prv_geom_metrics' fields in DATASET units.
-        tau (dataset units) defaults to 1 % of the reference's largest extent."""
+        tau (dataset units) defaults to 1 % of the reference's largest extent.  keep_largest / min_triangles (0: off): the
+        mesh is filtered first (Mesh.filter), so floaters do not enter accuracy and hausdorff_rec."""
         if not self._have_model:
             raise PrvError(L.PRV_E_STATE, "no model loaded")
         ref = np.asarray(reference_points, np.float64).reshape(-1, 3)
         if tau is None:
             tau = 0.01 * float((ref.max(axis=0) - ref.min(axis=0)).max())
-        m = self.ctx.marching_cubes(self._slot, resolution, None, thresh, colors=False)
+        m = self._without_floaters(self.ctx.marching_cubes(self._slot, resolution, None, thresh, colors=False), keep_largest, min_triangles)
         try:
             rec = m.sample(n_samples, seed)
         finally:

@@ -36,4 +36,40 @@ hipError_t launch_mesh_triangles(const MeshGrid& g, const uint8_t* flags, const 
 // the full field at each vertex seen from outside (dir = -normal), quantised as an opaque pixel
 hipError_t launch_mesh_colors(const FieldDev& fd, const float* xyz, const float* nrm, uint64_t nv, uint8_t* rgb, hipStream_t s);
 
+// ---- connected components and the filter (prv_components.hip)
+// hook + compress rounds the labelling may take; beyond it the call fails, it never loops on
+constexpr int kMeshComponentMaxRounds = 64;
+// prv_mesh_component's layout on the device, the box as order-preserving unsigned images of its floats
+// (key = bits ^ (sign ? 0xFFFFFFFF : 0x80000000): the host undoes it)
+struct MeshComponentDev {
+  uint32_t first_vertex, reserved;
+  unsigned long long n_vertices, n_triangles;
+  uint32_t lo[3], hi[3];
+};
+static_assert(sizeof(MeshComponentDev) == 48, "one table entry is 48 bytes on both sides");
+inline size_t mesh_comp_waves(uint64_t n) { return (size_t)((n + 63) / 64); }
+
+// parent[v] = v
+hipError_t launch_mesh_comp_init(uint32_t* parent, uint64_t nv, hipStream_t s);
+// one lane per triangle joins the roots of its vertices (the larger root under the smaller); *changed |= 1 if any triangle's
+// vertices were not under one root yet.  The caller zeroes *changed before the launch.
+hipError_t launch_mesh_comp_hook(const uint32_t* tri, uint64_t nt, uint32_t* parent, uint32_t* changed, hipStream_t s);
+// one lane per vertex: parent[v] = its root
+hipError_t launch_mesh_comp_compress(uint32_t* parent, uint64_t nv, hipStream_t s);
+// roots (parent[v] == v) per wave of 64 vertices: wave_n holds mesh_comp_waves(nv) counts, to be scanned (launch_mesh_scan)
+hipError_t launch_mesh_comp_roots(const uint32_t* parent, uint64_t nv, uint64_t* wave_n, hipStream_t s);
+// parent fully compressed, wave_n scanned: component ids in root order to vcomp (nv) and tcomp (nt), and the table (one
+// entry per root)
+hipError_t launch_mesh_comp_table(const uint32_t* parent, const uint64_t* wave_n, const float* xyz, uint64_t nv, const uint32_t* tri, uint64_t nt,
+                                  uint32_t* vcomp, uint32_t* tcomp, MeshComponentDev* table, hipStream_t s);
+// elements (vertices or triangles, by their component id) of kept components per wave of 64: mesh_comp_waves(n) counts
+hipError_t launch_mesh_comp_keep_count(const uint32_t* comp, uint64_t n, const uint8_t* keep, uint64_t* wave_n, hipStream_t s);
+// wave_n scanned: the kept vertices in their order (rgb may be NULL), and vmap[v] = the new id of every kept vertex
+hipError_t launch_mesh_comp_gather_vertices(const uint32_t* vcomp, uint64_t nv, const uint8_t* keep, const uint64_t* wave_n, const float* xyz,
+                                            const float* nrm, const uint8_t* rgb, float* out_xyz, float* out_nrm, uint8_t* out_rgb,
+                                            uint32_t* vmap, hipStream_t s);
+// wave_n scanned: the kept triangles in their order, with the new vertex ids
+hipError_t launch_mesh_comp_gather_triangles(const uint32_t* tcomp, uint64_t nt, const uint8_t* keep, const uint64_t* wave_n, const uint32_t* tri,
+                                             const uint32_t* vmap, uint32_t* out_tri, hipStream_t s);
+
 } // namespace prv

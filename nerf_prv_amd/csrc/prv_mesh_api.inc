@@ -6,6 +6,11 @@ struct prv_mesh {
   uint64_t nv = 0, nt = 0;
   bool colors = false;
   Buffer xyz, nrm, rgb, tri;
+  // connected components (prv_mesh_components): labelled once, then cached here
+  bool labelled = false;
+  int label_rounds = 0;
+  Buffer vcomp, tcomp; // component id per vertex / per triangle
+  std::vector<prv_mesh_component> comps;
 };
 
 static void mesh_release(prv_mesh* m) {
@@ -13,6 +18,8 @@ static void mesh_release(prv_mesh* m) {
   release(m->nrm);
   release(m->rgb);
   release(m->tri);
+  release(m->vcomp);
+  release(m->tcomp);
 }
 
 static void mesh_detach_all(prv_ctx* c) {
@@ -124,6 +131,108 @@ int mesh_alive(const prv_mesh* m) {
   if (!m) return fail(nullptr, PRV_E_INVALID, "mesh is NULL");
   if (!m->ctx) return fail(nullptr, PRV_E_STATE, "the mesh's context has been destroyed");
   return PRV_OK;
+}
+
+// ---- connected components
+struct CompWork { // labelling / filter scratch, released on every way out
+  Buffer parent, wave_v, wave_t, scratch, misc, table, keep, vmap;
+  ~CompWork() {
+    for (Buffer* b : {&parent, &wave_v, &wave_t, &scratch, &misc, &table, &keep, &vmap}) release(*b);
+  }
+};
+
+float comp_key_float(uint32_t k) { // undoes the kernels' order-preserving image
+  const uint32_t b = k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu);
+  float f;
+  memcpy(&f, &b, 4);
+  return f;
+}
+
+// labels the mesh (once): m->vcomp, m->tcomp, m->comps
+int mesh_label(prv_mesh* m) {
+  if (m->labelled) return PRV_OK;
+  prv_ctx* c = m->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  m->comps.clear();
+  m->label_rounds = 0;
+  if (m->nv == 0) {
+    m->labelled = true;
+    return PRV_OK;
+  }
+  CompWork w;
+  const size_t waves = mesh_comp_waves(m->nv);
+  int rc;
+  if ((rc = ensure(c, w.parent, m->nv * 4)) != PRV_OK || (rc = ensure(c, w.wave_v, waves * 8)) != PRV_OK ||
+      (rc = ensure(c, w.scratch, mesh_scan_scratch(waves) * 8)) != PRV_OK || (rc = ensure(c, w.misc, 16)) != PRV_OK ||
+      (rc = ensure(c, m->vcomp, m->nv * 4)) != PRV_OK || (rc = ensure(c, m->tcomp, std::max<uint64_t>(1, m->nt) * 4)) != PRV_OK)
+    return rc;
+  uint32_t* parent = (uint32_t*)w.parent.p;
+  uint64_t* total = (uint64_t*)w.misc.p;
+  uint32_t* changed = (uint32_t*)(total + 1);
+  HIPCHK(c, launch_mesh_comp_init(parent, m->nv, c->stream));
+  int rounds = 0;
+  while (m->nt > 0) { // hook, read the flag back, compress: until a hook pass finds every triangle under one root
+    rounds++;
+    uint32_t flag = 0;
+    HIPCHK(c, hipMemsetAsync(changed, 0, 4, c->stream));
+    HIPCHK(c, launch_mesh_comp_hook((const uint32_t*)m->tri.p, m->nt, parent, changed, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&flag, changed, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!flag) break; // nothing hooked since the last compress: parent[] is flat
+    if (rounds >= kMeshComponentMaxRounds)
+      return fail(c, PRV_E_INTERNAL, "component labelling did not settle in %d rounds (%llu vertices, %llu triangles)", kMeshComponentMaxRounds,
+                  (unsigned long long)m->nv, (unsigned long long)m->nt);
+    HIPCHK(c, launch_mesh_comp_compress(parent, m->nv, c->stream));
+  }
+  HIPCHK(c, launch_mesh_comp_roots(parent, m->nv, (uint64_t*)w.wave_v.p, c->stream));
+  HIPCHK(c, launch_mesh_scan((uint64_t*)w.wave_v.p, waves, (uint64_t*)w.scratch.p, total, c->stream));
+  uint64_t nc = 0;
+  HIPCHK(c, hipMemcpyAsync(&nc, total, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (nc == 0 || nc > m->nv) return fail(c, PRV_E_INTERNAL, "%llu components of %llu vertices", (unsigned long long)nc, (unsigned long long)m->nv);
+  if ((rc = ensure(c, w.table, nc * sizeof(MeshComponentDev))) != PRV_OK) return rc;
+  HIPCHK(c, launch_mesh_comp_table(parent, (const uint64_t*)w.wave_v.p, (const float*)m->xyz.p, m->nv, (const uint32_t*)m->tri.p, m->nt,
+                                   (uint32_t*)m->vcomp.p, (uint32_t*)m->tcomp.p, (MeshComponentDev*)w.table.p, c->stream));
+  std::vector<MeshComponentDev> dev(nc);
+  HIPCHK(c, hipMemcpyAsync(dev.data(), w.table.p, nc * sizeof(MeshComponentDev), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  m->comps.resize(nc);
+  for (uint64_t i = 0; i < nc; i++) {
+    prv_mesh_component& o = m->comps[i];
+    o.first_vertex = dev[i].first_vertex;
+    o.reserved = 0;
+    o.n_vertices = dev[i].n_vertices;
+    o.n_triangles = dev[i].n_triangles;
+    for (int a = 0; a < 3; a++) {
+      o.lo[a] = comp_key_float(dev[i].lo[a]);
+      o.hi[a] = comp_key_float(dev[i].hi[a]);
+    }
+  }
+  m->label_rounds = rounds;
+  m->labelled = true;
+  return PRV_OK;
+}
+
+// the filter's rule (include/prv.h): one keep byte per component
+std::vector<uint8_t> comp_keep(const std::vector<prv_mesh_component>& comps, const prv_mesh_filter_opts& o) {
+  const size_t nc = comps.size();
+  std::vector<uint8_t> keep(nc, 1);
+  if (o.min_triangles > 0)
+    for (size_t i = 0; i < nc; i++) keep[i] = comps[i].n_triangles >= o.min_triangles;
+  if (o.keep_largest > 0) {
+    std::vector<size_t> order;
+    for (size_t i = 0; i < nc; i++)
+      if (keep[i]) order.push_back(i);
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return comps[a].n_triangles > comps[b].n_triangles; });
+    for (size_t k = o.keep_largest; k < order.size(); k++) keep[order[k]] = 0;
+  }
+  if (o.min_diagonal > 0.0f)
+    for (size_t i = 0; i < nc; i++) {
+      const double dx = (double)comps[i].hi[0] - (double)comps[i].lo[0], dy = (double)comps[i].hi[1] - (double)comps[i].lo[1],
+                   dz = (double)comps[i].hi[2] - (double)comps[i].lo[2];
+      if (std::sqrt((dx * dx + dy * dy) + dz * dz) < (double)o.min_diagonal) keep[i] = 0;
+    }
+  return keep;
 }
 
 // ---- file writer (host only)
@@ -338,6 +447,125 @@ int prv_mesh_write_file(const char* path, uint64_t nv, const float* xyz, const f
                         const uint32_t* tri, double scale, const double offset[3]) try {
   return write_mesh_file(path, nv, xyz, normals, rgb, nt, tri, scale, offset);
 } catch (...) { return caught(nullptr); }
+
+int prv_mesh_filter_default_opts(prv_mesh_filter_opts* o) {
+  if (!o) return fail(nullptr, PRV_E_INVALID, "filter options are NULL");
+  o->min_triangles = 0;
+  o->keep_largest = 0;
+  o->min_diagonal = 0.0f;
+  return PRV_OK;
+}
+
+int prv_mesh_components(prv_mesh* m, uint64_t* n_components) try {
+  int rc = mesh_alive(m);
+  if (rc != PRV_OK) return rc;
+  if (!n_components) return fail(m->ctx, PRV_E_INVALID, "n_components is NULL");
+  if ((rc = mesh_label(m)) != PRV_OK) return rc;
+  *n_components = m->comps.size();
+  return PRV_OK;
+} catch (...) { return caught(m && m->ctx ? m->ctx : nullptr); }
+
+int prv_mesh_component_info(prv_mesh* m, uint64_t capacity, prv_mesh_component* out_host) try {
+  int rc = mesh_alive(m);
+  if (rc != PRV_OK) return rc;
+  if (!out_host) return fail(m->ctx, PRV_E_INVALID, "out_host is NULL");
+  if ((rc = mesh_label(m)) != PRV_OK) return rc;
+  if (capacity < m->comps.size())
+    return fail(m->ctx, PRV_E_INVALID, "capacity %llu is below the mesh's %llu components", (unsigned long long)capacity,
+                (unsigned long long)m->comps.size());
+  if (!m->comps.empty()) memcpy(out_host, m->comps.data(), m->comps.size() * sizeof(prv_mesh_component));
+  return PRV_OK;
+} catch (...) { return caught(m && m->ctx ? m->ctx : nullptr); }
+
+int prv_mesh_labels(prv_mesh* m, uint32_t* vertex_component, uint32_t* triangle_component) try {
+  int rc = mesh_alive(m);
+  if (rc != PRV_OK) return rc;
+  if ((rc = mesh_label(m)) != PRV_OK) return rc;
+  prv_ctx* c = m->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (vertex_component && m->nv) HIPCHK(c, hipMemcpyAsync(vertex_component, m->vcomp.p, m->nv * 4, hipMemcpyDeviceToHost, c->stream));
+  if (triangle_component && m->nt) HIPCHK(c, hipMemcpyAsync(triangle_component, m->tcomp.p, m->nt * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return PRV_OK;
+} catch (...) { return caught(m && m->ctx ? m->ctx : nullptr); }
+
+int prv_mesh_filter(prv_mesh* m, const prv_mesh_filter_opts* o, prv_mesh** out) try {
+  int rc = mesh_alive(m);
+  if (rc != PRV_OK) return rc;
+  prv_ctx* c = m->ctx;
+  if (!out) return fail(c, PRV_E_INVALID, "out is NULL");
+  *out = nullptr;
+  if (!o) return fail(c, PRV_E_INVALID, "filter options are NULL");
+  if (!(o->min_diagonal >= 0.0f) || !std::isfinite(o->min_diagonal))
+    return fail(c, PRV_E_INVALID, "min_diagonal must be finite and >= 0, got %g", (double)o->min_diagonal);
+  if ((rc = mesh_label(m)) != PRV_OK) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const std::vector<uint8_t> keep = comp_keep(m->comps, *o);
+  uint64_t nv = 0, nt = 0;
+  for (size_t i = 0; i < keep.size(); i++)
+    if (keep[i]) {
+      nv += m->comps[i].n_vertices;
+      nt += m->comps[i].n_triangles;
+    }
+  std::unique_ptr<prv_mesh> f(new prv_mesh());
+  f->ctx = c;
+  f->nv = nv;
+  f->nt = nt;
+  f->colors = m->colors;
+  if (nv > 0) {
+    CompWork w;
+    const size_t waves_v = mesh_comp_waves(m->nv), waves_t = mesh_comp_waves(m->nt);
+    if ((rc = ensure(c, w.keep, keep.size())) != PRV_OK || (rc = ensure(c, w.wave_v, waves_v * 8)) != PRV_OK ||
+        (rc = ensure(c, w.wave_t, std::max<size_t>(1, waves_t) * 8)) != PRV_OK ||
+        (rc = ensure(c, w.scratch, mesh_scan_scratch(std::max(waves_v, waves_t)) * 8)) != PRV_OK || (rc = ensure(c, w.misc, 16)) != PRV_OK ||
+        (rc = ensure(c, w.vmap, m->nv * 4)) != PRV_OK)
+      return rc;
+    const uint8_t* keep_dev = (const uint8_t*)w.keep.p;
+    uint64_t* tot = (uint64_t*)w.misc.p;
+    HIPCHK(c, hipMemcpyAsync(w.keep.p, keep.data(), keep.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(tot, 0, 16, c->stream));
+    HIPCHK(c, launch_mesh_comp_keep_count((const uint32_t*)m->vcomp.p, m->nv, keep_dev, (uint64_t*)w.wave_v.p, c->stream));
+    HIPCHK(c, launch_mesh_scan((uint64_t*)w.wave_v.p, waves_v, (uint64_t*)w.scratch.p, tot, c->stream));
+    if (m->nt > 0) {
+      HIPCHK(c, launch_mesh_comp_keep_count((const uint32_t*)m->tcomp.p, m->nt, keep_dev, (uint64_t*)w.wave_t.p, c->stream));
+      HIPCHK(c, launch_mesh_scan((uint64_t*)w.wave_t.p, waves_t, (uint64_t*)w.scratch.p, tot + 1, c->stream));
+    }
+    uint64_t totals[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(totals, tot, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (totals[0] != nv || totals[1] != nt) // the gather's extents come from the table: they must be the scans' too
+      return fail(c, PRV_E_INTERNAL, "filter counts disagree: table %llu / %llu, scan %llu / %llu", (unsigned long long)nv, (unsigned long long)nt,
+                  (unsigned long long)totals[0], (unsigned long long)totals[1]);
+    if ((rc = ensure(c, f->xyz, nv * 12)) != PRV_OK || (rc = ensure(c, f->nrm, nv * 12)) != PRV_OK ||
+        (f->colors && (rc = ensure(c, f->rgb, nv * 3)) != PRV_OK) || (rc = ensure(c, f->tri, std::max<uint64_t>(1, nt) * 12)) != PRV_OK) {
+      mesh_release(f.get());
+      return rc;
+    }
+    hipError_t e = launch_mesh_comp_gather_vertices((const uint32_t*)m->vcomp.p, m->nv, keep_dev, (const uint64_t*)w.wave_v.p, (const float*)m->xyz.p,
+                                                    (const float*)m->nrm.p, f->colors ? (const uint8_t*)m->rgb.p : nullptr, (float*)f->xyz.p,
+                                                    (float*)f->nrm.p, (uint8_t*)f->rgb.p, (uint32_t*)w.vmap.p, c->stream);
+    if (e == hipSuccess && nt > 0)
+      e = launch_mesh_comp_gather_triangles((const uint32_t*)m->tcomp.p, m->nt, keep_dev, (const uint64_t*)w.wave_t.p, (const uint32_t*)m->tri.p,
+                                            (const uint32_t*)w.vmap.p, (uint32_t*)f->tri.p, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+      mesh_release(f.get());
+      return fail(c, PRV_E_HIP, "mesh filter failed: %s", hipGetErrorString(e));
+    }
+  }
+  c->meshes.push_back(f.get());
+  *out = f.release();
+  return PRV_OK;
+} catch (...) { return caught(m && m->ctx ? m->ctx : nullptr); }
+
+int prv_debug_mesh_component_rounds(const prv_mesh* m, int* rounds) {
+  const int rc = mesh_alive(m);
+  if (rc != PRV_OK) return rc;
+  if (!rounds) return fail(m->ctx, PRV_E_INVALID, "rounds is NULL");
+  if (!m->labelled) return fail(m->ctx, PRV_E_STATE, "the mesh has not been labelled yet (prv_mesh_components)");
+  *rounds = m->label_rounds;
+  return PRV_OK;
+}
 
 void prv_mesh_destroy(prv_mesh* m) {
   if (!m) return;

@@ -23,7 +23,7 @@ for line in out.splitlines():
     t = m.group(1)
     if t.startswith("Function Name:"):
         name = subprocess.run(["c++filt", t.split(":", 1)[1].strip()], capture_output=True, text=True).stdout.strip()
-        cur = {"name": re.sub(r"\(.*", "", name).replace("void prv::", "")}
+        cur = {"name": re.sub(r"\(.*", "", name.replace("(anonymous namespace)::", "")).replace("void prv::", "")}
         rows.append(cur)
     elif cur is not None and ":" in t:
         k, v = t.split(":", 1)
