@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PRV_ABI_VERSION 5 /* 2: prv_field_desc.per_level_scale; 3: prv_render_opts.step_mode, prv_stats.samples_live; 4: prv_train_opts.patch_w / patch_h; 5: prv_train_opts.step_mode / deterministic */
+#define PRV_ABI_VERSION 5 /* 2: prv_field_desc.per_level_scale; 3: prv_render_opts.step_mode, prv_stats.samples_live; 4: prv_train_opts.patch_w / patch_h; 5: prv_train_opts.step_mode / deterministic (still 5: prv_train_create accepting lr = 0, which it refused, changes no layout and no call that worked) */
 
 /* error codes (0 = ok, < 0 = error; message via prv_last_error) */
 #define PRV_OK 0
@@ -640,13 +640,16 @@ typedef struct prv_train_opts {
   int32_t n_rays;    /* rays per step (with target_samples: the cap of the adaptive count; default 2^16) */
   int32_t n_samples; /* PRV_STEP_FIXED_S: samples per ray between the AABB hits, <= 128.  PRV_STEP_NGP: the most steps a ray takes,
                         <= PRV_NGP_MAX_STEPS (1024 = the cube's diagonal, what prv_train_default_opts sets for that rule) */
-  float lr, beta1, beta2, eps, l2_reg; /* Adam; l2_reg on the MLP weights only */
+  float lr, beta1, beta2, eps, l2_reg; /* Adam; l2_reg on the MLP weights only.  lr >= 0: at 0 the steps run (loss, sample
+                                          budget, density refreshes) and no weight moves */
   float min_T;       /* early termination of a training ray */
   uint64_t seed;
   int32_t random_bg; /* 1: random background colour per ray */
   int32_t occ_every; /* refresh the density grid every N steps (0 = never) */
   float occ_decay, occ_sigma_thresh; /* ema = max(ema*decay, sigma); occupied iff ema > thresh (default 5.9 =
-                                        upstream's optical thickness 0.01 over a sqrt(3)/1024 step) */
+                                        upstream's optical thickness 0.01 over a sqrt(3)/1024 step).  A new trainer's
+                                        EMA starts at 0 in every cell, whatever the slot's occupancy says: the first
+                                        refresh sets ema = sigma */
   int32_t target_samples; /* > 0: the ray count of a step adapts so that about this many samples are composited
                              (upstream keeps 2^18 samples per batch): after every step active = clamp(target *
                              active / used, active/2, 2*active) within [1, n_rays]; first step min(n_rays,

@@ -454,7 +454,7 @@ int prv_train_create(prv_ctx* c, int slot, const prv_camset* cs, const uint8_t* 
     if (o->patch_w < 0 || o->patch_h < 0 || pw > 16 || ph > 16 || pw * ph > 16 || pw > width || ph > height)
       return fail(c, PRV_E_INVALID, "patch_w x patch_h must be at most 16 pixels and fit the image, got %dx%d", o->patch_w, o->patch_h);
   }
-  if (!(o->lr > 0.0f) || !(o->beta1 >= 0.0f && o->beta1 < 1.0f) || !(o->beta2 >= 0.0f && o->beta2 < 1.0f) || !(o->eps > 0.0f))
+  if (!(o->lr >= 0.0f) || !(o->beta1 >= 0.0f && o->beta1 < 1.0f) || !(o->beta2 >= 0.0f && o->beta2 < 1.0f) || !(o->eps > 0.0f))
     return fail(c, PRV_E_INVALID, "bad optimiser settings");
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = check_device_ptr(c, images_rgba8_dev, "images_rgba8_dev")) != PRV_OK) return rc;

@@ -118,6 +118,7 @@ def lib():
         L.orc_train_master_table.restype, L.orc_train_master_table.argtypes = C.POINTER(C.c_float), [vp]
         L.orc_train_master_mlp.restype, L.orc_train_master_mlp.argtypes = C.POINTER(C.c_float), [vp]
         L.orc_train_table_size.restype, L.orc_train_table_size.argtypes = C.c_size_t, [vp]
+        L.orc_train_ema.argtypes = [vp, vp]
         L.orc_splat_points.argtypes = [vp, vp, C.c_size_t, C.c_float, vp, C.POINTER(Camera), C.c_int, C.c_int, C.c_int, C.c_int, vp]
         L.orc_lens_distort.argtypes = [C.c_float * 4, C.c_float, C.c_float, f32p, f32p]
         L.orc_lens_undistort.argtypes = [C.c_float * 4, f32p, f32p]
@@ -468,6 +469,12 @@ class OracleTrainer:
 
     def refresh_occupancy(self):
         lib().orc_train_refresh_occupancy(self.ptr)
+
+    def ema(self):
+        """a copy of the density EMA per occupancy cell (x fastest), zeros before the first refresh"""
+        out = np.zeros(self.desc.occ_res ** 3, np.float32)
+        lib().orc_train_ema(self.ptr, _p(out))
+        return out
 
     def __del__(self):
         try:

@@ -222,6 +222,7 @@ uint32_t orc_train_active_rays(const orc_trainer* t); /* ray count of the next s
 float* orc_train_master_table(orc_trainer* t);
 float* orc_train_master_mlp(orc_trainer* t);
 size_t orc_train_table_size(const orc_trainer* t);
+void orc_train_ema(const orc_trainer* t, float* out); /* copy of the density EMA, occ_res^3 floats (all 0 before the first refresh) */
 
 #ifdef __cplusplus
 }

@@ -405,3 +405,8 @@ double orc_train_step(orc_trainer* t) {
 float* orc_train_master_table(orc_trainer* t) { return t->tab_w; }
 float* orc_train_master_mlp(orc_trainer* t) { return t->mlp_w; }
 size_t orc_train_table_size(const orc_trainer* t) { return t->n_table; }
+/* the density EMA per occupancy cell, copied out (tests read it; nothing writes it from outside) */
+void orc_train_ema(const orc_trainer* t, float* out) {
+  const size_t R = (size_t)t->f->desc.occ_res;
+  memcpy(out, t->ema, R * R * R * sizeof(float));
+}
