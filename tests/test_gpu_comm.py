@@ -263,6 +263,37 @@ def test_planner_members_sharded_deals_the_trainings_and_walks_the_objects_in_lo
     assert se.count("train_pairs: 4 (object, member) trainings of this round on rank 0") == 3 and so.count("chosen_nbvs:") == 2
 
 
+@pytest.mark.parametrize("method", [7, 5])
+@pytest.mark.parametrize("score_path", ["fused", "png"])
+def test_lockstep_round_trains_once_and_the_final_evaluation_trains_its_own_field(ctx, tmp_path, method, score_path):
+    """`shard: members` on one rank with `evaluate: 1`, single-model methods (their scoring goes through the scorer under
+    either score_path): a lockstep round's training is the round's only one -- the scoring call takes the members as trained
+    and trains nothing --, and the final evaluation, which no lockstep round trained for, trains its field itself: one
+    train_members line.  Deterministic training: views, records and the final metrics equal the plain loop's, byte for byte."""
+    exe = os.path.join(ROOT, "nerf_prv_amd", "prv_planner")
+    runs = {}
+    for shard in ("objects", "members"):
+        pre = tmp_path / shard
+        pre.mkdir()
+        cfg = pre / "cfg.yaml"
+        text = YAML.format(pre=pre, vs=os.path.join(GOLD, "hemisphere"), method=method,
+                           model_source="synthetic_seed: 777\ntrain_steps: 40\ntrain_rays: 1024\ntrain_width: 64\ntrain_height: 36\nground_truth_seed: 4242\n"
+                                        f"train_deterministic: 1\ndump_scores: 1\nevaluate: 1\nevaluate_views: 5\nscore_path: \"{score_path}\"\nshard: \"{shard}\"")
+        cfg.write_text(text.replace("num_of_max_iteration: 3", "num_of_max_iteration: 2"))
+        env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "PRV_SHARD")}
+        out = subprocess.run([exe, str(cfg)], input="21\nobjA\n-1\n", text=True, capture_output=True, timeout=300, env=dict(env, PRV_PLANNER_TIMING="1"))
+        assert out.returncode == 0, out.stdout + out.stderr
+        save = pre / "Compare" / "ShapeNet" / f"objA_m{method}_v1_t0"
+        runs[shard] = dict(err=out.stderr, lines=[l for l in out.stdout.splitlines() if l.startswith(("chosen_nbvs:", "final PSNR"))],
+                           records=[p.read_bytes() for p in sorted((save / "records").iterdir())], metrics=(save / "metrics" / "2.txt").read_bytes())
+    plain, lock = runs["objects"], runs["members"]
+    assert plain["err"].count("train_members:") == 3 and "train_pairs:" not in plain["err"]  # two rounds and the evaluation
+    assert lock["err"].count("train_pairs: 1 (object, member) trainings of this round on rank 0") == 2
+    assert lock["err"].count("train_members:") == 1  # the final evaluation's own training, and no other
+    assert len(plain["lines"]) == 2 and len(plain["records"]) == 2
+    assert lock["lines"] == plain["lines"] and lock["records"] == plain["records"] and lock["metrics"] == plain["metrics"]
+
+
 def test_communicator_outliving_its_context_is_inert():
     """destroying the context first (interpreter shutdown order) must not leave the communicator pointing at freed memory"""
     c2 = api.Context(0)

@@ -726,6 +726,36 @@ def test_planner_executable_final_evaluation(ctx, tmp_path):
     assert (pre / "Coverage_images" / "ShapeNet" / "objA" / "64.json").exists()
 
 
+OWNED_SOURCE = (f"synthetic_seed: {SEED}\ntrain_steps: 40\ntrain_rays: 1024\ntrain_width: 64\ntrain_height: 36\nground_truth_seed: 4242\n"
+                "train_deterministic: 1\ndump_scores: 1\nevaluate: 1\nevaluate_views: 5\n"
+                "evaluate_geometry: 1\ngeometry_mc_res: 64\ngeometry_samples: 5000")
+
+
+def run_owned_buffers_config(pre):
+    """method 5 with training in the loop, final evaluation and geometric evaluation, two iterations -> (process, save tree)"""
+    exe = os.path.join(ROOT, "nerf_prv_amd", "prv_planner")
+    cfg = pre / "cfg.yaml"
+    text = YAML.format(pre=pre, vs=os.path.join(GOLD, "hemisphere"), method=5, model_source=OWNED_SOURCE)
+    cfg.write_text(text.replace("num_of_max_iteration: 3", "num_of_max_iteration: 2"))
+    out = subprocess.run([exe, str(cfg)], input="21\nobjA\n-1\n", text=True, capture_output=True, timeout=300)
+    return out, pre / "Compare" / "ShapeNet" / "objA_m5_v1_t0"
+
+
+def test_planner_owned_buffers_leave_the_recorded_choice_and_records(ctx, tmp_path):
+    """every device buffer the shell keeps for an object at once -- the reference images of method 5 and the per-round
+    pick out of them, the training data, the test images of `evaluate: 1`, the reference points and their index of
+    `evaluate_geometry: 1` -- in one two-iteration run: it exits 0 and chooses the views and gathers the records that
+    tests/golden/planner_owned.json holds (recorded from this configuration before the shell's buffers had owners)"""
+    want = json.load(open(os.path.join(GOLD, "planner_owned.json")))
+    out, save = run_owned_buffers_config(tmp_path)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert [l for l in out.stdout.splitlines() if l.startswith("chosen_nbvs:")] == [want["chosen_nbvs"]]
+    assert sorted(p.name for p in (save / "records").iterdir()) == sorted(want["records"])
+    for name, hexed in want["records"].items():
+        assert (save / "records" / name).read_bytes().hex() == hexed, name
+    assert "final PSNR" in out.stdout and list((save / "metrics").glob("*_geometry.txt"))
+
+
 def test_planner_executable_mode4_curve_files_and_stop_label(ctx, tmp_path):
     """mode 4 (main.cpp:2463-2487): one trained + evaluated field per coverage-set size, <gt_path>/<n>.txt in run.py's
     format -- then the stopping criterion (NeRF_fit_curve.cpp:119-206) fits the curve those files describe"""
