@@ -668,7 +668,8 @@ typedef struct prv_train_opts {
                         alpha = 1 - exp(-sigma dt) with that dt; the sample budget (target_samples) is unchanged, its first step
                         casts target_samples / n_samples rays.  A step lists at most 2^24 samples under this rule (64 x the
                         default budget); a batch beyond that makes prv_train_steps fail with PRV_E_STATE */
-  int32_t deterministic; /* 1 (tests): bit-reproducible training -- the ray batches are listed in ray order and the table gradient
+  int32_t deterministic; /* 1 (tests): bit-reproducible training -- the ray batches are listed in ray order (per-block counts, a scan,
+                            then the append: three launches per batch, no block waits for another) and the table gradient
                             is summed in 64-bit fixed point (order-independent) instead of f32 atomics; slower.  0: the product path */
 } prv_train_opts;
 typedef struct prv_trainer prv_trainer;

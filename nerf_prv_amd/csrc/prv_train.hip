@@ -9,6 +9,8 @@
 //                          masks, one returning atomic per block reserves the list range, every lane appends its own live samples.
 //                          From the second step of a call on the batch of step n + 1 is listed by extra blocks of step n's table-Adam
 //                          launch.  train_rays_patch_kernel: patches of adjacent pixels, listed depth step by depth step (an option)
+//                          A deterministic batch (tests) is listed in block order by three launches of its own -- count, scan
+//                          (train_scan_blocks_kernel), append -- and never listed ahead: no workgroup waits for another
 //   train_forward_fast_kernel  a lane pair per sample, 32 samples per wave and round: encode from the canonical table, both MLPs as 24
 //                          v_mfma_f32_32x32x16_f16 on prepacked A fragments (the render kernel's machinery); the B fragments the lanes
 //                          hold between the layers ARE the activations the backward pass needs and are kept (528 B per sample)
@@ -115,29 +117,29 @@ __device__ __forceinline__ bool rays_step(const TrainRaysParams& P, uint32_t bx,
 }
 
 constexpr float kTrainNgpDt = 1.7320508075688772f / 1024.0f; // = sqrtf(3.0f) / 1024.0f, the oracle's value bit for bit (as prv_kernels.hip)
-constexpr int kOrderWord = 144; // scal word of the deterministic append tickets (two, by step parity): sample_count + kOrderWord
-
-// a block's range of the sample list: ONE returning atomic on the step's counter (thread 0 calls).  deterministic: the blocks
-// append in index order -- block `ticket` waits until the blocks before it have appended (workgroups are dispatched in index
-// order, so the ones it waits for are running or done) -- and the list, its tiles and every sum over them are reproducible.
+// a block's range of the sample list (thread 0 calls): ONE returning atomic on the step's counter.  A deterministic batch
+// (tests) is listed in block order without any block waiting for another: the ray kernel runs twice around a scan.  PASS is
+// the kernel's compile-time parameter -- 0: the product's kernel, and the only one inside adam_table_kernel; 1: the count pass
+// leaves the block's total in block_tot[block] and returns (count_block); 2: the append pass finds its base there, the scan
+// having turned the totals into exclusive bases -- so the list, its tiles and every sum over them are reproducible, and the
+// product's kernel holds nothing of it.  A block beyond the step's ray budget returns early: in the count pass it writes its 0
+// itself, the scan reads every block's word and relies on nothing left from an earlier step.
 // A range that does not fit the list sets the sticky overflow flag: every later kernel then sees an empty batch
 // (batch_samples below) and prv_train_steps reports it.
-__device__ __forceinline__ uint32_t reserve_samples(const TrainRaysParams& P, uint32_t* counter, uint32_t step, uint32_t ticket, uint32_t tot) {
+template <int PASS>
+__device__ __forceinline__ uint32_t reserve_samples(const TrainRaysParams& P, uint32_t* counter, uint32_t block, uint32_t tot) {
+  static_assert(PASS == 0 || PASS == 2, "the count pass reserves nothing");
   uint32_t base;
-  if (P.deterministic) {
-    uint32_t* turn = P.sample_count + kOrderWord + (step & 1u);
-    while (__hip_atomic_load(turn, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != ticket) __builtin_amdgcn_s_sleep(1);
-    base = *(volatile uint32_t*)counter;
-    *(volatile uint32_t*)counter = base + tot;
-    __hip_atomic_store(turn, ticket + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-  } else {
-    base = tot ? atomicAdd(counter, tot) : 0u;
-  }
+  if constexpr (PASS == 2) base = P.block_tot[block];
+  else base = tot ? atomicAdd(counter, tot) : 0u;
   if (tot && (unsigned long long)base + tot > (unsigned long long)P.sample_cap) {
     P.state->overflow = 1u;
     base = 0xffffffffu;
   }
   return base;
+}
+__device__ __forceinline__ void count_block(const TrainRaysParams& P, uint32_t block, uint32_t tot) {
+  if (threadIdx.x == 0) P.block_tot[block] = tot;
 }
 // the samples of the step in flight as every kernel behind the ray batch sees them
 __device__ __forceinline__ uint32_t batch_samples(const uint32_t* sample_count, const TrainState* state) {
@@ -147,13 +149,16 @@ __device__ __forceinline__ uint32_t batch_samples(const uint32_t* sample_count, 
 // one WAVE = one ray: the lanes test the occupancy of the ray's steps (64 per round: two rounds for S <= 128 uniform
 // samples, up to sixteen for the engine's 1024 steps), ballots give the live masks (kept in LDS), each lane appends its
 // own live samples at (offset + rank)
-template <bool NGP>
+template <bool NGP, int PASS>
 __device__ __forceinline__ void train_rays_block(const TrainRaysParams& P, uint32_t bx) {
   const int lane = threadIdx.x & 63;
   const uint32_t j = bx * 4u + (threadIdx.x >> 6);
   uint32_t step, n_active_step;
   uint32_t* counter;
-  if (!rays_step(P, bx, step, n_active_step, counter)) return; // whole block beyond this step's ray budget (block-uniform)
+  if (!rays_step(P, bx, step, n_active_step, counter)) { // whole block beyond this step's ray budget (block-uniform)
+    if constexpr (PASS == 1) count_block(P, bx, 0u);
+    return;
+  }
   const bool in_budget = j < n_active_step;
   const uint64_t st = (uint64_t)step * 8u;
   const uint32_t img = (uint32_t)(((uint64_t)rng_u24(P.seed, st + 0, j) * (uint64_t)P.n_img) >> 24);
@@ -194,7 +199,12 @@ __device__ __forceinline__ void train_rays_block(const TrainRaysParams& P, uint3
   // to a single counter were a third of this kernel
   if (lane == 0) cnt[wv] = n_live;
   __syncthreads();
-  if (threadIdx.x == 0) base = reserve_samples(P, counter, step, bx, cnt[0] + cnt[1] + cnt[2] + cnt[3]);
+  if constexpr (PASS == 1) { // the count pass of a deterministic batch: the total, and nothing appended
+    count_block(P, bx, cnt[0] + cnt[1] + cnt[2] + cnt[3]);
+    return;
+  } else if (threadIdx.x == 0) {
+    base = reserve_samples<PASS>(P, counter, bx, cnt[0] + cnt[1] + cnt[2] + cnt[3]);
+  }
   __syncthreads();
   const bool fits = base != 0xffffffffu;
   uint32_t offset = fits ? base : 0u;
@@ -225,11 +235,13 @@ __device__ __forceinline__ void train_rays_block(const TrainRaysParams& P, uint3
     P.rays[j] = r;
   }
 }
+template <int PASS>
 __device__ __forceinline__ void train_rays_block_any(const TrainRaysParams& P, uint32_t bx) {
-  if (P.step_mode == PRV_STEP_NGP) train_rays_block<true>(P, bx);
-  else train_rays_block<false>(P, bx);
+  if (P.step_mode == PRV_STEP_NGP) train_rays_block<true, PASS>(P, bx);
+  else train_rays_block<false, PASS>(P, bx);
 }
-__global__ __launch_bounds__(256) void train_rays_kernel(TrainRaysParams P) { train_rays_block_any(P, blockIdx.x); }
+template <int PASS>
+__global__ __launch_bounds__(256) void train_rays_kernel(TrainRaysParams P) { train_rays_block_any<PASS>(P, blockIdx.x); }
 
 // Patch mode (prv_train_opts.patch_w x patch_h = PP > 1): one BLOCK = one patch of PP adjacent pixels of one image, one
 // wave per ray as above.  The rays of a patch share image, jitter and (nearly) their depth range, so the samples of ONE
@@ -239,13 +251,17 @@ __global__ __launch_bounds__(256) void train_rays_kernel(TrainRaysParams P) { tr
 // the hashed ones included, and the tile's scatter merges them into one add per entry (train_tile_kernel) -- the
 // memory side's atomic-request rate is what bounds the step (profiles/NOTES.md, round 4).  A ray's samples are no longer
 // contiguous in the list: slot_of[ray * S + k] is the list position of its k-th live sample (the compositing kernel's way in).
+template <int PASS>
 __global__ __launch_bounds__(1024) void train_rays_patch_kernel(TrainRaysParams P) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint32_t pw = (uint32_t)P.patch_w, PP = pw * (uint32_t)P.patch_h; // blockDim.x = 64 PP
   const uint32_t q = blockIdx.x, j = q * PP + (uint32_t)wv;
   const uint32_t n_active = P.state->n_active;
   uint32_t* const counter = P.sample_count + (P.state->step & 1u);
-  if (q * PP >= n_active) return; // whole patch beyond this step's ray budget (block-uniform)
+  if (q * PP >= n_active) { // whole patch beyond this step's ray budget (block-uniform)
+    if constexpr (PASS == 1) count_block(P, q, 0u);
+    return;
+  }
   const bool in_budget = j < n_active;
   const uint64_t st = (uint64_t)P.state->step * 8u;
   // image, patch origin and jitter are the PATCH's draws (index q), the background is the ray's (index j)
@@ -297,9 +313,12 @@ __global__ __launch_bounds__(1024) void train_rays_patch_kernel(TrainRaysParams 
     if (lane == 63) wtot[wv] = incl;
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
+  if constexpr (PASS == 1) { // the count pass of a deterministic batch: the total, and nothing appended
+    count_block(P, q, wtot[0] + wtot[1]);
+    return;
+  } else if (threadIdx.x == 0) {
     const uint32_t tot = wtot[0] + wtot[1];
-    base = reserve_samples(P, counter, P.state->step, q, tot); // one returning atomic per patch
+    base = reserve_samples<PASS>(P, counter, q, tot); // one returning atomic per patch
   }
   __syncthreads();
   const bool fits = base != 0xffffffffu;
@@ -1614,7 +1633,6 @@ __global__ void train_begin_kernel(TrainState* state, uint32_t* sample_count, fl
   const double n = (double)(state->step + 1u);
   state->lr_t = (float)((double)lr * sqrt(1.0 - pow((double)beta2, n)) / (1.0 - pow((double)beta1, n)));
   sample_count[state->step & 1u] = 0u;
-  sample_count[kOrderWord + (state->step & 1u)] = 0u;
 }
 
 // ------------------------------------------------------------------ optimiser
@@ -1655,7 +1673,6 @@ __device__ __forceinline__ void end_step(const AdamParams& P, uint32_t* sample_c
     uint32_t* mine = sample_count + ((done - 1u) & 1u);
     sample_count[7] = *mine; // dev: the finished step's listed-sample count stays readable (prv_train_api.inc: PRV_TRAIN_TIMING)
     *mine = 0u;
-    sample_count[kOrderWord + ((done - 1u) & 1u)] = 0u; // ... and its append ticket (deterministic batches)
   }
 }
 
@@ -1677,7 +1694,7 @@ __global__ __launch_bounds__(256) void adam_table_kernel(AdamParams P, size_t n,
   // behind them.
   const unsigned n_ray_blocks = gridDim.x - n_adam_blocks - n_dw_blocks;
   if (blockIdx.x < n_ray_blocks) {
-    train_rays_block_any(R, blockIdx.x);
+    train_rays_block_any<0>(R, blockIdx.x);
     return;
   }
   if (blockIdx.x < n_ray_blocks + n_dw_blocks) {
@@ -1922,10 +1939,53 @@ size_t train_tile_lds_bytes(bool fwd, int mode) {
   return 2u * (size_t)(kWLds + kARows * tsa) + (fwd ? 0u : 4u * (size_t)(kGRows * tsg));
 }
 
+// deterministic batches: block_tot[0, n) -> exclusive bases in place, their total -> the step's counter.  ONE workgroup, which
+// exchanges nothing with any other: thread t sums a contiguous chunk, the <= 1024 chunk sums are scanned across the block (a
+// wave scan, then the wave totals through LDS), thread t rewrites its chunk.  1 <= n; n reaches 2^20 (n_rays = 2^22): 1024 words a thread.
+__global__ __launch_bounds__(1024) void train_scan_blocks_kernel(uint32_t* __restrict__ block_tot, uint32_t n, uint32_t* sample_count, const TrainState* state) {
+  const uint32_t per = (n + blockDim.x - 1u) / blockDim.x;
+  const uint32_t lo = min(threadIdx.x * per, n), hi = min(lo + per, n);
+  uint32_t sum = 0u;
+  for (uint32_t i = lo; i < hi; i++) sum += block_tot[i];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  uint32_t incl = sum;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t u = __shfl_up(incl, d);
+    if (lane >= (uint32_t)d) incl += u;
+  }
+  __shared__ uint32_t wave_tot[16];
+  if (lane == 63u) wave_tot[wv] = incl;
+  __syncthreads();
+  uint32_t base = incl - sum;
+  for (uint32_t w = 0; w < wv; w++) base += wave_tot[w];
+  for (uint32_t i = lo; i < hi; i++) {
+    const uint32_t tot = block_tot[i];
+    block_tot[i] = base;
+    base += tot;
+  }
+  if (threadIdx.x == blockDim.x - 1u) sample_count[state->step & 1u] = base; // the last chunk's end = the batch's samples
+}
+
+// one ray batch.  The product's is one launch; a deterministic one (P.block_tot) is three -- count, scan, append (reserve_samples)
+// -- and nobody else knows: the occupancy masks are computed twice, which a path for tests can afford
+template <int PASS>
+static void launch_rays_pass(const TrainRaysParams& P, unsigned n_blocks, hipStream_t s) {
+  const int pp = P.patch_w * P.patch_h;
+  if (pp > 1) hipLaunchKernelGGL(train_rays_patch_kernel<PASS>, dim3(n_blocks), dim3(64 * pp), 0, s, P);
+  else hipLaunchKernelGGL(train_rays_kernel<PASS>, dim3(n_blocks), dim3(256), 0, s, P);
+}
 hipError_t launch_train_rays(const TrainRaysParams& P, hipStream_t s) {
   const int pp = P.patch_w * P.patch_h;
-  if (pp > 1) hipLaunchKernelGGL(train_rays_patch_kernel, dim3((P.n_rays + pp - 1) / pp), dim3(64 * pp), 0, s, P);
-  else hipLaunchKernelGGL(train_rays_kernel, dim3((P.n_rays + 3) / 4), dim3(256), 0, s, P);
+  const unsigned n_blocks = pp > 1 ? (unsigned)((P.n_rays + pp - 1) / pp) : (unsigned)((P.n_rays + 3) / 4); // >= 1: prv_train_create refuses n_rays < 1
+  if (!P.block_tot) {
+    launch_rays_pass<0>(P, n_blocks, s);
+  } else {
+    launch_rays_pass<1>(P, n_blocks, s);
+    const unsigned n_threads = n_blocks < 1024u ? (n_blocks + 63u) & ~63u : 1024u; // whole waves (the wave scan shuffles)
+    hipLaunchKernelGGL(train_scan_blocks_kernel, dim3(1), dim3(n_threads), 0, s, P.block_tot, n_blocks, P.sample_count, P.state);
+    launch_rays_pass<2>(P, n_blocks, s);
+  }
   return hipGetLastError();
 }
 
@@ -2047,6 +2107,7 @@ hipError_t launch_adam_table(const AdamParams& P, size_t n, float* grad, float* 
   TrainRaysParams R{};
   unsigned n_rays_blocks = 0u;
   if (next_rays) {
+    if (next_rays->block_tot) return hipErrorInvalidValue; // a deterministic batch is launches of its own (launch_train_rays)
     R = *next_rays;
     n_rays_blocks = (unsigned)((R.n_rays + 3) / 4);
   }

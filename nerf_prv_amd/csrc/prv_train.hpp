@@ -57,10 +57,12 @@ struct TrainRaysParams {
   uint32_t* slot_of;
   int step_mode;        // PRV_STEP_FIXED_S | PRV_STEP_NGP (then S = the most steps of a ray, <= 1024)
   uint32_t sample_cap;  // capacity of `samples`; a batch that does not fit sets state->overflow
-  // deterministic = 1 (tests): the blocks append in block order -- block b waits for its ticket (scal word kOrderWord +
-  // (step & 1), zeroed with the sample counters; blocks are dispatched in index order), so the sample list, the tiles and
-  // every sum over them are the same run after run
-  int deterministic;
+  // deterministic batches (tests): block_tot != NULL, one word per block of the ray launch, and launch_train_rays lists the
+  // batch in block order by three launches -- the ray kernel's count instance (block b leaves its total in block_tot[b],
+  // appends nothing), a scan (totals -> exclusive bases, their sum -> the step's counter), the ray kernel's append instance
+  // (block b's base is block_tot[b]) -- so the sample list, the tiles and every sum over them are the same run after run.
+  // The pass is a template parameter of the ray kernels: the product's instance never reads this field
+  uint32_t* block_tot;
 };
 
 struct TrainTileParams {
@@ -164,8 +166,8 @@ hipError_t launch_train_forward_fast(const TrainTileParams& P, const half8* frag
 hipError_t launch_train_composite(const TrainCompositeParams& P, hipStream_t s);
 hipError_t launch_train_begin(TrainState* state, uint32_t* sample_count, float lr, float beta1, float beta2, hipStream_t s);
 // wmv: one {w[4], m[4], v[4]} record (48 B) per group of four table scalars, ceil(n / 4) records
-// next_rays != NULL (single-pixel batches only: the patch kernel has another block size): the NEXT step's ray batch as further
-// extra blocks of the same launch (TrainRaysParams::next = 1)
+// next_rays != NULL (single-pixel batches only: the patch kernel has another block size; never a deterministic batch): the NEXT
+// step's ray batch as further extra blocks of the same launch (TrainRaysParams::next = 1)
 hipError_t launch_adam_table(const AdamParams& P, size_t n, float* grad, float* wmv, uint16_t* w16, hipStream_t s, const float* dw_partial = nullptr,
                              int dw_slots = 0, float* dw_stage = nullptr, const TrainRaysParams* next_rays = nullptr, long long* grad_q = nullptr);
 hipError_t launch_grad_q_to_f32(long long* q, size_t n, float* out, hipStream_t s); // deterministic trainers: fixed-point gradient -> f32, cleared

@@ -19,6 +19,7 @@ struct prv_trainer {
   prv::LevelCanon levels[kMaxLevels];
   Buffer tile_live; // one byte per 32-sample tile of the list (prv_train.hpp: TrainTileParams::tile_live)
   Buffer tab_gq; // deterministic trainers: the table gradient in 64-bit fixed point (prv_train.hip: table_grad_add)
+  Buffer block_tot; // deterministic trainers: a word per block of the ray launch (prv_train.hpp: TrainRaysParams::block_tot)
   uint32_t list_cap = 0; // samples the step's list holds (n_rays x n_samples; PRV_STEP_NGP: at most 2^24)
   Buffer cams, tab_wmv, tab_g, mlp_w, mlp_m, mlp_v, mlp_g, mlp_f, ema, rays, samples, logits, seeds,
       ray_loss, ray_used, scal, losses, dw_part, loss_part, frags, act, slot_of, frag_pos;
@@ -64,10 +65,9 @@ int train_check(prv_trainer* t) {
 
 // scal: [0] sample_count u32 x 2 (a step lists into the word of its parity) | [8] used u64 | [16] loss f32 (scratch of prv_train_gradients) | [24] loss ticket u32 |
 //       [32] TrainState |
-//       [64..] dev-only phase stamps
-//       [576] append tickets u32 x 2 (deterministic ray batches; prv_train.hip: kOrderWord)
+//       [64, 576) dev-only phase stamps
 static prv::TrainState* train_state(prv_trainer* t) { return (prv::TrainState*)((char*)t->scal.p + 32); }
-constexpr size_t kScalOrder = 64 + 64 * 8, kScalBytes = kScalOrder + 64;
+constexpr size_t kScalBytes = 64 + 64 * 8;
 
 // the ray batch of the step in flight (next = false) or of the one after it (true: launched beside the table's Adam pass)
 prv::TrainRaysParams train_rays_params(prv_trainer* t, bool next) {
@@ -98,7 +98,7 @@ prv::TrainRaysParams train_rays_params(prv_trainer* t, bool next) {
   rp.patch_ray_jitter = t->patch_ray_jitter ? 1 : 0;
   rp.step_mode = t->o.step_mode;
   rp.sample_cap = t->list_cap;
-  rp.deterministic = t->o.deterministic ? 1 : 0;
+  rp.block_tot = t->o.deterministic ? (uint32_t*)t->block_tot.p : nullptr;
   return rp;
 }
 
@@ -192,10 +192,11 @@ int train_publish(prv_trainer* t) {
 }
 
 // May the next step's ray batch be listed beside this step's Adam pass?  Single-pixel batches on the fast path only (the
-// patch kernel has another block size; the plain path opens a step with a kernel of its own).
+// patch kernel has another block size; the plain path opens a step with a kernel of its own), and never a deterministic
+// trainer's: its batch is three launches of its own (prv::launch_train_rays), so the shared launch orders nothing.
 static bool can_list_ahead(const prv_trainer* t) {
   static const bool off = getenv("PRV_TRAIN_LIST_AHEAD") && atoi(getenv("PRV_TRAIN_LIST_AHEAD")) == 0; // dev: A/B on one box
-  return !off && t->fast_forward && t->o.patch_w * t->o.patch_h <= 1;
+  return !off && t->fast_forward && t->o.patch_w * t->o.patch_h <= 1 && !t->o.deterministic;
 }
 
 // The launches of one optimiser step behind its ray batch (everything that varies per step is read from TrainState on the
@@ -298,7 +299,6 @@ int train_begin_call(prv_trainer* t, float* losses_dev) {
     st.lr_t = (float)((double)t->o.lr * std::sqrt(1.0 - std::pow((double)t->o.beta2, n)) / (1.0 - std::pow((double)t->o.beta1, n)));
   }
   HIPCHK(t->ctx, hipMemsetAsync(t->scal.p, 0, 8, t->stream)); // the two sample counters (a step lists into the word of its parity)
-  HIPCHK(t->ctx, hipMemsetAsync((char*)t->scal.p + kScalOrder, 0, 8, t->stream)); // ... and their append tickets (deterministic batches)
   t->rays_listed = false;
   HIPCHK(t->ctx, hipMemcpyAsync(train_state(t), &st, sizeof(st), hipMemcpyHostToDevice, t->stream));
   HIPCHK(t->ctx, hipStreamSynchronize(t->stream)); // `st` is a stack object
@@ -358,7 +358,7 @@ void train_release(prv_trainer* t, bool park = false) {
   t->stream = nullptr;
   Buffer* all[] = {&t->cams, &t->tab_wmv, &t->tab_g, &t->mlp_w, &t->mlp_m, &t->mlp_v, &t->mlp_g,
                    &t->mlp_f, &t->ema, &t->rays, &t->samples, &t->logits, &t->seeds, &t->ray_loss, &t->ray_used,
-                   &t->scal, &t->losses, &t->dw_part, &t->loss_part, &t->frags, &t->act, &t->slot_of, &t->frag_pos, &t->tab_gq, &t->tile_live};
+                   &t->scal, &t->losses, &t->dw_part, &t->loss_part, &t->frags, &t->act, &t->slot_of, &t->frag_pos, &t->tab_gq, &t->block_tot, &t->tile_live};
   for (Buffer* b : all) {
     // (parked memory is bounded: 16 GiB of the device's 288, 512 buffers; the oldest go first, so sizes nobody asks for
     // any more do not stay for the life of the context)
@@ -534,6 +534,10 @@ int prv_train_create(prv_ctx* c, int slot, const prv_camset* cs, const uint8_t* 
   if (t->o.patch_w * t->o.patch_h > 1 && (rc = train_buffer(c, t->slot_of, ns * 4)) != PRV_OK) return rc; // list position of (ray, k-th live sample)
   if ((rc = train_buffer(c, t->frag_pos, (size_t)2 * PRV_MLP_HALFS * sizeof(int))) != PRV_OK) return rc; // every weight's place in the forward / backward fragments
   if (o->deterministic && (rc = train_buffer(c, t->tab_gq, t->n_table * 8)) != PRV_OK) return rc;
+  if (o->deterministic) { // a word per block of the ray launch, whichever kernel lists the batch (four rays, or a patch, per block)
+    const size_t pp = (size_t)std::max(t->o.patch_w * t->o.patch_h, 1), nr = (size_t)o->n_rays;
+    if ((rc = train_buffer(c, t->block_tot, std::max((nr + 3) / 4, (nr + pp - 1) / pp) * 4)) != PRV_OK) return rc;
+  }
   if ((rc = train_buffer(c, t->tile_live, ((size_t)t->list_cap + 31) / 32 + 64)) != PRV_OK) return rc;
   // The forward pass keeps its activations for the backward pass (528 B per sample: 512 of activations + the position; PRV_TRAIN_KEEP_ACT=0: recompute).
   // Sized for the step the sample budget aims at, with room for the adaptive ray count to overshoot (it may double from
@@ -555,6 +559,7 @@ int prv_train_create(prv_ctx* c, int slot, const prv_camset* cs, const uint8_t* 
   for (Buffer* b : zero)
     if (e == hipSuccess) e = hipMemsetAsync(b->p, 0, b->bytes, c->stream);
   if (e == hipSuccess && t->tab_gq.p) e = hipMemsetAsync(t->tab_gq.p, 0, t->tab_gq.bytes, c->stream);
+  if (e == hipSuccess && t->block_tot.p) e = hipMemsetAsync(t->block_tot.p, 0, t->block_tot.bytes, c->stream);
   if (e == hipSuccess) e = hipMemsetAsync(t->tile_live.p, 0, t->tile_live.bytes, c->stream);
   if (e == hipSuccess) e = prv::launch_widen_table((const uint16_t*)m.table.p, t->n_table, (float*)t->tab_wmv.p, c->stream);
   if (e == hipSuccess) e = prv::launch_widen((const uint16_t*)m.mlp.p, PRV_MLP_HALFS, (float*)t->mlp_w.p, c->stream);

@@ -485,14 +485,23 @@ def test_deterministic_training_is_bit_reproducible(ctx, oracle, scene, rule):
     np.testing.assert_allclose(gtr.steps(12)[:4], a[3][:4], rtol=1e-3)
 
 
-def test_a_batch_beyond_the_sample_list_fails_loudly(ctx, oracle, scene):
+@pytest.mark.parametrize("deterministic", [0, 1])
+def test_a_batch_beyond_the_sample_list_fails_loudly(ctx, oracle, scene, deterministic):
     """PRV_STEP_NGP: a step may list at most 2^24 samples (64 x the default budget).  200,000 rays of these cameras through an
     all-occupied cube are well beyond it: the call fails with a message, nothing is written out of bounds, and the trainer keeps working for a
-    batch that fits"""
+    batch that fits.  Both ways of reserving a block's range: the product's atomic, and the scanned bases of a deterministic batch"""
     kw, ocams, cams, imgs = scene
     f, otr, gtr = start(ctx, oracle, scene, n_rays=8)
     gtr.close()
-    big = api.Trainer(ctx, 3, cams, ctx.torch.from_numpy(imgs), api.train_opts(step_mode=api.L.STEP_NGP, n_rays=200000, target_samples=0, occ_every=0))
-    with pytest.raises(api.PrvError, match="sample list"):
+    big = api.Trainer(ctx, 3, cams, ctx.torch.from_numpy(imgs), api.train_opts(step_mode=api.L.STEP_NGP, n_rays=200000, target_samples=0, occ_every=0,
+                                                                                deterministic=deterministic))
+    with pytest.raises(api.PrvError) as err:
         big.steps(2)
+    assert err.value.code == api.L.PRV_E_STATE and "sample list" in str(err.value)
     big.close()
+    # the next trainer, whose batch fits, works: the oracle's samples and loss
+    f, otr, gtr = start(ctx, oracle, scene, n_rays=8, deterministic=deterministic)
+    want_loss = otr.gradients()[0]
+    assert gtr.gradients()[0] == pytest.approx(want_loss, rel=1e-3) and gtr.info()["samples_last"] == otr.samples_last > 0
+    assert np.isfinite(gtr.steps(2)).all()
+    gtr.close()
