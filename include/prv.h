@@ -48,6 +48,10 @@ extern "C" {
 #define PRV_SCORE_RAY_ENTROPY 7          /* mean over the view's pixels of prv_render_entropy's H: one model, no reference
                                             images.  This build's own (not in the reference), like 5; the ids mirror the
                                             planner's method_of_IG values, where 6 stays unassigned */
+#define PRV_SCORE_TERMINATION_JSD 9      /* mean over the view's pixels of the Jensen-Shannon divergence between the ensemble
+                                            members' ray-termination histograms (prv_render_termination, prv_termination_divergence):
+                                            2..8 models, no reference images.  This build's own; 8 stays unassigned */
+#define PRV_TERMINATION_BINS_DEFAULT 16  /* depth bins of PRV_SCORE_TERMINATION_JSD's histograms */
 #define PRV_COVERAGE_WEIGHT_DEFAULT 1.0  /* the reference adds its density term with unit weight too (main.cpp:2147-2148) */
 
 #define PRV_MAX_MODELS 8  /* members of one ensemble (one scoring call) */
@@ -296,6 +300,43 @@ int prv_render_footprint(prv_ctx* ctx, int model_slot, const prv_camset* cs, con
 int prv_render_surface(prv_ctx* ctx, int model_slot, const prv_camset* cs, const int* view_ids, int n_views,
                        const prv_render_opts* opts, float level, float* out_entropy_dev, float* out_alpha_dev,
                        float* out_depth_dev, float* out_hit_dev, prv_stats* stats);
+/* The ray-termination histogram of a view (this build's own): WHERE along the ray its samples' weights lie, over positions that
+ * do not depend on the field, so the histograms of different models line up bin for bin.  One density-only launch, like
+ * prv_render_entropy; no colour is evaluated.  Per ray (every spp sub-sample), over exactly the samples, weights w_i = alpha_i T_i
+ * and early termination prv_render_entropy walks:
+ *     bin(i) = (uint32)(i * M) >> 16,  M = floor(n_bins * 65536 / n_max),  i = the sample's step index (t_i = fmaf(i + 0.5, dt, t0)),
+ *     n_max = opts->samples_per_ray under PRV_STEP_FIXED_S, 1024 under PRV_STEP_NGP (there a plain shift): n_bins equal
+ *     stretches of the ray's unit-cube span, bin(i) < n_bins for every i < n_max (the kernel also takes min(bin, n_bins - 1): a
+ *     guard that changes no bin of such a step and keeps any other inside the planes);
+ *     out_bins[k] = the sum of the w_i with bin(i) = k, float32 adds in depth order, starting from 0.
+ * out_bins_dev: n_bins planes of n_views*h*w float32, plane k at out_bins_dev + k * n_views*h*w; required.  n_bins: a power of
+ *   two in [4, 64].  The bins and the escape 1 - alpha sum to 1 within n_bins + 1 roundings.  The pixel of every plane is the
+ *   sum of its sub-samples in order, times 1/spp.  Rays that miss the box or have no live sample, and bins no live sample of
+ *   the ray falls in, give exactly 0.
+ *   The values depend on n_bins and on the stepping rule (which samples exist and which bin they fall in): they compare between
+ *   models and views of one set of options, not across them.
+ * out_alpha_dev: n_views*h*w float32, the pixel's opacity; may be NULL.
+ * CONTRACT: out_alpha_dev and stats are bit-identical to prv_render_entropy's for the same call.
+ * Errors (PRV_E_INVALID with a message): n_bins not a power of two in [4, 64]; a NULL out_bins_dev; a host pointer. */
+int prv_render_termination(prv_ctx* ctx, int model_slot, const prv_camset* cs, const int* view_ids, int n_views,
+                           const prv_render_opts* opts, int n_bins, float* out_bins_dev, float* out_alpha_dev, prv_stats* stats);
+/* The Jensen-Shannon divergence between n_models termination histograms, per pixel, and its mean per view: the reduce of
+ * PRV_SCORE_TERMINATION_JSD alone, on planes the caller holds (prv_render_termination's, one call per model with the same views
+ * and options).  bins_dev[e]: n_bins planes of n_views*width*height float32; alpha_dev[e]: n_views*width*height float32.
+ * Per pixel, with p_e[k] (k < n_bins) member e's bins and p_e[n_bins] = 1.0f - alpha_e its escape, all float32 in this order:
+ *     m_k = (p_0[k] + p_1[k] + ... + p_{E-1}[k]) * (1.0f / E)                 (members in argument order)
+ *     h(p) = p >= 2^-126 ? -p log2(p) : 0                                     (prv_render_entropy's h and hardware log)
+ *     A = sum_k h(m_k),  B_e = sum_k h(p_e[k])                                (k ascending, each term one fmaf as there)
+ *     J = max(A - (B_0 + ... + B_{E-1}) * (1.0f / E), 0)                      bits
+ * J = H(mean of the members) - mean of the members' H: 0 where the members agree however spread the ray is (exactly 0.0 for two
+ * identical members), at most log2(E) where they stop in different places.
+ * out_jsd_dev: n_views*width*height float32 J, or NULL.  view_jsd_host / view_opacity_host: n_views doubles each, the view's
+ * mean J and the mean over members and pixels of alpha (per pixel (a_0 + ... + a_{E-1}) * (1.0f / E) in float32; the sums over
+ * pixels in fp64, block partials summed in block order: deterministic); either may be NULL.
+ * Errors (PRV_E_INVALID with a message): n_models outside 2..PRV_MAX_MODELS; n_bins as above; a NULL or host plane. */
+int prv_termination_divergence(prv_ctx* ctx, const float* const* bins_dev, const float* const* alpha_dev, int n_models,
+                               int n_views, int width, int height, int n_bins, float* out_jsd_dev, double* view_jsd_host,
+                               double* view_opacity_host);
 
 /* replaces: Perception_3D::precept / precept_thread_process, the reference's CPU render path
  * (main.cpp:98-284: project -> ray -> OctoMap castRay, max range main.cpp:258).  Per pixel the
@@ -351,6 +392,12 @@ int prv_evaluate(prv_ctx* ctx, int model_slot, const prv_camset* cs, const int* 
  *   method 7   : model_slots[0] alone (n_models == 1, gt_rgba_dev NULL): score = the mean over the view's pixels of
  *                prv_render_entropy's H in fp64 (block partials summed in block order: deterministic), coverage = the mean
  *                opacity, psnr = 0.  The march and the entropy kernel are the round's only render launches; no colour image.
+ *   method 9   : model_slots = the ensemble (2..8 models, gt_rgba_dev NULL): score = the view's mean J of
+ *                prv_termination_divergence over the members' prv_render_termination planes at PRV_TERMINATION_BINS_DEFAULT
+ *                bins (fp64, deterministic), coverage = the mean over members and pixels of the opacity, psnr = 0.  The members
+ *                are rendered one after another per batch of views (E density-only launches, no colour image), then reduced;
+ *                only one batch's planes are resident.  Scores compare between the views of one call: the bin count and the
+ *                stepping rule change them.
  * records_host and/or records_dev (n_views records) receive the result; records_dev is
  * what a caller hands to its all-gather. */
 int prv_score_views(prv_ctx* ctx, int method, const int* model_slots, int n_models,

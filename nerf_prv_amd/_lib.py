@@ -21,6 +21,8 @@ SCORE_ENSEMBLE_RGB = 2
 SCORE_ENSEMBLE_RGB_DENSITY = 3
 SCORE_PSNR_COVERAGE = 5
 SCORE_RAY_ENTROPY = 7
+SCORE_TERMINATION_JSD = 9
+TERMINATION_BINS_DEFAULT = 16
 STEP_FIXED_S = 0  # prv.h: samples_per_ray uniform samples between the AABB hits (BASELINE configs[1], [3])
 STEP_NGP = 1      # instant-ngp's rule, what run.py:304 renders with: dt = sqrt(3)/1024, every step tested, no cap
 NGP_MAX_STEPS = 1024
@@ -164,6 +166,8 @@ SIGNATURES = {
     "prv_render_rgba8": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), _vp, _P(Stats)]),
     "prv_render_depth": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), _vp, _vp, _P(Stats)]),
     "prv_render_entropy": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), _vp, _vp, _P(Stats)]),
+    "prv_render_termination": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), _i, _vp, _vp, _P(Stats)]),
+    "prv_termination_divergence": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "prv_render_footprint": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), _vp, _vp, _vp, _P(Stats)]),
     "prv_render_surface": (_i, [_vp, _i, _vp, _vp, _i, _P(RenderOpts), C.c_float, _vp, _vp, _vp, _vp, _P(Stats)]),
     "prv_select_default_opts": (_i, [_P(SelectOpts)]),

@@ -338,6 +338,35 @@ class Context:
                                               _ptr(out_alpha), C.byref(st) if want_stats else None))
         return out, out_alpha, st
 
+    def render_termination(self, slot, camset, view_ids, opts, n_bins=L.TERMINATION_BINS_DEFAULT, want_stats=True):
+        """prv_render_termination -> (bins [n_bins, n, h, w] float32, alpha [n, h, w] float32, stats).  bins[k]: the ray's
+        compositing weights that fall in depth bin k of its unit-cube span (bin positions do not depend on the field, so
+        different models' histograms line up); alpha: `render_entropy`'s, bit for bit.  No colour evaluated."""
+        ids = self._ids(camset, view_ids)
+        bins = self.torch.empty((max(int(n_bins), 0), len(ids), opts.height, opts.width), dtype=self.torch.float32, device=self.device)
+        alpha = self.torch.empty((len(ids), opts.height, opts.width), dtype=self.torch.float32, device=self.device)
+        st = L.Stats()
+        self._chk(self.lib.prv_render_termination(self.handle, slot, camset.handle, _ptr(ids), len(ids), C.byref(opts), int(n_bins),
+                                                  _ptr(bins), _ptr(alpha), C.byref(st) if want_stats else None))
+        return bins, alpha, st
+
+    def termination_divergence(self, bins, alphas, want_image=True):
+        """prv_termination_divergence on the members' device planes (bins[e]: [n_bins, n, h, w], alphas[e]: [n, h, w], as
+        `render_termination` returns them) -> (jsd [n, h, w] float32 in bits or None, view mean jsd [n] float64, view mean
+        opacity [n] float64)"""
+        if len(bins) == 0 or len(bins) != len(alphas):
+            raise ValueError("one bins tensor and one alpha plane per member, at least one member")
+        n_bins, n, h, w = (int(x) for x in bins[0].shape)
+        for b, a in zip(bins, alphas):
+            if tuple(b.shape) != (n_bins, n, h, w) or tuple(a.shape) != (n, h, w) or not b.is_contiguous() or not a.is_contiguous():
+                raise ValueError("every member needs contiguous planes of one shape: bins [n_bins, n, h, w], alpha [n, h, w]")
+        barr = (C.c_void_p * len(bins))(*[b.data_ptr() for b in bins])
+        aarr = (C.c_void_p * len(alphas))(*[a.data_ptr() for a in alphas])
+        out = self.torch.empty((n, h, w), dtype=self.torch.float32, device=self.device) if want_image else None
+        vj, vo = np.zeros(n, np.float64), np.zeros(n, np.float64)
+        self._chk(self.lib.prv_termination_divergence(self.handle, barr, aarr, len(bins), n, w, h, n_bins, _ptr(out), _ptr(vj), _ptr(vo)))
+        return out, vj, vo
+
     def render_footprint(self, slot, camset, view_ids, opts, want_stats=True):
         """prv_render_footprint -> (entropy, alpha, depth: [n, h, w] float32 each, stats): `render_entropy`'s two planes and
         `render_depth`'s depth plane, bit for bit, from one density-only launch"""
@@ -451,7 +480,8 @@ class Context:
     def score_views(self, method, slots, camset, view_ids, opts, gt=None, records_dev=None, to_host=True,
                     want_stats=False):
         """prv_score_views: SCORE_ENSEMBLE_RGB / _RGB_DENSITY (slots = the ensemble), SCORE_PSNR_COVERAGE (one slot, gt = the
-        views' reference images) or SCORE_RAY_ENTROPY (one slot, no gt: the mean of `render_entropy` per view)"""
+        views' reference images), SCORE_RAY_ENTROPY (one slot, no gt: the mean of `render_entropy` per view) or
+        SCORE_TERMINATION_JSD (slots = an ensemble of 2..8, no gt: the mean of `termination_divergence` per view at 16 bins)"""
         ids = self._ids(camset, view_ids)
         slots = np.ascontiguousarray(slots, np.int32)
         rec = np.zeros(len(ids), RECORD_DTYPE) if to_host else None

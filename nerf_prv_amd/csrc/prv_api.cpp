@@ -85,6 +85,8 @@ struct prv_ctx {
   Buffer stage_depth; // prv_render_depth with spp > 1: the sub-samples' depth images (spp x batch x image floats)
   Buffer stage_foot;  // prv_render_footprint with spp > 1: the sub-samples' depth images (stage_depth holds their entropy)
   Buffer stage_hit;   // prv_render_surface with spp > 1: the sub-samples' hit flags (its depth images go to stage_foot)
+  Buffer stage_bins;  // prv_render_termination with spp > 1: the sub-samples' bin planes (n_bins x spp x batch x image floats)
+  Buffer term_planes; // PRV_SCORE_TERMINATION_JSD: one batch of views' bin and opacity planes of every member
   Buffer sel_planes, sel_voxel, sel_q, sel_bits, sel_sums; // prv_select_*: the footprint planes of prv_select_views, voxel and gain per pixel, the covered bitset, the views' sums
   Buffer counters_multi, occ_multi; // the ensemble's one-launch march: queue heads + counts per member, the interleaved occupancy bytes
   int march_multi = -1;             // PRV_MARCH_MULTI=0/1 (-1: on where an instance exists, render_ensemble_ngp)
@@ -816,6 +818,7 @@ RenderParams render_params(prv_ctx* c, const Model& m, const prv_render_opts* o,
 //   kRenderEntropy   (prv_render_entropy, PRV_SCORE_RAY_ENTROPY): no colour at all -- the march and the planes kernel, which writes entropy and alpha
 //   kRenderFootprint (prv_render_footprint): as kRenderEntropy, and depth from the same launch
 //   kRenderSurface   (prv_render_surface):   as kRenderEntropy, and the first-crossing depth and its hit flag from the same launch
+//   kRenderTermination (prv_render_termination, PRV_SCORE_TERMINATION_JSD): as kRenderEntropy, with n_bins bin planes where its entropy plane is
 struct RenderTargets {
   int mode = kRenderColour;
   float* rgba = nullptr;    // H * W * 4 floats per view
@@ -823,6 +826,9 @@ struct RenderTargets {
   float *depth = nullptr, *entropy = nullptr, *alpha = nullptr; // H * W floats per view
   float* hit = nullptr;                                         // kRenderSurface: H * W floats per view
   float level = 0.5f;                                           // kRenderSurface: the accumulated opacity a ray is located at
+  float* bins = nullptr;                                        // kRenderTermination: n_bins planes, bins_stride floats apart, H * W floats per view each
+  int n_bins = 0;
+  size_t bins_stride = 0;
   bool zero_stats = true;      // the call starts a new statistics window
   bool private_output = false; // the caller consumes rgba / the planes through the views' cull rectangles only
 };
@@ -831,7 +837,7 @@ struct RenderTargets {
 int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, const prv_render_opts* o,
                  const RenderTargets& t) {
   const bool colour = t.mode == kRenderColour || t.mode == kRenderDepth; // the launch writes an RGBA image
-  const bool surface = t.mode == kRenderSurface;
+  const bool surface = t.mode == kRenderSurface, term = t.mode == kRenderTermination;
   const bool depth = t.mode == kRenderDepth || t.mode == kRenderFootprint || surface;
   const bool private_output = t.private_output && o->spp == 1 && !t.rgba8 && !depth; // sub-sample staging, byte and depth images are written in full
   const Model& m = c->models[slot];
@@ -866,12 +872,14 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
   } planes[4];
   int n_planes = 0;
   if (!colour) { // H where the depth render's depth would go, the opacity where the colour would
-    planes[n_planes++] = {t.entropy, &c->stage_depth, &RenderPlanesParams::out_entropy};
+    if (!term) planes[n_planes++] = {t.entropy, &c->stage_depth, &RenderPlanesParams::out_entropy};
     planes[n_planes++] = {t.alpha, &c->stage, &RenderPlanesParams::out_alpha};
   }
+  // the termination mode's bin planes are not in that list: n_bins of them, one stride apart, behind ONE kernel parameter
+  const size_t n_bins = term ? (size_t)t.n_bins : 0;
   if (depth) planes[n_planes++] = {t.depth, colour ? &c->stage_depth : &c->stage_foot, &RenderPlanesParams::out_depth};
   if (surface) planes[n_planes++] = {t.hit, &c->stage_hit, &RenderPlanesParams::out_hit};
-  const size_t stage_px = (colour ? 16 : 0) + 4 * (size_t)n_planes; // staging bytes per sub-sample pixel
+  const size_t stage_px = (colour ? 16 : 0) + 4 * ((size_t)n_planes + n_bins); // staging bytes per sub-sample pixel
   if (spp > 1) batch = std::min<size_t>(batch, std::max<size_t>(1, c->stage_budget / (npix * stage_px * (size_t)spp)));
   if (batch * npix * (size_t)spp >= (1ull << 32)) batch = ((1ull << 32) - 1) / (npix * (size_t)spp); // 32-bit pixel ids
   if (batch == 0) return fail(c, PRV_E_INVALID, "image x spp too large");
@@ -883,6 +891,7 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
   if (spp > 1 && colour && (rc = ensure(c, c->stage, batch * npix * (size_t)spp * 16)) != PRV_OK) return rc;
   for (int i = 0; i < n_planes && spp > 1; i++)
     if ((rc = ensure(c, *planes[i].stage, batch * npix * (size_t)spp * 4)) != PRV_OK) return rc;
+  if (term && spp > 1 && (rc = ensure(c, c->stage_bins, n_bins * batch * npix * (size_t)spp * 4)) != PRV_OK) return rc;
 
   const int n_blocks = render_blocks(c, m, npix);
   for (size_t b0 = 0; b0 < (size_t)n_views; b0 += batch) {
@@ -895,6 +904,14 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
       target[i] = spp > 1 ? (float*)planes[i].stage->p : dst[i];
       HIPCHK(c, hipMemsetAsync(target[i], 0, (size_t)nb * npix * (size_t)spp * 4, c->stream));
     }
+    // the bin planes: the sub-samples' go to the staging buffer, one launch's pixels apart; spp = 1 renders straight into the caller's
+    const size_t bins_stride = spp > 1 ? (size_t)nb * npix * (size_t)spp : t.bins_stride;
+    float* const bins_target = !term ? nullptr : spp > 1 ? (float*)c->stage_bins.p : t.bins + b0 * npix;
+    // (one fill where the launch's planes lie back to back: the staging buffer always, the caller's planes when this batch is all of them)
+    const size_t plane_px = (size_t)nb * npix * (size_t)spp;
+    if (n_bins && bins_stride == plane_px) HIPCHK(c, hipMemsetAsync(bins_target, 0, n_bins * plane_px * 4, c->stream));
+    else
+      for (size_t k = 0; k < n_bins; k++) HIPCHK(c, hipMemsetAsync(bins_target + k * bins_stride, 0, plane_px * 4, c->stream));
     // one fill per batch: heads and counts, and with them the statistics when this call starts a new window
     HIPCHK(c, hipMemsetAsync(c->counters.p, 0, b0 == 0 && t.zero_stats ? kCountersBytes : kStatOffset, c->stream));
     MarchParams mp;
@@ -938,6 +955,12 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
     pp.npix = (uint32_t)npix;
     pp.nb = (uint32_t)nb;
     pp.T_cross = 1.0f - t.level;
+    if (term) {
+      pp.out_bins = bins_target;
+      pp.plane_stride = bins_stride;
+      pp.n_bins = (uint32_t)n_bins;
+      pp.bin_mul = (uint32_t)(n_bins * 65536u / (size_t)(ngp ? kNgpMaxSteps : o->samples_per_ray));
+    }
     if ((rc = timed(c, c->ev_render, [&] {
            HIPCHK(c, n_planes ? launch_render_planes(pp, t.mode, n_blocks, c->stream) : launch_render(pp.r, n_blocks, c->stream));
            return PRV_OK;
@@ -945,6 +968,8 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
       return rc;
     if (spp > 1 && colour) HIPCHK(c, launch_spp_reduce((const float*)c->stage.p, (size_t)nb * npix, spp, o->background, dst_f32, dst_u8, c->stream));
     for (int i = 0; i < n_planes && spp > 1; i++) HIPCHK(c, launch_spp_reduce_depth(target[i], (size_t)nb * npix, spp, dst[i], c->stream));
+    for (size_t k = 0; k < n_bins && spp > 1; k++)
+      HIPCHK(c, launch_spp_reduce_depth(bins_target + k * bins_stride, (size_t)nb * npix, spp, t.bins + k * t.bins_stride + b0 * npix, c->stream));
   }
   return PRV_OK;
 }
@@ -1179,6 +1204,8 @@ void prv_destroy(prv_ctx* c) {
   release(c->stage_depth);
   release(c->stage_foot);
   release(c->stage_hit);
+  release(c->stage_bins);
+  release(c->term_planes);
   for (Buffer* b : {&c->sel_planes, &c->sel_voxel, &c->sel_q, &c->sel_bits, &c->sel_sums}) release(*b);
   release(c->counters);
   if (c->pin) (void)hipHostFree(c->pin);
@@ -1710,6 +1737,84 @@ int prv_render_surface(prv_ctx* c, int slot, const prv_camset* cs, const int* vi
                       "bad camset / view count / surface output (entropy, alpha, depth and hit planes are all required)");
 } catch (...) { return caught(c); }
 
+namespace {
+int check_termination_bins(prv_ctx* c, int n_bins) {
+  if (n_bins < 4 || n_bins > 64 || (n_bins & (n_bins - 1)) != 0) return fail(c, PRV_E_INVALID, "n_bins must be a power of two in [4, 64], got %d", n_bins);
+  return PRV_OK;
+}
+} // namespace
+
+int prv_render_termination(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, const prv_render_opts* o, int n_bins,
+                           float* out_bins, float* out_alpha, prv_stats* st) try {
+  if (!c) return PRV_E_INVALID;
+  int rc;
+  if ((rc = check_opts(c, o)) != PRV_OK || (rc = check_termination_bins(c, n_bins)) != PRV_OK) return rc;
+  RenderTargets t; // a null out_alpha: the kernel writes the opacity anyway, into the context's scratch
+  t.mode = kRenderTermination;
+  t.bins = out_bins;
+  t.n_bins = n_bins;
+  t.bins_stride = (size_t)std::max(n_views, 0) * o->width * o->height;
+  t.alpha = out_alpha;
+  return render_entry(c, slot, cs, view_ids, n_views, o, st, t, {{out_bins, "out_bins_dev"}, {out_alpha, "out_alpha_dev"}}, !out_bins,
+                      "bad camset / view count / termination output (the bin planes are required)", &RenderTargets::alpha, 4);
+} catch (...) { return caught(c); }
+
+namespace {
+// the reduce of PRV_SCORE_TERMINATION_JSD over n_views views' planes: partials in c->partial, then (rec not null) one record per view (score = mean J, coverage = mean opacity)
+int termination_jsd_dev(prv_ctx* c, TerminationJsdParams P, int n_views, prv_score_record* rec) {
+  const int nblk = score_blocks(P.npix);
+  int rc;
+  if ((rc = ensure(c, c->partial, (size_t)n_views * nblk * 2 * sizeof(double))) != PRV_OK) return rc;
+  P.partial = (double*)c->partial.p;
+  HIPCHK(c, launch_score_termination_jsd(P, n_views, nblk, c->stream));
+  if (rec) HIPCHK(c, launch_score_finalize((const double*)c->partial.p, n_views, nblk, PRV_SCORE_RAY_ENTROPY, P.npix, 0.0, rec, c->stream)); // the same two means
+  return PRV_OK;
+}
+} // namespace
+
+int prv_termination_divergence(prv_ctx* c, const float* const* bins, const float* const* alpha, int n_models, int n_views, int W, int H,
+                               int n_bins, float* out_jsd, double* view_jsd, double* view_opacity) try {
+  if (!c) return PRV_E_INVALID;
+  int rc;
+  if (n_models < 2 || n_models > PRV_MAX_MODELS) return fail(c, PRV_E_INVALID, "the divergence takes 2..%d models, got %d", PRV_MAX_MODELS, n_models);
+  if ((rc = check_termination_bins(c, n_bins)) != PRV_OK) return rc;
+  if (!bins || !alpha || n_views < 0 || W < 1 || H < 1 || W > 16384 || H > 16384) return fail(c, PRV_E_INVALID, "bad argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  for (int e = 0; e < n_models; e++) {
+    if (!bins[e] || !alpha[e]) return fail(c, PRV_E_INVALID, "member %d: the bin and opacity planes are required", e);
+    if ((rc = check_device_ptr(c, bins[e], "bins_dev") ) != PRV_OK || (rc = check_device_ptr(c, alpha[e], "alpha_dev")) != PRV_OK) return rc;
+  }
+  if ((rc = check_device_ptr(c, out_jsd, "out_jsd_dev")) != PRV_OK) return rc;
+  if (n_views == 0) return PRV_OK;
+  TerminationJsdParams P;
+  memset(&P, 0, sizeof(P));
+  for (int e = 0; e < n_models; e++) {
+    P.bins[e] = bins[e];
+    P.alpha[e] = alpha[e];
+  }
+  P.E = n_models;
+  P.n_bins = n_bins;
+  P.npix = (size_t)W * H;
+  P.plane_stride = (size_t)n_views * P.npix;
+  P.out_jsd = out_jsd;
+  if ((rc = termination_jsd_dev(c, P, n_views, nullptr)) != PRV_OK) return rc;
+  // the block partials, summed in block order as score_finalize_kernel sums them (method 9's record score is view_jsd's bits; the
+  // opacity keeps its fp64 here, where a record rounds it to float)
+  const int nblk = score_blocks(P.npix);
+  std::vector<double> part((size_t)n_views * nblk * 2);
+  if ((rc = prv_memcpy_d2h(c, part.data(), c->partial.p, part.size() * sizeof(double))) != PRV_OK) return rc;
+  for (int v = 0; v < n_views; v++) {
+    double sj = 0.0, sa = 0.0;
+    for (int b = 0; b < nblk; b++) {
+      sj += part[((size_t)v * nblk + b) * 2 + 0];
+      sa += part[((size_t)v * nblk + b) * 2 + 1];
+    }
+    if (view_jsd) view_jsd[v] = sj / (double)P.npix;
+    if (view_opacity) view_opacity[v] = sa / (double)P.npix;
+  }
+  return PRV_OK;
+} catch (...) { return caught(c); }
+
 int prv_first_hit(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, int W, int H,
                   float max_range, int32_t* out) try {
   if (!c) return PRV_E_INVALID;
@@ -1945,11 +2050,13 @@ int prv_score_views(prv_ctx* c, int method, const int* model_slots, int n_models
   if ((rc = check_opts(c, o)) != PRV_OK) return rc;
   if (!cs || !model_slots || n_views < 0) return fail(c, PRV_E_INVALID, "bad argument");
   const bool ens = method == PRV_SCORE_ENSEMBLE_RGB || method == PRV_SCORE_ENSEMBLE_RGB_DENSITY;
-  const bool entropy = method == PRV_SCORE_RAY_ENTROPY;
-  if (!ens && !entropy && method != PRV_SCORE_PSNR_COVERAGE) return fail(c, PRV_E_INVALID, "unknown score method %d", method);
+  const bool entropy = method == PRV_SCORE_RAY_ENTROPY, jsd = method == PRV_SCORE_TERMINATION_JSD;
+  if (jsd && (n_models < 2 || n_models > PRV_MAX_MODELS || gt))
+    return fail(c, PRV_E_INVALID, "method 9 scores an ensemble of 2..%d models (got %d) and takes no reference images", PRV_MAX_MODELS, n_models);
+  if (!ens && !entropy && !jsd && method != PRV_SCORE_PSNR_COVERAGE) return fail(c, PRV_E_INVALID, "unknown score method %d", method);
   if (ens && (n_models < 1 || n_models > PRV_MAX_MODELS)) return fail(c, PRV_E_INVALID, "ensemble size %d", n_models);
   if (entropy && (n_models != 1 || gt)) return fail(c, PRV_E_INVALID, "method 7 scores one model and takes no reference images");
-  if (!ens && !entropy && (n_models != 1 || !gt)) return fail(c, PRV_E_INVALID, "method 5 needs one model and reference images");
+  if (!ens && !entropy && !jsd && (n_models != 1 || !gt)) return fail(c, PRV_E_INVALID, "method 5 needs one model and reference images");
   for (int e = 0; e < n_models; e++)
     if ((rc = check_model(c, model_slots[e])) != PRV_OK) return rc;
   HIPCHK(c, hipSetDevice(c->device));
@@ -1957,8 +2064,47 @@ int prv_score_views(prv_ctx* c, int method, const int* model_slots, int n_models
   const size_t npix = (size_t)o->width * o->height;
   if ((rc = ensure(c, c->records, std::max<size_t>(16, (size_t)n_views * sizeof(prv_score_record)))) != PRV_OK) return rc;
   prv_score_record* rec = (prv_score_record*)c->records.p;
-  if ((rc = ensure(c, c->img_f32, std::max<size_t>(16, (size_t)n_views * npix * (entropy ? 8 : 16)))) != PRV_OK) return rc;
-  if (entropy) {
+  if (!jsd && (rc = ensure(c, c->img_f32, std::max<size_t>(16, (size_t)n_views * npix * (entropy ? 8 : 16)))) != PRV_OK) return rc;
+  if (jsd) {
+    // per batch of views: every member's termination planes (the march and one density-only launch each, no colour image), then
+    // the divergence reduce over them; only that batch's planes are resident.  Which views share a batch changes no pixel and no
+    // view's partial sums
+    constexpr size_t K = PRV_TERMINATION_BINS_DEFAULT;
+    const size_t view_bytes = (size_t)n_models * (K + 1) * npix * 4;
+    const size_t batch = std::min<size_t>(std::max<size_t>(1, c->stage_budget / view_bytes), (size_t)std::max(n_views, 1));
+    if ((rc = ensure(c, c->term_planes, batch * view_bytes)) != PRV_OK) return rc;
+    if (n_views == 0) { // (a new statistics window all the same)
+      RenderTargets t;
+      t.mode = kRenderTermination;
+      if ((rc = render_views(c, model_slots[0], cs, view_ids, 0, o, t)) != PRV_OK) return rc;
+    }
+    std::vector<int> ids((size_t)std::max(n_views, 0)); // (a NULL view_ids lists the camera set's views in order)
+    for (int i = 0; i < n_views; i++) ids[i] = view_ids ? view_ids[i] : i;
+    for (size_t b0 = 0; b0 < (size_t)n_views; b0 += batch) {
+      const size_t nb = std::min(batch, (size_t)n_views - b0), member = (K + 1) * nb * npix; // a member: K bin planes, then its opacity
+      TerminationJsdParams P;
+      memset(&P, 0, sizeof(P));
+      for (int e = 0; e < n_models; e++) {
+        float* base = (float*)c->term_planes.p + (size_t)e * member;
+        RenderTargets t;
+        t.mode = kRenderTermination;
+        t.bins = base;
+        t.n_bins = (int)K;
+        t.bins_stride = nb * npix;
+        t.alpha = base + K * nb * npix;
+        t.zero_stats = b0 == 0 && e == 0;
+        t.private_output = o->spp == 1;
+        if ((rc = render_views(c, model_slots[e], cs, ids.data() + b0, (int)nb, o, t)) != PRV_OK) return rc;
+        P.bins[e] = t.bins;
+        P.alpha[e] = t.alpha;
+      }
+      P.E = n_models;
+      P.n_bins = (int)K;
+      P.npix = npix;
+      P.plane_stride = nb * npix;
+      if ((rc = termination_jsd_dev(c, P, (int)nb, rec + b0)) != PRV_OK) return rc;
+    }
+  } else if (entropy) {
     // no colour image: the march and the entropy kernel fill the view's entropy and opacity planes (zeroed first, so the tiles
     // outside a view's cull rectangle need not be launched), one reduce sums both
     float* hp = (float*)c->img_f32.p;

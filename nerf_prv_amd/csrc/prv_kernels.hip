@@ -743,13 +743,21 @@ __device__ __forceinline__ float entropy_add(float p, float H) { return p >= 1.1
 // the footprint mode has its FMA, t kept live across mlp_density2 as there -- and at ray end z = Dm * dot(d, f) to
 // X->out_depth[pix], with the depth mode's cosine, and Dm > 0 as 1.0 / 0.0 to X->out_hit[pix].  H and 1 - T are the entropy
 // mode's bits.  Movable state: five words, {record, next sample, T, H, Dm}; Dm lives in the footprint mode's D.
+// kRenderTermination (prv_render_termination): density-only like the entropy mode, but no H: the ray's compositing weights go to
+// a histogram over X->n_bins depth bins of its unit-cube span.  Sample i falls in bin (i * X->bin_mul) >> 16 (the host:
+// bin_mul = floor(n_bins * 65536 / n_max), n_max = the most steps a ray can have under the rule, so the bin never reaches n_bins
+// and depends on the ray and the rule alone).  The lane keeps the open bin and its sum (one float add per sample, depth order);
+// when the bin changes the sum goes to X->out_bins[bin * X->plane_stride + pix] with one store and restarts at 0, the open bin is
+// flushed at ray end beside 1 - T to X->out_alpha[pix] (the entropy mode's bits).  A bin address is written at most once per
+// ray, by whichever lane holds the ray then: no atomics, nothing read back.  Movable state: five words, {record, next sample,
+// T, sum, bin}; the sum lives in the entropy mode's H.
 template <int F, int NDENSE, bool NGP, bool CACHE, int MODE>
 __device__ __forceinline__ void render_queue64_body(RenderParams P, const RenderPlanesParams* X) {
-  constexpr bool FOOT = MODE == kRenderFootprint, SURF = MODE == kRenderSurface;
-  constexpr bool DEPTH = MODE == kRenderDepth || FOOT, ENTROPY = MODE == kRenderEntropy || FOOT || SURF; // DEPTH: the D sum; ENTROPY: density layers only, the H sum
+  constexpr bool FOOT = MODE == kRenderFootprint, SURF = MODE == kRenderSurface, TERM = MODE == kRenderTermination;
+  constexpr bool DEPTH = MODE == kRenderDepth || FOOT, ENTROPY = MODE == kRenderEntropy || FOOT || SURF || TERM; // DEPTH: the D sum; ENTROPY: density layers only, the H sum (TERM: the open bin's sum in its place)
   constexpr bool DSTATE = DEPTH || SURF;                        // the ray carries D (SURF: Dm) and keeps its sample's t across the MLP
   constexpr int kDWord = ENTROPY ? 4 : 6;                       // where D sits in the movable state
-  constexpr int kMoveWords = (ENTROPY ? 4 : 6) + (DSTATE ? 1 : 0); // {record, next sample, T, r, g, b (, D)} or {record, next sample, T, H (, D)}
+  constexpr int kMoveWords = (ENTROPY ? 4 : 6) + (DSTATE || TERM ? 1 : 0); // {record, next sample, T, r, g, b (, D)} or {record, next sample, T, H (, D)}; TERM: {.., sum, bin}
   constexpr int kFrags = ENTROPY ? 8 : kNumFrags;       // fragment sets staged in LDS: the density layers', or both MLPs'
   __shared__ half8 wl[kFrags * 64];
   __shared__ uint32_t mv[4][32][kMoveWords]; // tail merges: {record, next sample, T, r, g, b (, D)} of the rays that change slots, per wave
@@ -789,7 +797,8 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
   uint32_t cur = 0, m1 = 0, m2 = 0, m3 = 0, base = 0;
   float T = 1.f, cr = 0.f, cg = 0.f, cb = 0.f;
   float D = 0.f; // DEPTH: sum of w_i t_i so far; SURF: Dm, the t of the first crossing, 0 before it
-  float Hs = 0.f; // ENTROPY: sum of h(w_i) so far
+  float Hs = 0.f; // ENTROPY: sum of h(w_i) so far; TERM: sum of the w_i of the open bin
+  uint32_t tbin = 0u; // TERM: the open bin
   half8 shA = {0, 0, 0, 0, 0, 0, 0, 0}, shB = {0, 0, 0, 0, 0, 0, 0, 0}; // SH rows [8g, 8g+8) of the rays in slots (r, A) and (r, B)
   bool drained = false;
   unsigned long long n_eval = 0ull, n_rounds = 0ull;
@@ -895,6 +904,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
             e[5] = __float_as_uint(cb);
           }
           if constexpr (DSTATE) e[kDWord] = __float_as_uint(D);
+          if constexpr (TERM) e[4] = tbin;
           active = false;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -917,6 +927,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
               cr = __uint_as_float(e[3]); cg = __uint_as_float(e[4]); cb = __uint_as_float(e[5]);
             }
             if constexpr (DSTATE) D = __uint_as_float(e[kDWord]);
+            if constexpr (TERM) tbin = e[4];
             take_ray(ri, e[1]);
           }
         }
@@ -951,6 +962,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
               e[5] = __float_as_uint(cb);
             }
             if constexpr (DSTATE) e[kDWord] = __float_as_uint(D);
+            if constexpr (TERM) e[4] = tbin;
             active = false;
           }
           if (fits && lane == 0) *(volatile uint32_t*)&pool_n = at + n_g;
@@ -990,6 +1002,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
               cr = __uint_as_float(ent[3]); cg = __uint_as_float(ent[4]); cb = __uint_as_float(ent[5]);
             }
             if constexpr (DSTATE) D = __uint_as_float(ent[kDWord]);
+            if constexpr (TERM) tbin = ent[4];
             take_ray(ent[0], ent[1]);
           }
         }
@@ -1028,6 +1041,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
             T = 1.f; cr = 0.f; cg = 0.f; cb = 0.f;
             if constexpr (DSTATE) D = 0.f;
             if constexpr (ENTROPY) Hs = 0.f;
+            if constexpr (TERM) tbin = 0u; // (a first sample in a later bin stores bin 0's empty sum: the 0 the plane holds)
             take_ray(q_cur + (uint32_t)r, 0u);
           }
         }
@@ -1052,6 +1066,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
     for (int s = 0; s < 4; s++) asm volatile("" : "=v"(f[s]));
     bool last = false;
     float ts = 0.f; // DSTATE: the sample's ray parameter, kept across the MLP
+    uint32_t sbin = 0u; // TERM: the sample's bin, kept across the MLP
     if (active) {
       const uint32_t i = base + (uint32_t)__builtin_ctz(cur);
       cur &= cur - 1u;
@@ -1067,6 +1082,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
       }
       const float t = fmaf((float)i + 0.5f, dt, t0);
       if constexpr (DSTATE) ts = t;
+      if constexpr (TERM) sbin = min((i * X->bin_mul) >> 16, X->n_bins - 1u); // (the min changes no bin of a ray within n_max steps: it keeps any other inside the planes)
       encode_sample<F, NDENSE, CACHE>(P.field.table, lvl, hc, fmaf(t, d[0], o[0]), fmaf(t, d[1], o[1]), fmaf(t, d[2], o[2]), f, cc);
     }
     // f[2s] | f[2s+1] = k rows [16s, 16s+8) | [16s+8, 16s+16) of the lane's own sample -> B operands of the two groups
@@ -1091,7 +1107,14 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
       const float sigma = fast_exp(dens + P.field.density_bias);
       const float alpha = 1.0f - fast_exp(-(sigma * dt));
       const float wgt = alpha * T;
-      if constexpr (ENTROPY) {
+      if constexpr (TERM) {
+        if (sbin != tbin) {
+          X->out_bins[(size_t)tbin * X->plane_stride + pix] = Hs;
+          Hs = 0.f;
+          tbin = sbin;
+        }
+        Hs = Hs + wgt;
+      } else if constexpr (ENTROPY) {
         Hs = entropy_add(wgt, Hs);
       } else {
         cr = fmaf(wgt, fast_sigmoid(lr), cr);
@@ -1111,7 +1134,10 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
         reinterpret_cast<float4*>(P.out_f32)[pix] = v;
         if (P.last_pass && P.out_u8) P.out_u8[pix] = quantize_rgba8(v.x, v.y, v.z, v.w, P.bg);
       }
-      if constexpr (ENTROPY) {
+      if constexpr (TERM) {
+        X->out_bins[(size_t)tbin * X->plane_stride + pix] = Hs; // the open bin
+        X->out_alpha[pix] = 1.0f - T;
+      } else if constexpr (ENTROPY) {
         X->out_entropy[pix] = entropy_add(T, Hs); // + h(T_end): the ray escapes with what is left
         X->out_alpha[pix] = 1.0f - T;
       }
@@ -1142,8 +1168,8 @@ void render_queue64_kernel(RenderParams P) {
   render_queue64_body<F, NDENSE, NGP, CACHE, kRenderColour>(P, nullptr);
 }
 
-// prv_render_depth / prv_render_entropy / prv_render_footprint / prv_render_surface: the render that writes scalar planes (render_queue64_body,
-// MODE = kRenderDepth / kRenderEntropy / kRenderFootprint / kRenderSurface), for the (F, NDENSE) set of the colour instances; no corner-cache
+// prv_render_depth / prv_render_entropy / prv_render_footprint / prv_render_surface / prv_render_termination: the render that writes scalar planes (render_queue64_body,
+// MODE = kRenderDepth / kRenderEntropy / kRenderFootprint / kRenderSurface / kRenderTermination), for the (F, NDENSE) set of the colour instances; no corner-cache
 // instance.  Waves per SIMD as the colour instances ask for.  Depth: no spills at either.  Entropy and footprint: without the
 // colour MLP's accumulators, SH rows and colour sums the dense-level instances take 122-130 registers (colour: 160-168; three
 // waves, the F = 2 ones under the engine's rule four), the all-hashed ones 183-218 (two waves), none spills a VGPR
@@ -1151,7 +1177,8 @@ void render_queue64_kernel(RenderParams P) {
 // instances', but for the F = 4 dense-level ones under the fixed rule: asked for three waves they take 134 registers where the
 // footprint twins take 126 (the fourth plane's store; no placement or form of it changes that), so those two are asked for the
 // four waves their twins have, and take 126 with no spill of either kind.  The predicate follows what this compiler does:
-// look at scripts/kernel_resources.py's rows of the surface instances again whenever the compiler changes
+// look at scripts/kernel_resources.py's rows of the surface instances again whenever the compiler changes.  Termination: asked for
+// what the footprint instances are asked for
 template <int F, int NDENSE, bool NGP, int MODE>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(NDENSE == 0 ? 1 : MODE == kRenderSurface && F == 4 && !NGP ? 4 : 3)))
@@ -1471,6 +1498,64 @@ __global__ __launch_bounds__(256) void score_entropy_kernel(const float* __restr
   if (threadIdx.x == 0) {
     partial[((size_t)v * gridDim.x + blockIdx.x) * 2 + 0] = s0;
     partial[((size_t)v * gridDim.x + blockIdx.x) * 2 + 1] = s1;
+  }
+}
+
+// PRV_SCORE_TERMINATION_JSD (prv_termination_divergence): one lane = one pixel of view blockIdx.y over the E members' termination
+// histograms (the termination render's planes; p_e[n_bins] = 1 - alpha_e, what escapes).  All float32, in this order:
+//   m_k = (p_0[k] + ... + p_{E-1}[k]) * (1 / E), members in slot order;  A = sum_k h(m_k), B_e = sum_k h(p_e[k]), k ascending,
+//   h and its FMA the entropy render's (entropy_add);  J = max(A - (B_0 + ... + B_{E-1}) * (1 / E), 0)
+// Two identical members: m_k = (p + p) * 0.5 = p exactly, so A = B_0 = B_1, (B + B) * 0.5 = B and J = 0 exactly.
+// The view's sums of J and of the members' mean opacity: fp64 block partials, summed in block order by score_finalize_kernel
+// (score_entropy_kernel's scheme)
+__global__ __launch_bounds__(256) void score_termination_jsd_kernel(TerminationJsdParams P) {
+  __shared__ double sm[4];
+  const size_t v = blockIdx.y, npix = P.npix;
+  const int E = P.E, K = P.n_bins;
+  const float inv_e = 1.0f / (float)E;
+  double sj = 0.0, sa = 0.0;
+  for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < npix; p += (size_t)gridDim.x * 256) {
+    const size_t at = v * npix + p;
+    float A = 0.f, B[PRV_MAX_MODELS];
+#pragma unroll
+    for (int e = 0; e < PRV_MAX_MODELS; e++) B[e] = 0.f;
+    for (int k = 0; k < K; k++) {
+      float m = 0.f;
+#pragma unroll
+      for (int e = 0; e < PRV_MAX_MODELS; e++) {
+        if (e < E) {
+          const float q = P.bins[e][(size_t)k * P.plane_stride + at];
+          m = e == 0 ? q : m + q;
+          B[e] = entropy_add(q, B[e]);
+        }
+      }
+      A = entropy_add(m * inv_e, A);
+    }
+    float m = 0.f, asum = 0.f;
+#pragma unroll
+    for (int e = 0; e < PRV_MAX_MODELS; e++) {
+      if (e < E) {
+        const float a = P.alpha[e][at], q = 1.0f - a;
+        m = e == 0 ? q : m + q;
+        asum = e == 0 ? a : asum + a;
+        B[e] = entropy_add(q, B[e]);
+      }
+    }
+    A = entropy_add(m * inv_e, A);
+    float bs = B[0];
+#pragma unroll
+    for (int e = 1; e < PRV_MAX_MODELS; e++)
+      if (e < E) bs = bs + B[e];
+    const float J = fmaxf(A - bs * inv_e, 0.f);
+    if (P.out_jsd) P.out_jsd[at] = J;
+    sj += (double)J;
+    sa += (double)(asum * inv_e);
+  }
+  const double s0 = block_reduce_sum(sj, sm);
+  const double s1 = block_reduce_sum(sa, sm);
+  if (threadIdx.x == 0) {
+    P.partial[(v * gridDim.x + blockIdx.x) * 2 + 0] = s0;
+    P.partial[(v * gridDim.x + blockIdx.x) * 2 + 1] = s1;
   }
 }
 
@@ -1884,6 +1969,7 @@ hipError_t launch_render_planes(const RenderPlanesParams& P, int mode, int n_blo
   else if (mode == kRenderEntropy) launch_render_planes_mode<kRenderEntropy>(P, n_blocks, s);
   else if (mode == kRenderFootprint) launch_render_planes_mode<kRenderFootprint>(P, n_blocks, s);
   else if (mode == kRenderSurface) launch_render_planes_mode<kRenderSurface>(P, n_blocks, s);
+  else if (mode == kRenderTermination) launch_render_planes_mode<kRenderTermination>(P, n_blocks, s);
   else return hipErrorInvalidValue;
   return hipGetLastError();
 }
@@ -1891,6 +1977,11 @@ hipError_t launch_render_planes(const RenderPlanesParams& P, int mode, int n_blo
 hipError_t launch_score_entropy(const float* entropy, const float* alpha, size_t npix, int n_views, int n_blocks, double* partial,
                                 hipStream_t s) {
   hipLaunchKernelGGL(score_entropy_kernel, dim3((unsigned)n_blocks, (unsigned)n_views), dim3(256), 0, s, entropy, alpha, npix, partial);
+  return hipGetLastError();
+}
+
+hipError_t launch_score_termination_jsd(const TerminationJsdParams& P, int n_views, int n_blocks, hipStream_t s) {
+  hipLaunchKernelGGL(score_termination_jsd_kernel, dim3((unsigned)n_blocks, (unsigned)n_views), dim3(256), 0, s, P);
   return hipGetLastError();
 }
 

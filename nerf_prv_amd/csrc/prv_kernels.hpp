@@ -107,7 +107,7 @@ struct RenderParams {
 };
 
 // what a launch renders: the colour image, or scalar planes (render_planes_kernel's MODE)
-enum : int { kRenderColour = 0, kRenderDepth = 1, kRenderEntropy = 2, kRenderFootprint = 3, kRenderSurface = 4 };
+enum : int { kRenderColour = 0, kRenderDepth = 1, kRenderEntropy = 2, kRenderFootprint = 3, kRenderSurface = 4, kRenderTermination = 5 };
 
 // the plane-writing renders (render_planes_kernel): the colour launch's parameters, untouched, plus one float per pixel of
 // the launch's images (r.out_f32 / 4) per plane.  A plane starts zeroed, which is what a dead ray contributes.
@@ -116,6 +116,8 @@ enum : int { kRenderColour = 0, kRenderDepth = 1, kRenderEntropy = 2, kRenderFoo
 //   kRenderFootprint (prv_render_footprint): all three planes from one density-only launch; r.out_f32 / out_u8 are not touched
 //   kRenderSurface (prv_render_surface):     out_entropy and out_alpha as kRenderEntropy; out_depth = the premultiplied z-depth of the first
 //                                            sample after which T <= T_cross, out_hit = 1 where there is one; r.out_f32 / out_u8 are not touched
+//   kRenderTermination (prv_render_termination): out_bins (n_bins planes, plane_stride floats apart: the ray's compositing weights by
+//                                            depth bin) and out_alpha as kRenderEntropy; r.out_f32 / out_u8 are not touched
 struct RenderPlanesParams {
   RenderParams r;
   float* out_depth; // premultiplied z-depth, engine units           (null where the mode does not write the plane)
@@ -131,6 +133,11 @@ struct RenderPlanesParams {
   // the surface mode's own come behind everything the older instances read, so their argument offsets stay what they were
   float T_cross;  // the ray is located at its first sample after which T <= T_cross (the host: 1.0f - level)
   float* out_hit; // 1.0 where the ray got there, else 0.0
+  // the termination mode's own, behind those again
+  float* out_bins;     // plane k = the weights of the samples in depth bin k, at out_bins + k * plane_stride
+  size_t plane_stride; // floats between two bin planes: the pixels of the buffer the launch writes (its images x W x H, or the caller's planes)
+  uint32_t bin_mul;    // sample i falls in bin (i * bin_mul) >> 16: floor(n_bins * 65536 / n_max), n_max = the rule's step limit
+  uint32_t n_bins;     // a power of two in [4, 64]
 };
 
 struct EnsembleParams {
@@ -160,10 +167,20 @@ hipError_t launch_march(const MarchParams& P, int n_views, int n_spp, hipStream_
 hipError_t launch_spp_reduce(const float* stage, size_t n_pixels, int spp, const float bg[4], float* out, uint32_t* out_u8,
                              hipStream_t s);
 hipError_t launch_render(const RenderParams& P, int n_blocks, hipStream_t s);
-hipError_t launch_render_planes(const RenderPlanesParams& P, int mode, int n_blocks, hipStream_t s); // mode: kRenderDepth / Entropy / Footprint / Surface
+hipError_t launch_render_planes(const RenderPlanesParams& P, int mode, int n_blocks, hipStream_t s); // mode: kRenderDepth / Entropy / Footprint / Surface / Termination
 hipError_t launch_spp_reduce_depth(const float* stage, size_t n_pixels, int spp, float* out, hipStream_t s);
 hipError_t launch_score_entropy(const float* entropy, const float* alpha, size_t npix, int n_views, int n_blocks, double* partial,
                                 hipStream_t s);
+// PRV_SCORE_TERMINATION_JSD / prv_termination_divergence: the Jensen-Shannon divergence of E members' termination histograms, per pixel
+struct TerminationJsdParams {
+  const float* bins[PRV_MAX_MODELS];  // member e: n_bins planes, plane_stride floats apart, of n_views * npix floats
+  const float* alpha[PRV_MAX_MODELS]; // member e: n_views * npix floats
+  int E, n_bins;
+  size_t npix, plane_stride;
+  float* out_jsd;  // n_views * npix floats, or null
+  double* partial; // [view][block][2]: the block's sums of J and of the members' mean opacity
+};
+hipError_t launch_score_termination_jsd(const TerminationJsdParams& P, int n_views, int n_blocks, hipStream_t s);
 // compiled instances of the field-evaluating kernels (render, planes, mesh, field hook): NDENSE = the field's count of leading dense levels when an
 // instance for exactly that count exists (5 / 3 for F = 4, 10 / 6 for F = 2: api.FIELD_256 / FIELD_512 run <4,5> / <2,10>) and its hashed levels share their hash
 // constants; any other field -- util.SMALL (4 dense), SMALL_F2 (9), instant-ngp's base.json (F = 2, 5 dense), levels > 16 MiB -- runs <F, 0> (tests/instances.py)

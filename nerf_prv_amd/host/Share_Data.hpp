@@ -17,8 +17,10 @@
 namespace prvhost {
 
 // method_of_IG values (Share_Data.hpp:198-202) + the single-model scores of this build: 5 (against reference images) and
-// 7 (ray entropy: no ground truth; 6 is unassigned)
-enum { RandomIterative = 0, RandomOneshot = 1, EnsembleRGB = 2, EnsembleRGBDensity = 3, PVBCoverage = 4, PSNRCoverage = 5, RayEntropy = 7 };
+// 7 (ray entropy: no ground truth; 6 is unassigned), and its ensemble score 9 (the Jensen-Shannon divergence between the members'
+// ray-termination histograms: no colour, no ground truth; 8 is unassigned)
+enum { RandomIterative = 0, RandomOneshot = 1, EnsembleRGB = 2, EnsembleRGBDensity = 3, PVBCoverage = 4, PSNRCoverage = 5, RayEntropy = 7,
+       EnsembleTermination = 9 };
 
 struct rs2_intrinsics { // Share_Data.hpp:79-89 (float fields, like librealsense)
   int width = 0, height = 0;
@@ -222,7 +224,7 @@ public:
     save_path += name_of_pcd;
     if (test_method != -1) save_path += "_m" + std::to_string(method_of_IG);
     if (method_of_IG == 2) ensemble_num = 2;      // the paper's values (Share_Data.hpp:505-510)
-    else if (method_of_IG == 3) ensemble_num = 5;
+    else if (method_of_IG == 3 || method_of_IG == EnsembleTermination) ensemble_num = 5; // (9: method 3's ensemble)
     // view set: <viewspace_path><num_of_views>.txt, N rows of 3 numbers (Share_Data.hpp:517-528)
     if (num_of_views > 0) {
       std::ifstream fin_sphere(viewspace_path + std::to_string(num_of_views) + ".txt");

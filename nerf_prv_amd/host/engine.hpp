@@ -31,7 +31,7 @@ inline int configured_train_steps(const FileStorage& fs, const Share_Data& sd) {
 
 // every yaml key the shell and its engine read beyond Share_Data's own, read once
 struct EngineConfig {
-  int n_members = 1;        // methods 2 and 3: Share_Data's ensemble_num; every other method scores one field
+  int n_members = 1;        // methods 2, 3 and 9: Share_Data's ensemble_num; every other method scores one field
   prv_field_desc field{};   // field_* / synthetic_table_amp: the members that are loaded or synthesised, the ground truth, the reference
   double object_size = 0.1; // synthetic objects sit at the origin (+1e-10, main.cpp:447) with the configured size
   bool synthetic = false;   // synthetic_seed: member e = seed + e, method 5's reference field = seed + 4096
@@ -82,7 +82,7 @@ inline EngineConfig engine_config(const FileStorage& fs, const Share_Data& sd, i
   EngineConfig c;
   auto num = [&](const char* k, double dflt) { return fs.has(k) ? fs.num(k) : dflt; };
   auto on = [&](const char* k) { return fs.has(k) && fs.num(k) > 0; };
-  c.n_members = (method == EnsembleRGB || method == EnsembleRGBDensity) ? sd.ensemble_num : 1;
+  c.n_members = (method == EnsembleRGB || method == EnsembleRGBDensity || method == EnsembleTermination) ? sd.ensemble_num : 1;
   c.field.n_levels = (int)num("field_levels", 8);
   c.field.n_features = (int)num("field_features", 4);
   c.field.log2_hashmap = (int)num("field_log2_hashmap", 19);
@@ -673,7 +673,7 @@ struct PlannerEngine {
       }
       o.background[3] = 0.f;
       rc = prv_score_views_sharded(ctx, comm, PRV_SCORE_PSNR_COVERAGE, slots.data(), 1, cams.get(), n, 1, &o, gt_sel.get(), rec.data(), nullptr);
-    } else { // the ensembles, and RayEntropy (= PRV_SCORE_RAY_ENTROPY): one member, no reference images
+    } else { // the ensembles (EnsembleTermination = PRV_SCORE_TERMINATION_JSD among them), and RayEntropy (= PRV_SCORE_RAY_ENTROPY): one member, no reference images
       rc = prv_score_views_sharded(ctx, comm, method, slots.data(), n_members, cams.get(), n, 1, &o, nullptr, rec.data(), nullptr);
       if (rc == PRV_OK && cfg.save_renders) { // <save_path>/render/<it>/ensemble_<e>/rgbaClip_<view id>.png, the files :2047 reads
         DeviceArray<uint8_t> dev;

@@ -92,7 +92,7 @@ private:
 int PlanningJob::read_config(const std::string& cfg, const std::string& name, int method, prv_comm* comm, bool lockstep, EngineConfig* config) {
   if (!NBV_Net_Labeler::method_in_scope(method)) { // before any directory, model or training: methods 1 / 4 are the PRVNet pipeline's
     std::cerr << "method_of_IG " << method << " is not built: this planner runs methods 0 (RandomIterative), 2 (EnsembleRGB), 3 "
-                 "(EnsembleRGBDensity), 5 (PSNRCoverage) and 7 (RayEntropy); 1 (RandomOneshot) and 4 (PVBCoverage) need the reference's PRVNet server" << std::endl;
+                 "(EnsembleRGBDensity), 5 (PSNRCoverage) and 7 (RayEntropy), plus 9 (EnsembleTermination); 1 (RandomOneshot) and 4 (PVBCoverage) need the reference's PRVNet server" << std::endl;
     return -10;
   }
   sd = std::make_shared<Share_Data>(cfg, name, -1, -1, method); // main.cpp:3876
@@ -105,6 +105,10 @@ int PlanningJob::read_config(const std::string& cfg, const std::string& name, in
     std::cerr << "views_per_iteration " << sd->views_per_iteration << " needs method_of_IG 7 (RayEntropy), score_path: fused and one rank "
                  "(the selection stage is single-rank); nothing was written" << std::endl;
     return -14;
+  }
+  if (!NBV_Net_Labeler::score_path_in_scope(method, sd->score_from_pngs)) { // before anything is written
+    std::cerr << "method_of_IG 9 (EnsembleTermination) needs score_path: fused, not score_path: png; nothing was written" << std::endl;
+    return -16;
   }
   if (rank > 0) sd->relocate_outputs(sd->pre_path + "rank" + std::to_string(rank) + "/"); // same loop, own scratch tree
   FileStorage fs;
@@ -250,7 +254,7 @@ int run_members_lockstep(prv_ctx* ctx, const std::string& cfg, const std::vector
       int members = 1;
       {
         Share_Data probe(cfg, names[b0 + k], -1, -1, method);
-        if (probe.ok && (method == EnsembleRGB || method == EnsembleRGBDensity)) members = probe.ensemble_num;
+        if (probe.ok && (method == EnsembleRGB || method == EnsembleRGBDensity || method == EnsembleTermination)) members = probe.ensemble_num;
       }
       int rc = j.setup(ctx, cfg, names[b0 + k], method, comm, 8 + (int)k * PRV_MAX_MODELS, (int)(b0 + k) * members);
       if (rc == 0) rc = j.lab->nbv_begin(j.first_view_id, 0);

@@ -286,8 +286,13 @@ public:
   // Methods 1 (RandomOneshot, main.cpp:1981-2037) and 4 (PVBCoverage, :2163-2242: PRVNet's view budget) never render and
   // are outside this build's scope: refused BEFORE the loop writes anything, with a message.
   static bool method_in_scope(int method) {
-    return method == RandomIterative || method == EnsembleRGB || method == EnsembleRGBDensity || method == PSNRCoverage || method == RayEntropy;
+    return method == RandomIterative || method == EnsembleRGB || method == EnsembleRGBDensity || method == PSNRCoverage || method == RayEntropy ||
+           method == EnsembleTermination;
   }
+
+  // EnsembleTermination is a device reduction over planes that never leave the GPU: it has no PNG form, so unlike the single-model
+  // scores (which ignore `score_path: png`) it REFUSES it, before the loop writes anything
+  static bool score_path_in_scope(int method, bool score_from_pngs) { return method != EnsembleTermination || !score_from_pngs; }
 
   // `views_per_iteration: k > 1` rests on the footprint render of the single-model entropy score: RayEntropy on the fused path
   // only.  Anything else is refused BEFORE the loop writes anything, as method_in_scope refuses.
@@ -322,7 +327,7 @@ public:
     if (first_view_id == -1) first_view_id = 0; // :1725-1728
     Share_Data& sd = *share_data;
     if (!method_in_scope(sd.method_of_IG)) {
-      std::cerr << "nbv_loop: method_of_IG " << sd.method_of_IG << " is not built: the loop runs 0, 2, 3, 5 (PSNRCoverage) and 7 (RayEntropy); "
+      std::cerr << "nbv_loop: method_of_IG " << sd.method_of_IG << " is not built: the loop runs 0, 2, 3, 5 (PSNRCoverage), 7 (RayEntropy) and 9 (EnsembleTermination); "
                    "RandomOneshot = 1 and PVBCoverage = 4 belong to the reference's PRVNet pipeline, outside this build's scope; "
                    "nothing was written" << std::endl;
       return -10;
@@ -331,6 +336,10 @@ public:
       std::cerr << "nbv_loop: views_per_iteration " << sd.views_per_iteration << " needs method_of_IG 7 (RayEntropy) and score_path: fused, not method "
                 << sd.method_of_IG << (sd.score_from_pngs ? " with score_path: png" : "") << "; nothing was written" << std::endl;
       return -14;
+    }
+    if (!score_path_in_scope(sd.method_of_IG, sd.score_from_pngs)) {
+      std::cerr << "nbv_loop: method_of_IG 9 (EnsembleTermination) needs score_path: fused, not score_path: png; nothing was written" << std::endl;
+      return -16;
     }
     if (sd.views_per_iteration > 1 && !selector) {
       std::cerr << "nbv_loop: views_per_iteration " << sd.views_per_iteration << " needs a selector; nothing was written" << std::endl;
@@ -431,10 +440,11 @@ public:
       case EnsembleRGB:
       case EnsembleRGBDensity:
       case PSNRCoverage:
-      case RayEntropy: { // :2039-2161: score every unchosen view, keep the arg-max
+      case RayEntropy:
+      case EnsembleTermination: { // :2039-2161: score every unchosen view, keep the arg-max
         std::vector<double> scores(candidates.size(), 0.0);
         // (the single-model scores are device reductions with no PNG form: `score_path: png` does not apply to them)
-        if (sd.score_from_pngs && sd.method_of_IG != PSNRCoverage && sd.method_of_IG != RayEntropy) {
+        if (sd.score_from_pngs && sd.method_of_IG != PSNRCoverage && sd.method_of_IG != RayEntropy && sd.method_of_IG != EnsembleTermination) {
           // the reference's data flow, call for call: one engine run per member (:2041-2043, :2101-2103), then the PNGs
           // (no train_time/<it>.txt here: the reference writes it for ensemble_id == -1 only, :1707-1711)
           for (int ensemble_id = 0; ensemble_id < sd.ensemble_num; ensemble_id++) {
