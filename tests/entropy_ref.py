@@ -1,19 +1,16 @@
 """CPU reference of the ray-entropy render (test infrastructure, in the manner of tests/depth_ref.py).
 
-Restates the oracle's march (oracle/prv_oracle.c: march_ray, render_worker) with the entropy sum of prv_render_entropy
-(include/prv.h), through the oracle's exported primitives only (orc_spp_offset, orc_raygen, orc_ray_aabb, orc_occupied,
-orc_eval):
+A fold over tests/march_ref.py's samples, the one restatement of the oracle's march, with the entropy sum of
+prv_render_entropy (include/prv.h):
   * w_i = alpha_i T_i over exactly the samples, weights and early termination of the colour composite;
   * H = sum_i h(w_i) + h(T_end), h(p) = p >= 2^-126 ? -p log2(p) : 0, accumulated in depth order as H = fmaf(p, -log2 p, H),
     the escape term last; a ray that misses the box or has no live sample gives 0;
   * per pixel the sub-samples summed in order, then scaled by 1 / spp.
-fmaf is computed in float64 and rounded to float32; log2 is numpy's float32 one; everything else is float32 arithmetic.
+log2 is numpy's float32 one.
 """
-import ctypes as C
-
 import numpy as np
 
-from tests.depth_ref import NGP_DT, _p, f32, fmaf, strided  # noqa: F401  (strided: re-exported for the tests)
+from tests.march_ref import assert_alpha_is_the_oracles, composite, f32, fmaf, mean, ray_samples, rays
 
 FLT_MIN = f32(2.0 ** -126)
 
@@ -39,70 +36,28 @@ def entropy_of_alphas(alphas, min_T=0.0):
 
 
 def march_ray(lib, field, o, d, step_mode, S, min_T):
-    """-> (r, g, b, a, H) of one ray: the oracle's march_ray plus the entropy sum"""
-    t0, t1 = C.c_float(), C.c_float()
-    if not lib.orc_ray_aabb(_p(o), _p(d), C.byref(t0), C.byref(t1)):
-        return np.zeros(5, np.float32)
-    t0, t1 = f32(t0.value), f32(t1.value)
-    if step_mode == 1:
-        dt, n = NGP_DT, 1024
-    else:
-        dt, n = f32((t1 - t0) / f32(S)), S
-    T, r, g, b, H = f32(1), f32(0), f32(0), f32(0), f32(0)
-    p = np.zeros(3, np.float32)
-    rgb = np.zeros(3, np.float32)
-    raw = np.zeros(32, np.float32)
-    sigma = C.c_float()
-    for i in range(n):
-        t = fmaf(f32(i) + f32(0.5), dt, t0)
-        if step_mode == 1 and not t < t1:
-            break
-        p[:] = (fmaf(t, d[0], o[0]), fmaf(t, d[1], o[1]), fmaf(t, d[2], o[2]))
-        if not lib.orc_occupied(field.ptr, _p(p)):
-            continue
-        lib.orc_eval(field.ptr, _p(p), _p(d), C.byref(sigma), _p(rgb), _p(raw))
-        alpha = f32(1) - f32(np.exp(-f32(f32(sigma.value) * dt)))
-        wgt = f32(alpha * T)
-        r, g, b = fmaf(wgt, rgb[0], r), fmaf(wgt, rgb[1], g), fmaf(wgt, rgb[2], b)
-        H = h_add(wgt, H)
-        T = f32(T * (f32(1) - alpha))
-        if T < min_T:
-            break
+    """-> (r, g, b, a, H) of one ray: the colour composite plus the entropy sum"""
+    _, _, alphas, rgbs, _ = ray_samples(lib, field, o, d, step_mode, S, min_T)
+    (r, g, b), T = composite(alphas, rgbs, 3)
     if T == f32(1):  # no live sample: exactly 0 (h(1) = 0 anyway)
         return np.array([r, g, b, f32(0), f32(0)], np.float32)
-    return np.array([r, g, b, f32(1) - T, h_add(T, H)], np.float32)
+    H, T = entropy_of_alphas(alphas, min_T)
+    return np.array([r, g, b, f32(1) - T, H], np.float32)
 
 
 def render(lib, field, cam, w, h, S=128, spp=1, min_T=1e-4, step_mode=0, pixel_stride=1):
     """-> (h, w, 5) float32: r, g, b, alpha (as OracleField.render) and H (bits).
-    pixel_stride n > 1: only the pixels whose row-major index is a multiple of n are computed (`strided` picks the same
-    ones out of an image); the others stay 0."""
-    out = np.zeros((h, w, 5), np.float32)
-    min_T = f32(min_T)
-    o, d = np.zeros(3, np.float32), np.zeros(3, np.float32)
-    ox, oy = C.c_float(), C.c_float()
-    inv_spp = f32(1) / f32(spp)
-    offs = []
-    for k in range(spp):
-        lib.orc_spp_offset(k, C.byref(ox), C.byref(oy))
-        offs.append((ox.value, oy.value))
-    for y in range(h):
-        for x in range(w):
-            if (y * w + x) % pixel_stride:
-                continue
-            acc = np.zeros(5, np.float32)
-            for k in range(spp):
-                lib.orc_raygen(C.byref(cam), x, y, C.c_float(offs[k][0]), C.c_float(offs[k][1]), _p(o), _p(d))
-                acc = (acc + march_ray(lib, field, o, d, step_mode, S, min_T)).astype(np.float32)
-            out[y, x] = (acc * inv_spp).astype(np.float32)
-    return out
+    pixel_stride n > 1: only the pixels whose row-major index is a multiple of n are computed (`march_ref.strided` picks the
+    same ones out of an image); the others stay 0."""
+    sub = np.zeros((spp, h, w, 5), np.float32)
+    for k, y, x, o, d in rays(lib, cam, w, h, spp, pixel_stride):
+        sub[k, y, x] = march_ray(lib, field, o, d, step_mode, S, f32(min_T))
+    return mean(sub)
 
 
 def reference(oracle, f, ocam, w, h, S, spp, min_T, mode, pixel_stride=1):
     want = render(oracle.lib(), f, ocam, w, h, S, spp, min_T, mode, pixel_stride)
-    # self-check: the restatement's colour and alpha are the oracle's own render
-    img, _ = f.render(ocam, w, h, S, spp, min_T, step_mode=mode)
-    assert np.abs(strided(want, pixel_stride)[:, :4] - strided(img, pixel_stride)).max() <= 1e-6
+    assert_alpha_is_the_oracles(f, ocam, w, h, S, spp, min_T, mode, want[..., :4], pixel_stride)  # its colour too
     return want
 
 

@@ -2,12 +2,12 @@
 
 Restates the contract of prv_select_from_images (include/prv.h) in numpy float32, operation by operation: the gain word, the
 point a pixel's expected depth names, its voxel, and the greedy rounds in exact integers.  Rays come from
-Context.debug_raygen, the forward cosine from depth_ref.forward_cos, whose FMAs are depth_ref.fmaf; nothing here is shared
+Context.debug_raygen, the forward cosine from march_ref.forward_cos, whose FMAs are march_ref.fmaf; nothing here is shared
 with prv_select.hip.
 """
 import numpy as np
 
-from tests import depth_ref
+from tests import march_ref
 
 f32 = np.float32
 UNLOCATED = 0xFFFFFFFF
@@ -15,7 +15,7 @@ Q_CAP = f32(4294967040.0)  # the largest float32 below 2^32
 
 
 class _Cam:
-    """what depth_ref.forward_cos reads of a camera: c2w, 12 float32, row-major 3x4"""
+    """what march_ref.forward_cos reads of a camera: c2w, 12 float32, row-major 3x4"""
 
     def __init__(self, c2w):
         self.c2w = np.ascontiguousarray(c2w, np.float32).reshape(12)
@@ -54,7 +54,7 @@ def footprint(ctx, camset, view, w, h, H, alpha, z, G, alpha_min):
     """(h, w) planes of one view -> (voxel, q), (h, w) uint32 each"""
     o, d, _ = ctx.debug_raygen(camset, int(view), w, h, 0)
     c2w, _ = camset.get(int(view))
-    cos = depth_ref.forward_cos(_Cam(c2w), d.T)
+    cos = march_ref.forward_cos(_Cam(c2w), d.T)
     vox = voxels_from_rays(o, d, cos, np.asarray(alpha).ravel(), np.asarray(z).ravel(), G, alpha_min)
     return vox.reshape(h, w), gain_words(H).reshape(h, w)
 

@@ -1,21 +1,19 @@
 """CPU reference of the surface render (test infrastructure, in the manner of tests/entropy_ref.py).
 
-Restates the oracle's march (oracle/prv_oracle.c: march_ray, render_worker) with the first-crossing locator of
-prv_render_surface (include/prv.h), through the oracle's exported primitives only:
-  * the ray's live samples (t_i, alpha_i), walked and cut as tests/entropy_ref.py's march_ray walks and cuts them;
+A fold over tests/march_ref.py's samples, the one restatement of the oracle's march, with the first-crossing locator of
+prv_render_surface (include/prv.h):
+  * the ray's live samples (t_i, alpha_i) are march_ref.ray_samples';
   * H and 1 - T_end of those opacities by entropy_ref.entropy_of_alphas;
   * Dm = t_i of the first sample after which T = T * (1 - alpha_i) is <= T_cross, or 0; hit = Dm > 0;
-  * per sub-sample z = Dm * dot(d, f) with tests/depth_ref.py's cosine;
-  * per pixel the sub-samples summed in order, then scaled by 1 / spp.
+  * per sub-sample z = Dm * dot(d, f) with march_ref.forward_cos;
+  * per pixel the sub-samples summed in order, then scaled by 1 / spp (march_ref.mean).
 A GPU ray's T differs from this one's by rounding (exp2 / rcp, MFMA order), so a ray whose T lands on T_cross may cross one
 sample apart: `bounds` renders at T_cross * {1, 1 + s, 1 - s}, s = util.TERMINATION_SLACK, in one march.
 """
-import ctypes as C
-
 import numpy as np
 
 from tests import entropy_ref, util
-from tests.depth_ref import NGP_DT, _p, f32, fmaf, forward_cos
+from tests.march_ref import assert_alpha_is_the_oracles, f32, fmaf, forward_cos, mean, ray_samples, rays
 
 
 def surface_of_alphas(alphas, ts, level, min_T=0.0):
@@ -38,75 +36,27 @@ def _cross(alphas, ts, T_cross, min_T):
     return [(d, f32(1) if d > 0 else f32(0)) for d in Dm]
 
 
-def ray_samples(lib, field, o, d, step_mode, S, min_T):
-    """-> (ts, alphas, dt): the live samples entropy_ref.march_ray composites, up to and including the one that cuts the ray"""
-    t0, t1 = C.c_float(), C.c_float()
-    if not lib.orc_ray_aabb(_p(o), _p(d), C.byref(t0), C.byref(t1)):
-        return [], [], f32(0)
-    t0, t1 = f32(t0.value), f32(t1.value)
-    if step_mode == 1:
-        dt, n = NGP_DT, 1024
-    else:
-        dt, n = f32((t1 - t0) / f32(S)), S
-    T = f32(1)
-    p = np.zeros(3, np.float32)
-    rgb = np.zeros(3, np.float32)
-    raw = np.zeros(32, np.float32)
-    sigma = C.c_float()
-    ts, alphas = [], []
-    for i in range(n):
-        t = fmaf(f32(i) + f32(0.5), dt, t0)
-        if step_mode == 1 and not t < t1:
-            break
-        p[:] = (fmaf(t, d[0], o[0]), fmaf(t, d[1], o[1]), fmaf(t, d[2], o[2]))
-        if not lib.orc_occupied(field.ptr, _p(p)):
-            continue
-        lib.orc_eval(field.ptr, _p(p), _p(d), C.byref(sigma), _p(rgb), _p(raw))
-        alpha = f32(1) - f32(np.exp(-f32(f32(sigma.value) * dt)))
-        ts.append(t)
-        alphas.append(alpha)
-        T = f32(T * (f32(1) - alpha))
-        if T < min_T:
-            break
-    return ts, alphas, dt
-
-
 def render_variants(lib, field, cam, w, h, T_cross, S=128, spp=1, min_T=1e-4, step_mode=0):
     """-> (spp, h, w, 2 + 2 n) float32 per SUB-SAMPLE: alpha, H, then (z, hit) for each of the n thresholds of T_cross"""
-    n = len(T_cross)
-    out = np.zeros((spp, h, w, 2 + 2 * n), np.float32)
+    out = np.zeros((spp, h, w, 2 + 2 * len(T_cross)), np.float32)
     min_T = f32(min_T)
-    o, d = np.zeros(3, np.float32), np.zeros(3, np.float32)
-    ox, oy = C.c_float(), C.c_float()
-    for k in range(spp):
-        lib.orc_spp_offset(k, C.byref(ox), C.byref(oy))
-        for y in range(h):
-            for x in range(w):
-                lib.orc_raygen(C.byref(cam), x, y, C.c_float(ox.value), C.c_float(oy.value), _p(o), _p(d))
-                ts, alphas, _ = ray_samples(lib, field, o, d, step_mode, S, min_T)
-                if not ts:
-                    continue
-                H, T = entropy_ref.entropy_of_alphas(alphas, min_T)
-                cos = forward_cos(cam, d)
-                px = [f32(1) - T, H]
-                for Dm, hit in _cross(alphas, ts, T_cross, min_T):
-                    px += [f32(Dm * cos), hit]
-                out[k, y, x] = px
+    for k, y, x, o, d in rays(lib, cam, w, h, spp):
+        _, ts, alphas, _, _ = ray_samples(lib, field, o, d, step_mode, S, min_T)
+        if not ts:
+            continue
+        H, T = entropy_ref.entropy_of_alphas(alphas, min_T)
+        cos = forward_cos(cam, d)
+        px = [f32(1) - T, H]
+        for Dm, hit in _cross(alphas, ts, T_cross, min_T):
+            px += [f32(Dm * cos), hit]
+        out[k, y, x] = px
     return out
-
-
-def _mean(sub):
-    """(spp, ...) -> the pixel: its sub-samples summed in order, then scaled by 1 / spp"""
-    acc = np.zeros(sub.shape[1:], np.float32)
-    for k in range(sub.shape[0]):
-        acc = (acc + sub[k]).astype(np.float32)
-    return (acc * (f32(1) / f32(sub.shape[0]))).astype(np.float32)
 
 
 def render(lib, field, cam, w, h, T_cross, S=128, spp=1, min_T=1e-4, step_mode=0):
     """-> (h, w, 4) float32 per pixel: H, alpha, z, hit for the threshold T_cross"""
     sub = render_variants(lib, field, cam, w, h, [T_cross], S, spp, min_T, step_mode)
-    return _mean(sub[..., [1, 0, 2, 3]])
+    return mean(sub[..., [1, 0, 2, 3]])
 
 
 class Bounds:
@@ -115,11 +65,11 @@ class Bounds:
 
     def __init__(self, sub):
         z, hit = sub[..., 2::2], sub[..., 3::2]  # (spp, h, w, 3)
-        self.z_lo, self.z_hi = _mean(z.min(axis=-1)), _mean(z.max(axis=-1))
-        self.hit_lo, self.hit_hi = _mean(hit.min(axis=-1)), _mean(hit.max(axis=-1))
-        self.z_var = np.stack([_mean(z[..., j]) for j in range(3)])
-        self.hit_var = np.stack([_mean(hit[..., j]) for j in range(3)])
-        self.alpha = _mean(sub[..., 0])
+        self.z_lo, self.z_hi = mean(z.min(axis=-1)), mean(z.max(axis=-1))
+        self.hit_lo, self.hit_hi = mean(hit.min(axis=-1)), mean(hit.max(axis=-1))
+        self.z_var = np.stack([mean(z[..., j]) for j in range(3)])
+        self.hit_var = np.stack([mean(hit[..., j]) for j in range(3)])
+        self.alpha = mean(sub[..., 0])
 
     @property
     def hit_pixels(self):
@@ -135,9 +85,7 @@ def bounds(oracle, f, ocam, w, h, S, spp, min_T, mode, level):
     T_cross = f32(1) - f32(level)
     sub = render_variants(oracle.lib(), f, ocam, w, h, [f32(v) for v in util.termination_variants(T_cross)], S, spp, min_T, mode)
     b = Bounds(sub)
-    # self-check: the restatement's alpha is the oracle's own render
-    img, _ = f.render(ocam, w, h, S, spp, min_T, step_mode=mode)
-    assert np.abs(b.alpha - img[..., 3]).max() <= 1e-6
+    assert_alpha_is_the_oracles(f, ocam, w, h, S, spp, min_T, mode, b.alpha)
     return b
 
 
@@ -188,8 +136,7 @@ def case_bounds(oracle, f, ocams, mode, level, min_T):
         sub = render_variants(oracle.lib(), f, oc, FW, FH, tc, S, 3, min_T, mode)
         for spp in SPP:
             b = Bounds(sub[:spp])
-            img, _ = f.render(oc, FW, FH, S, spp, min_T, step_mode=mode)  # self-check: the restatement's alpha is the oracle's
-            assert np.abs(b.alpha - img[..., 3]).max() <= 1e-6
+            assert_alpha_is_the_oracles(f, oc, FW, FH, S, spp, min_T, mode, b.alpha)
             out[spp].append(b)
     return out
 
@@ -220,21 +167,16 @@ def shell_rays(lib, field, cam, w, h, S, min_T, T_cross):
     out = {k: np.zeros((h, w), np.float32) for k in ("w1", "t_gap0", "t_gap1", "dt", "cos")}
     out["t_cross"] = np.zeros((len(T_cross), h, w), np.float32)
     z_mid = (SHELL_CELLS[0][0] + SHELL_CELLS[1][-1] + 1) / 2.0 / field.desc.occ_res
-    o, d = np.zeros(3, np.float32), np.zeros(3, np.float32)
-    ox, oy = C.c_float(), C.c_float()
-    lib.orc_spp_offset(0, C.byref(ox), C.byref(oy))
-    for y in range(h):
-        for x in range(w):
-            lib.orc_raygen(C.byref(cam), x, y, C.c_float(ox.value), C.c_float(oy.value), _p(o), _p(d))
-            ts, alphas, dt = ray_samples(lib, field, o, d, 0, S, f32(min_T))
-            first = [i for i, t in enumerate(ts) if fmaf(t, d[2], o[2]) > z_mid]
-            if not first or len(first) == len(ts) or first != list(range(len(first))):
-                continue  # the ray does not go through the near shell and then the far one
-            T = f32(1)
-            for a in alphas[: len(first)]:
-                T = f32(T * (f32(1) - a))
-            out["w1"][y, x] = f32(1) - T
-            out["t_gap0"][y, x], out["t_gap1"][y, x] = ts[len(first) - 1], ts[len(first)]
-            out["dt"][y, x], out["cos"][y, x] = dt, forward_cos(cam, d)
-            out["t_cross"][:, y, x] = [Dm for Dm, _ in _cross(alphas, ts, T_cross, min_T)]
+    for _, y, x, o, d in rays(lib, cam, w, h, 1):
+        _, ts, alphas, _, dt = ray_samples(lib, field, o, d, 0, S, f32(min_T))
+        first = [i for i, t in enumerate(ts) if fmaf(t, d[2], o[2]) > z_mid]
+        if not first or len(first) == len(ts) or first != list(range(len(first))):
+            continue  # the ray does not go through the near shell and then the far one
+        T = f32(1)
+        for a in alphas[: len(first)]:
+            T = f32(T * (f32(1) - a))
+        out["w1"][y, x] = f32(1) - T
+        out["t_gap0"][y, x], out["t_gap1"][y, x] = ts[len(first) - 1], ts[len(first)]
+        out["dt"][y, x], out["cos"][y, x] = dt, forward_cos(cam, d)
+        out["t_cross"][:, y, x] = [Dm for Dm, _ in _cross(alphas, ts, T_cross, min_T)]
     return out

@@ -1,27 +1,24 @@
 """CPU reference of the termination render and of the Jensen-Shannon view score (test infrastructure, in the manner of
 tests/entropy_ref.py and tests/surface_ref.py).
 
-The histogram (prv_render_termination, include/prv.h), through the oracle's exported primitives only:
-  * the ray's live samples (t_i, alpha_i) are surface_ref.ray_samples' -- what entropy_ref.march_ray composites, cut as it cuts;
-  * the step index i of every live sample is carried along: t_i = fmaf(i + 0.5, dt, t0) is recomputed for every step of the
-    ray and matched bit for bit, so i is the index the kernel forms t from, not a division's guess;
+The histogram (prv_render_termination, include/prv.h), a fold over tests/march_ref.py's samples, the one restatement of the
+oracle's march:
+  * the ray's live samples (i, alpha_i) are march_ref.ray_samples': i is the step index t_i = fmaf(i + 0.5, dt, t0) was formed
+    from, the one the kernel forms t from;
   * bin(i) = (i * M) >> 16 in 32-bit unsigned arithmetic, M = floor(K * 65536 / n_max), n_max = S (fixed rule) or 1024;
   * w_i = alpha_i T_i is added to its bin in float32, in depth order; the escape is T_end, alpha = 1 - T_end;
-  * per pixel the sub-samples are summed in order, then scaled by 1 / spp (surface_ref._mean).
+  * per pixel the sub-samples are summed in order, then scaled by 1 / spp (march_ref.mean).
 A GPU ray's T differs from this one's by rounding, so a ray whose T lands on min_T may stop one sample apart: `render_variants`
 walks the thresholds of util.termination_variants(min_T) in one march.
 
 The score (prv_termination_divergence): `jsd` restates J = H(mean of the members) - mean of the members' H in float64 from
 given planes.
 """
-import ctypes as C
-
 import numpy as np
 
-from tests import surface_ref, util
-from tests.depth_ref import NGP_DT, _p, f32
+from tests import util
+from tests.march_ref import NGP_STEPS, assert_alpha_is_the_oracles, f32, mean, ray_samples, rays
 
-NGP_STEPS = 1024
 BINS = (4, 8, 16, 32, 64)
 
 
@@ -37,23 +34,6 @@ def bin_mul(K, nmax):
 def bin_of(i, K, nmax):
     """the sample's bin: 32-bit unsigned multiply, shift"""
     return ((int(i) * bin_mul(K, nmax)) & 0xFFFFFFFF) >> 16
-
-
-def ray_steps(lib, o, d, step_mode, S, ts):
-    """-> the step index of every live sample of surface_ref.ray_samples' ts: each t is matched bit for bit against
-    fmaf(i + 0.5, dt, t0) over the ray's steps"""
-    if not ts:
-        return []
-    t0, t1 = C.c_float(), C.c_float()
-    assert lib.orc_ray_aabb(_p(o), _p(d), C.byref(t0), C.byref(t1))
-    t0, t1 = f32(t0.value), f32(t1.value)
-    dt = NGP_DT if step_mode == 1 else f32((t1 - t0) / f32(S))
-    # fmaf(i + 0.5, dt, t0) of every step at once: the float64 product and sum are exact enough to round as the fused operation
-    # does (depth_ref.fmaf's own form), and t grows with i, so every live t is found by bisection and must match bit for bit
-    t_all = ((np.arange(n_max(step_mode, S), dtype=np.float32) + f32(0.5)).astype(np.float64) * np.float64(dt) + np.float64(t0)).astype(np.float32)
-    steps = np.searchsorted(t_all, np.asarray(ts, np.float32))
-    assert (steps < len(t_all)).all() and np.array_equal(t_all[steps], np.asarray(ts, np.float32))
-    return [int(i) for i in steps]
 
 
 def histogram(steps, alphas, K, nmax, min_T=0.0):
@@ -79,29 +59,15 @@ def render_variants(lib, field, cam, w, h, K, min_Ts, S=128, spp=1, step_mode=0)
     sub = np.zeros((n, spp, h, w, K + 1), np.float32)
     live = np.zeros((spp, h, w, K), bool)
     nmax = n_max(step_mode, S)
-    o, d = np.zeros(3, np.float32), np.zeros(3, np.float32)
-    ox, oy = C.c_float(), C.c_float()
     lo = f32(min(min_Ts))
-    for k in range(spp):
-        lib.orc_spp_offset(k, C.byref(ox), C.byref(oy))
-        for y in range(h):
-            for x in range(w):
-                lib.orc_raygen(C.byref(cam), x, y, C.c_float(ox.value), C.c_float(oy.value), _p(o), _p(d))
-                ts, alphas, _ = surface_ref.ray_samples(lib, field, o, d, step_mode, S, lo)  # the longest of the variants' walks
-                if not ts:
-                    continue
-                steps = ray_steps(lib, o, d, step_mode, S, ts)
-                for j, mt in enumerate(min_Ts):
-                    bins, T, lv = histogram(steps, alphas, K, nmax, mt)
-                    sub[j, k, y, x, :K] = bins
-                    sub[j, k, y, x, K] = f32(1) - T
-                    live[k, y, x] |= lv
+    for k, y, x, o, d in rays(lib, cam, w, h, spp):
+        steps, _, alphas, _, _ = ray_samples(lib, field, o, d, step_mode, S, lo)  # the longest of the variants' walks
+        for j, mt in enumerate(min_Ts):
+            bins, T, lv = histogram(steps, alphas, K, nmax, mt)
+            sub[j, k, y, x, :K] = bins
+            sub[j, k, y, x, K] = f32(1) - T
+            live[k, y, x] |= lv
     return sub, live
-
-
-def mean(sub):
-    """(spp, ...) -> the pixel, as surface_ref._mean"""
-    return surface_ref._mean(sub)
 
 
 def render(lib, field, cam, w, h, K, S=128, spp=1, min_T=1e-4, step_mode=0):
@@ -114,9 +80,7 @@ def reference(oracle, f, ocam, w, h, K, S, spp, min_T, mode):
     """-> (variants [3, h, w, K + 1], live [h, w, K]) at the thresholds of util.termination_variants(min_T), for spp sub-samples"""
     sub, live = render_variants(oracle.lib(), f, ocam, w, h, K, [f32(v) for v in util.termination_variants(min_T)], S, spp, mode)
     want = np.stack([mean(sub[j]) for j in range(sub.shape[0])])
-    # self-check: the restatement's alpha is the oracle's own render
-    img, _ = f.render(ocam, w, h, S, spp, min_T, step_mode=mode)
-    assert np.abs(want[0][..., K] - img[..., 3]).max() <= 1e-6
+    assert_alpha_is_the_oracles(f, ocam, w, h, S, spp, min_T, mode, want[0][..., K])
     return want, live.any(axis=0)
 
 

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from nerf_prv_amd import api
-from tests import depth_ref, util
+from tests import depth_ref, march_ref, util
 
 pytestmark = pytest.mark.gpu
 
@@ -117,7 +117,7 @@ def test_depth_known_answer_slab(ctx, mode):
     s = (0.5 - o[:, 2]) / d[:, 2]  # where the ray crosses the plane z = 0.5
     x, y = o[:, 0] + s * d[:, 0], o[:, 1] + s * d[:, 1]
     cos = -d[:, 2]
-    dt = np.where(mode == 1, float(depth_ref.NGP_DT), (t[:, 1] - t[:, 0]) / S)
+    dt = np.where(mode == 1, float(march_ref.NGP_DT), (t[:, 1] - t[:, 0]) / S)
     m = 0.02  # clear of the slab's edges by more than a step
     inside = ((x > m) & (x < 1 - m) & (y > m) & (y < 1 - m)).reshape(h, w)
     outside = ((x < -m) | (x > 1 + m) | (y < -m) | (y > 1 + m)).reshape(h, w)

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from nerf_prv_amd import api, planner
-from tests import entropy_ref, instances, util
+from tests import entropy_ref, instances, march_ref, util
 from tests.test_gpu_comm import free_port
 from tests.test_gpu_instances import CONFIG_IDS, CONFIGS, MIN_T, PRODUCT_STRIDE, environment, load
 from tests.test_gpu_planner import GOLD, ROOT, YAML
@@ -146,11 +146,11 @@ def test_entropy_on_the_product_fields(ctx, oracle, product, S, min_T):
     mode = 1 if S == 0 else 0
     ent, alpha, st, plain, st0 = _both(ctx, SLOT_PRODUCT, cs, api.engine_render_opts(w, h, S, 1, min_T))
     _check_identity(alpha, st, plain, st0)  # the whole view
-    got_h, got_a = entropy_ref.strided(ent[0], PRODUCT_STRIDE)[:, 0], entropy_ref.strided(alpha[0], PRODUCT_STRIDE)[:, 0]
+    got_h, got_a = march_ref.strided(ent[0], PRODUCT_STRIDE)[:, 0], march_ref.strided(alpha[0], PRODUCT_STRIDE)[:, 0]
     assert len(got_h) * 4 >= w * h
 
     def ref(mt):
-        return entropy_ref.strided(entropy_ref.reference(oracle, product.f, oc, w, h, S, 1, mt, mode, PRODUCT_STRIDE), PRODUCT_STRIDE)
+        return march_ref.strided(entropy_ref.reference(oracle, product.f, oc, w, h, S, 1, mt, mode, PRODUCT_STRIDE), PRODUCT_STRIDE)
 
     if min_T == 0.01:
         wants = [ref(mt)[:, 3:5] for mt in util.termination_variants(min_T)]

@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 from nerf_prv_amd import api, planner
-from tests import depth_ref, instances, mesh_ref, util
+from tests import depth_ref, instances, march_ref, mesh_ref, util
 from tests.test_gpu_mesh import AABB, grid_points
 from tests.test_gpu_parity import RTOL
 
@@ -387,11 +387,11 @@ def test_product_depth(ctx, oracle, product, candidate, S, min_T):
     assert opts.step_mode == (api.L.STEP_NGP if S == 0 else api.L.STEP_FIXED_S)
     rgba, depth, st, plain, st0 = depth_ref.both(ctx, SLOT_PRODUCT, cs, opts)
     depth_ref.check_identity(rgba, st, plain, st0)  # the whole view
-    got = depth_ref.strided(np.concatenate([rgba[0], depth[0][..., None]], axis=-1), PRODUCT_STRIDE)
+    got = march_ref.strided(np.concatenate([rgba[0], depth[0][..., None]], axis=-1), PRODUCT_STRIDE)
     assert len(got) * 4 >= w * h  # at least one pixel in four
 
     def ref(mt):
-        return depth_ref.strided(depth_ref.reference(oracle, product.f, oc, w, h, S, 1, mt, mode, PRODUCT_STRIDE), PRODUCT_STRIDE)
+        return march_ref.strided(depth_ref.reference(oracle, product.f, oc, w, h, S, 1, mt, mode, PRODUCT_STRIDE), PRODUCT_STRIDE)
 
     if min_T == 0.01:
         util.assert_pixels_close_any(got, [ref(mt) for mt in util.termination_variants(min_T)])

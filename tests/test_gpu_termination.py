@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from nerf_prv_amd import api
-from tests import depth_ref, instances, surface_ref, termination_ref as tr, util
+from tests import instances, march_ref, surface_ref, termination_ref as tr, util
 from tests.surface_ref import FH, FW
 from tests.test_gpu_comm import free_port
 from tests.test_gpu_instances import environment, load
@@ -67,8 +67,7 @@ def _check_case(ctx, oracle, m, slot, cs, ocams, mode, S, K, spps):
         for v, oc in enumerate(ocams):
             sub, live = refs[v]
             want = np.stack([tr.mean(sub[j, :spp]) for j in range(sub.shape[0])])
-            img, _ = m.f.render(oc, FW, FH, S, spp, MIN_T, step_mode=mode)  # self-check: the restatement's alpha is the oracle's
-            assert np.abs(want[0][..., K] - img[..., 3]).max() <= 1e-6
+            march_ref.assert_alpha_is_the_oracles(m.f, oc, FW, FH, S, spp, MIN_T, mode, want[0][..., K])
             _assert_against_reference(bins[:, v], alpha[v], want, f"{m.name}/{'ngp' if mode else 'S%d' % S}/K{K}/spp{spp}/view{v}")
             untouched = ~live[:spp].any(axis=0)  # [h, w, K]: bins no live sample of any sub-sample falls in
             assert not np.moveaxis(bins[:, v], 0, -1)[untouched].any()
@@ -192,9 +191,9 @@ def test_termination_is_consistent_with_entropy_and_footprint(ctx, oracle):
             for v, oc in enumerate(ocams):
                 o, d, t = ctx.debug_raygen(cs, v, FW, FH)
                 t0, t1 = t[:, 0].reshape(FH, FW).astype(np.float64), t[:, 1].reshape(FH, FW).astype(np.float64)
-                cos = np.array([depth_ref.forward_cos(oc, di) for di in d], np.float64).reshape(FH, FW)
+                cos = np.array([march_ref.forward_cos(oc, di) for di in d], np.float64).reshape(FH, FW)
                 # bin k holds steps [k n_max / K, (k + 1) n_max / K): its middle in t, and the width of a bin
-                width = (t1 - t0) / K if mode == 0 else float(depth_ref.NGP_DT) * tr.NGP_STEPS / K
+                width = (t1 - t0) / K if mode == 0 else float(march_ref.NGP_DT) * march_ref.NGP_STEPS / K
                 solid = alpha[v] >= 0.5
                 assert solid.sum() > 20
                 centre = (bins[:, v].astype(np.float64) * (np.arange(K) + 0.5)[:, None, None]).sum(axis=0)[solid] / total[v][solid]
