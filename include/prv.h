@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PRV_ABI_VERSION 5 /* 2: prv_field_desc.per_level_scale; 3: prv_render_opts.step_mode, prv_stats.samples_live; 4: prv_train_opts.patch_w / patch_h; 5: prv_train_opts.step_mode / deterministic (still 5: prv_train_create accepting lr = 0, which it refused, changes no layout and no call that worked) */
+#define PRV_ABI_VERSION 5 /* 2: prv_field_desc.per_level_scale; 3: prv_render_opts.step_mode, prv_stats.samples_live; 4: prv_train_opts.patch_w / patch_h; 5: prv_train_opts.step_mode / deterministic (still 5: prv_train_create accepting lr = 0, which it refused, changes no layout and no call that worked; nor do the prv_coverage_* entry points: additive) */
 
 /* error codes (0 = ok, < 0 = error; message via prv_last_error) */
 #define PRV_OK 0
@@ -631,6 +631,76 @@ int prv_geometry_metrics(prv_ctx* ctx, const float* rec_xyz_dev, uint64_t n_rec,
  * ref_xyz_dev / n_ref must be the points the index was made of (n_ref is checked); identical results. */
 int prv_geometry_metrics_indexed(prv_ctx* ctx, const float* rec_xyz_dev, uint64_t n_rec, prv_nn_index* ref_index,
                                  const float* ref_xyz_dev, uint64_t n_ref, float tau, prv_geom_metrics* out);
+
+/* ---- surface coverage of a reference cloud by a set of views ------------------ */
+/* replaces: nothing in the reference.  This build's own: the training-free ground truth of the next-best-view literature --
+ * the share of a reference surface that a list of views sees, against the number of views, and what the greedy choice of as
+ * many views out of the same set would have seen.  It prices a view choice without training a field on it.
+ * Inputs: n_points points in the ENGINE frame (device n*3 float32: what prv_mesh_sample writes and prv_nn_index_create takes;
+ * a dataset-frame cloud goes through q = fmaf(p, scale, offset), e = (q1, q2, q0) first, as prv_splat_points places it); n_views
+ * views of a camset (view_ids NULL: cameras 0..n_views-1) at width x height, with the meaning prv_splat_points gives the size.
+ * ARITHMETIC CONTRACT.  Every float operation below is one IEEE float32 operation in the order written (fmaf = one fused
+ * multiply-add), so a float32 restatement is bit-exact.  M = the view's engine-frame c2w (3 x 4, row-major), o its column 3,
+ * (fx, fy, cx, cy) its intrinsics at width x height, e the point.
+ *   projection (prv_splat_points' own):
+ *     d_a = e_a - o_a
+ *     c_a = fmaf(M[0][a], d_0, fmaf(M[1][a], d_1, M[2][a] * d_2))                  a = 0, 1, 2
+ *     it fails unless c_2 > 1e-6f (a NaN fails) and, for this stage, c_2 < +Inf
+ *     x = c_0 / c_2, y = c_1 / c_2; a lens camera distorts them: (x, y) = lens_eval(x, y), the OpenCV model in the ray generator's order
+ *     u = fmaf(fx, x, cx), v = fmaf(fy, y, cy), z = c_2
+ *   stage A, depth buffers: one uint32 per pixel and view, 0xFFFFFFFF at the start.  With ps = (float)point_size:
+ *     fx0 = floorf(u - 0.5f * ps + 0.5f), fy0 = floorf(v - 0.5f * ps + 0.5f)      (u - 0.5f * ps, then + 0.5f)
+ *     the block is dropped unless fx0 > -ps, fx0 < (float)width, fy0 > -ps and fy0 < (float)height (a NaN fails);
+ *     x0 = (int)fx0, y0 = (int)fy0; every pixel (x0 + i, y0 + j), 0 <= i, j < point_size, inside the image takes
+ *     min(pixel, bits of z) -- z > 1e-6, so the bits order as the floats do.  These are the pixels prv_splat_points writes.
+ *     A minimum does not depend on the order.  depth_out_dev: the buffers as float, 0 where no point fell.
+ *   stage B, visibility: point i is visible in view v iff the projection succeeds, fu = floorf(u) and fv = floorf(v) satisfy
+ *     0 <= fu < (float)width and 0 <= fv < (float)height (a NaN fails), and
+ *         z <= zmin * tol1        one float32 multiply, one comparison
+ *     with zmin the depth buffer at ((int)fu, (int)fv) (an empty pixel fails) and tol1 = 1.0f + depth_tol, formed once in
+ *     float32.  The point's own block covers its pixel, so zmin <= z: with depth_tol = 0 exactly the nearest points of a pixel
+ *     are visible (equal depths all are).  bits[v][w], w < ceil(n_points / 64): bit j of the word = point 64 w + j; the bits
+ *     past n_points are 0.
+ *   stage C, in integers: C = a set of points, empty at the start.
+ *     curve: for j = 0..k-1: gain_j = popcount(bits[order[j]] & ~C); C |= bits[order[j]]; covered[j] = gain_0 + .. + gain_j;
+ *       first_seen[i] = the first j whose view sees point i, 0xFFFFFFFF if none does.  A repeated view gains 0.
+ *     greedy: k rounds; each takes the largest popcount(bits[i] & ~C) among the views not yet chosen, on a tie the smallest
+ *       position i, and goes on when that gain is 0; covered[j] is cumulative as above.
+ *   order and chosen_out hold POSITIONS 0..n_views-1 in the handle's view list, not camset ids.
+ * The gains are integer atomics and popcounts, the arg-max is taken on the host from a read-back of the gains per round:
+ * two calls return identical bytes.  The views' depth buffers are built in batches that fit a fixed scratch budget (256 MiB,
+ * at least one view per batch: no view count fails for depth-buffer memory alone); the batching changes no byte.  The handle
+ * keeps the bit matrix (n_views * ceil(n_points / 64) * 8 bytes) and copies nothing else: the points may go away.
+ * n_points = 0 is not an error: every count is 0.  Synchronises.
+ * Errors, PRV_E_INVALID with a message: a NULL or host pointer where a device pointer is required, point_size outside 1..64,
+ * depth_tol negative or not finite, k < 1 or k > n_views (greedy), an order entry out of range, more than 2^31 points.
+ * LIMITS: visibility comes from a POINT z-buffer, not from a rasterised surface -- holes between the points of a sparse cloud
+ * let the far side through (raise point_size, or sample more points, until a pixel's footprint holds several), and depth_tol
+ * trades the undercount at grazing angles (one pixel spans a range of depths there) against seeing through thin parts; its
+ * default 0.02 is an option value, NOT a measured one.  There is no incidence-angle or distance weighting: a point seen
+ * once, from whatever angle, counts as seen (the selection stage's "coverage is binary", priced here rather than lifted).
+ * The stage is SINGLE-RANK: the bit matrix of every view lives on one device. */
+typedef struct prv_coverage prv_coverage; /* owns the bit matrix; inert (PRV_E_STATE) if it outlives its context */
+typedef struct prv_coverage_opts {
+  int32_t point_size; /* 1..64, default 1 */
+  float depth_tol;    /* >= 0, default 0.02 */
+} prv_coverage_opts;
+int prv_coverage_default_opts(prv_coverage_opts* opts); /* point_size 1, depth_tol 0.02 */
+/* opts NULL: the defaults.  depth_out_dev (device, optional): n_views*h*w float32, nearest z per pixel, 0 = empty, unflipped */
+int prv_coverage_create(prv_ctx* ctx, const float* xyz_dev, uint64_t n_points, const prv_camset* cs, const int* view_ids,
+                        int n_views, int width, int height, const prv_coverage_opts* opts, float* depth_out_dev,
+                        prv_coverage** out);
+/* n_coverable: points at least one view sees; any pointer may be NULL */
+int prv_coverage_info(const prv_coverage* cov, uint64_t* n_points, int* n_views, uint64_t* n_coverable);
+/* per_view_host: n_views counts, the points each view sees on its own */
+int prv_coverage_visible(const prv_coverage* cov, uint64_t* per_view_host);
+/* words_host: the ceil(n_points / 64) words of one view (a test hook) */
+int prv_coverage_bits(const prv_coverage* cov, int view, uint64_t* words_host);
+/* covered_host: k cumulative counts; first_seen_dev (device, optional): n_points uint32 */
+int prv_coverage_curve(prv_coverage* cov, const int* order, int k, uint64_t* covered_host, uint32_t* first_seen_dev);
+/* chosen_out: k positions (host); covered_host: k cumulative counts (host, may be NULL) */
+int prv_coverage_greedy(prv_coverage* cov, int k, int* chosen_out, uint64_t* covered_host);
+void prv_coverage_destroy(prv_coverage* cov);
 
 /* ---- several GPUs: view sharding + one all-gather ----------------------------- */
 /* replaces: nothing in the reference -- its loops over the candidates are serial (main.cpp:2045-2094, 2105-2158;

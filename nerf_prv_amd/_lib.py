@@ -94,6 +94,10 @@ class SelectOpts(C.Structure):
     _fields_ = [("k", C.c_int32), ("grid_res", C.c_int32), ("alpha_min", C.c_float)]
 
 
+class CoverageOpts(C.Structure):
+    _fields_ = [("point_size", C.c_int32), ("depth_tol", C.c_float)]
+
+
 class GeomMetrics(C.Structure):
     _fields_ = [("n_rec", C.c_uint64), ("n_ref", C.c_uint64)] + [(n, C.c_double) for n in (
         "accuracy", "completeness", "accuracy_sq", "completeness_sq", "chamfer", "precision", "recall", "fscore", "hausdorff_rec",
@@ -200,6 +204,14 @@ SIGNATURES = {
     "prv_nn_index_destroy": (None, [_vp]),
     "prv_geometry_metrics": (_i, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_float, _P(GeomMetrics)]),
     "prv_geometry_metrics_indexed": (_i, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.c_float, _P(GeomMetrics)]),
+    "prv_coverage_default_opts": (_i, [_P(CoverageOpts)]),
+    "prv_coverage_create": (_i, [_vp, _vp, C.c_uint64, _vp, _vp, _i, _i, _i, _P(CoverageOpts), _vp, _P(_vp)]),
+    "prv_coverage_info": (_i, [_vp, _P(C.c_uint64), _P(_i), _P(C.c_uint64)]),
+    "prv_coverage_visible": (_i, [_vp, _vp]),
+    "prv_coverage_bits": (_i, [_vp, _i, _vp]),
+    "prv_coverage_curve": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "prv_coverage_greedy": (_i, [_vp, _i, _vp, _vp]),
+    "prv_coverage_destroy": (None, [_vp]),
     "prv_score_ensemble_images": (_i, [_vp, _i, _vp, _i, _i, C.c_size_t, _vp]),
     "prv_score_psnr_images": (_i, [_vp, _vp, _vp, _i, C.c_size_t, _vp, _vp]),
     "prv_evaluate_images": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

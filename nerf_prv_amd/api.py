@@ -595,6 +595,19 @@ class Context:
             self._chk(self.lib.prv_geometry_metrics(self.handle, _ptr(a), a.shape[0], _ptr(b), b.shape[0], float(tau), C.byref(out)))
         return {name: getattr(out, name) for name, _ in L.GeomMetrics._fields_}
 
+    def coverage(self, points, camset, view_ids, width, height, point_size=1, depth_tol=0.02, want_depth=False):
+        """which of `points` ((n, 3), ENGINE frame) each of the views sees (prv_coverage_create) -> Coverage; want_depth: its
+        `.depth` is the views' nearest-depth buffers, float32 [n_views, h, w] on the device, 0 = empty"""
+        t = self.torch
+        pts = self._points(points)
+        ids = self._ids(camset, view_ids)
+        o = L.CoverageOpts(int(point_size), float(depth_tol))
+        depth = t.empty((len(ids), int(height), int(width)), dtype=t.float32, device=self.device) if want_depth else None
+        h = C.c_void_p()
+        self._chk(self.lib.prv_coverage_create(self.handle, _ptr(pts) if pts.shape[0] else None, pts.shape[0], camset.handle, _ptr(ids),
+                                               len(ids), int(width), int(height), C.byref(o), _ptr(depth), C.byref(h)))
+        return Coverage(self, h, depth)
+
     def mesh_stage_ms(self):
         """milliseconds of the last extraction's stages: density grid, classify + scans, emit, colours"""
         ms = (C.c_float * 4)()
@@ -768,6 +781,70 @@ class NNIndex:
     def close(self):
         if self.handle:
             self.ctx.lib.prv_nn_index_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Coverage:
+    """the visibility bit matrix of a cloud under a list of views, owned by the library (prv_coverage).  Views are named by
+    their POSITION in the list the handle was made with"""
+
+    def __init__(self, ctx, handle, depth=None):
+        self.ctx, self.handle, self.depth = ctx, handle, depth
+
+    _chk = NNIndex._chk
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self):
+        n, v, cov = C.c_uint64(), C.c_int(), C.c_uint64()
+        self._chk(self.ctx.lib.prv_coverage_info(self.handle, C.byref(n), C.byref(v), C.byref(cov)))
+        return dict(n_points=n.value, n_views=v.value, n_coverable=cov.value)
+
+    def visible(self):
+        """-> uint64 (n_views,): the points each view sees on its own"""
+        out = np.zeros(self.info()["n_views"], np.uint64)
+        self._chk(self.ctx.lib.prv_coverage_visible(self.handle, _ptr(out)))
+        return out
+
+    def bits(self, view):
+        """-> uint64 (ceil(n_points / 64),): bit j of word w = point 64 w + j is visible in the view at position `view`"""
+        out = np.zeros((self.info()["n_points"] + 63) // 64, np.uint64)
+        self._chk(self.ctx.lib.prv_coverage_bits(self.handle, int(view), _ptr(out)))
+        return out
+
+    def curve(self, order, want_first_seen=False):
+        """the points the views order[0..j] see together, j = 0..k-1 -> uint64 (k,); with want_first_seen also an int32 device
+        tensor (n_points,) holding uint32 bit patterns: the first j whose view sees the point, 0xFFFFFFFF = never"""
+        order = np.ascontiguousarray(order, np.int32).ravel()
+        out = np.zeros(len(order), np.uint64)
+        first = None
+        if want_first_seen:
+            t = self.ctx.torch
+            first = t.empty((self.info()["n_points"],), dtype=t.int32, device=self.ctx.device)
+        self._chk(self.ctx.lib.prv_coverage_curve(self.handle, _ptr(order), len(order), _ptr(out),
+                                                  _ptr(first) if first is not None and first.numel() else None))
+        return (out, first) if want_first_seen else out
+
+    def greedy(self, k):
+        """k greedy rounds -> (chosen positions int32 (k,), cumulative covered counts uint64 (k,))"""
+        k = int(k)
+        chosen, covered = np.zeros(max(k, 0), np.int32), np.zeros(max(k, 0), np.uint64)
+        self._chk(self.ctx.lib.prv_coverage_greedy(self.handle, k, _ptr(chosen), _ptr(covered)))
+        return chosen, covered
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.prv_coverage_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -1252,6 +1329,24 @@ class Testbed:
             out[k] /= self.scale
         for k in ("accuracy_sq", "completeness_sq"):
             out[k] /= self.scale ** 2
+        return out
+
+    def compute_coverage(self, reference_points, camset, chosen, width=None, height=None, point_size=1, depth_tol=0.02):
+        """how much of a reference surface the views `chosen` (camera ids of `camset`, in the order they were taken) see, against
+        the greedy choice of as many views out of the WHOLE camset.  reference_points: (n, 3), dataset frame; the size defaults
+        to the camset's.  Needs no model: nothing is trained or rendered.
+        -> dict(n_points, n_coverable, covered[k] cumulative, greedy_covered[k], greedy_chosen[k] camera ids)"""
+        ref = np.asarray(reference_points, np.float64).reshape(-1, 3)
+        w, h = camset.size
+        chosen = [int(v) for v in chosen]
+        with self.ctx.coverage(dataset_to_engine(ref, self.scale, self.offset).astype(np.float32), camset, None,
+                               int(width or w), int(height or h), point_size, depth_tol) as cov:
+            info = cov.info()
+            out = dict(n_points=info["n_points"], n_coverable=info["n_coverable"], covered=[], greedy_covered=[], greedy_chosen=[])
+            if chosen:
+                out["covered"] = [int(c) for c in cov.curve(chosen)]
+                g, gc = cov.greedy(min(len(chosen), info["n_views"]))
+                out["greedy_chosen"], out["greedy_covered"] = [int(v) for v in g], [int(c) for c in gc]
         return out
 
     def _ground_truth(self, i, width, height):

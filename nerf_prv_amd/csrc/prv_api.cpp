@@ -22,6 +22,7 @@
 #include "prv_mesh.hpp"
 #include "prv_geom.hpp"
 #include "prv_select.hpp"
+#include "prv_coverage.hpp"
 #include "prv_levels.hpp"
 #include "prv_ingp.hpp"
 #include "prv_train.hpp"
@@ -68,6 +69,7 @@ static void train_detach_all(struct prv_ctx* c);
 static void comm_detach_all(struct prv_ctx* c);
 static void mesh_detach_all(struct prv_ctx* c);
 static void nn_detach_all(struct prv_ctx* c);
+static void coverage_detach_all(struct prv_ctx* c);
 
 struct prv_ctx {
   int device = 0;
@@ -104,6 +106,7 @@ struct prv_ctx {
   std::vector<struct prv_comm*> comms;       // live communicators of this context (detached by prv_destroy)
   std::vector<struct prv_mesh*> meshes;      // live meshes of this context (detached by prv_destroy)
   std::vector<struct prv_nn_index*> nn_indexes; // live nearest-neighbour indexes of this context (detached by prv_destroy)
+  std::vector<struct prv_coverage*> coverages;  // live coverage handles of this context (detached by prv_destroy)
   float mesh_ms[4] = {0, 0, 0, 0};           // stages of the last mesh extraction (prv_mesh_api.inc: prv_debug_mesh_stages)
   int queue_segments = 8; // ray-queue segments = XCDs (PRV_QUEUE_SEGMENTS: 1 = single shared head)
   int spatial_regions = 1; // a wave's records go to the region of its first live ray's octant (PRV_SPATIAL_REGIONS=0: block id % regions, rounds 1-5)
@@ -1186,6 +1189,7 @@ void prv_destroy(prv_ctx* c) {
   comm_detach_all(c);  // ... and so do communicators
   mesh_detach_all(c);  // ... and meshes
   nn_detach_all(c);    // ... and nearest-neighbour indexes
+  coverage_detach_all(c); // ... and coverage handles
   for (hipEvent_t e : c->ev_render) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_march) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_free) (void)hipEventDestroy(e);
@@ -2288,3 +2292,4 @@ int prv_debug_field(prv_ctx* c, int slot, const float* pos, const float* dir, in
 #include "prv_mesh_api.inc"
 #include "prv_geom_api.inc"
 #include "prv_select_api.inc"
+#include "prv_coverage_api.inc"

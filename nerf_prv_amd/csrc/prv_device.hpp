@@ -148,6 +148,35 @@ __device__ __forceinline__ void raygen(const CamDev& cam, int px, int py, float 
   for (int r = 0; r < 3; r++) d[r] = v[r] * inv;
 }
 
+// dataset-frame point -> the engine frame, as a cloud is placed where the cameras go: q = fmaf(p, scale, off), e = (q1, q2, q0)
+__device__ __forceinline__ void dataset_to_engine_point(float scale, const float off[3], const float* p, float e[3]) {
+  const float q[3] = {fmaf(p[0], scale, off[0]), fmaf(p[1], scale, off[1]), fmaf(p[2], scale, off[2])};
+  e[0] = q[1];
+  e[1] = q[2];
+  e[2] = q[0];
+}
+
+// engine-frame point -> pixel coordinates (u, v) and camera depth z of a view; false: not in front of the camera (z <= 1e-6 or NaN).
+// The point splat's and the coverage stage's projection (the contract is written out in include/prv.h, "surface coverage")
+__device__ __forceinline__ bool project_engine_point(const CamDev& cam, const float e[3], float& u, float& v, float& z) {
+  const float d[3] = {e[0] - cam.c2w[3], e[1] - cam.c2w[7], e[2] - cam.c2w[11]};
+  float c[3];
+#pragma unroll
+  for (int a = 0; a < 3; a++) c[a] = fmaf(cam.c2w[a], d[0], fmaf(cam.c2w[4 + a], d[1], cam.c2w[8 + a] * d[2]));
+  if (!(c[2] > 1e-6f)) return false;
+  float x = c[0] / c[2], y = c[1] / c[2];
+  if (has_lens(cam)) {
+    float xd, yd, J[4];
+    lens_eval(cam.lens, x, y, xd, yd, J);
+    x = xd;
+    y = yd;
+  }
+  u = fmaf(cam.fx, x, cam.cx);
+  v = fmaf(cam.fy, y, cam.cy);
+  z = c[2];
+  return true;
+}
+
 // slab test against the unit cube; returns hit
 __device__ __forceinline__ bool ray_aabb(const float o[3], const float d[3], float& t0, float& t1) {
   float tmin = 0.0f, tmax = __builtin_inff();

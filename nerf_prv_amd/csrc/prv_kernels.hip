@@ -1815,27 +1815,7 @@ __global__ __launch_bounds__(256) void debug_field64_kernel(FieldDev fd, const f
 // Share_Data.hpp:771-784) as a z-buffered square-splat rasteriser: one lane = one point of one view, the
 // depth test is a 64-bit atomicMin on (depth bits << 32 | colour), so the result does not depend on order
 
-__device__ __forceinline__ bool splat_project(const CamDev& cam, float scale, const float off[3], const float* p,
-                                              float& u, float& v, float& z) {
-  const float q[3] = {fmaf(p[0], scale, off[0]), fmaf(p[1], scale, off[1]), fmaf(p[2], scale, off[2])};
-  const float e[3] = {q[1], q[2], q[0]};
-  const float d[3] = {e[0] - cam.c2w[3], e[1] - cam.c2w[7], e[2] - cam.c2w[11]};
-  float c[3];
-#pragma unroll
-  for (int a = 0; a < 3; a++) c[a] = fmaf(cam.c2w[a], d[0], fmaf(cam.c2w[4 + a], d[1], cam.c2w[8 + a] * d[2]));
-  if (!(c[2] > 1e-6f)) return false;
-  float x = c[0] / c[2], y = c[1] / c[2];
-  if (has_lens(cam)) {
-    float xd, yd, J[4];
-    lens_eval(cam.lens, x, y, xd, yd, J);
-    x = xd;
-    y = yd;
-  }
-  u = fmaf(cam.fx, x, cam.cx);
-  v = fmaf(cam.fy, y, cam.cy);
-  z = c[2];
-  return true;
-}
+// (the frame change and the projection are prv_device.hpp's: the coverage stage projects with the same pair)
 
 __global__ __launch_bounds__(256) void splat_points_kernel(const float* __restrict__ xyz, const uint8_t* __restrict__ rgb,
                                                            size_t n, float scale, float ox, float oy, float oz,
@@ -1846,8 +1826,9 @@ __global__ __launch_bounds__(256) void splat_points_kernel(const float* __restri
   const CamDev cam = cams[blockIdx.y];
   const float off[3] = {ox, oy, oz};
   const float p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
-  float u, v, z;
-  if (!splat_project(cam, scale, off, p, u, v, z)) return;
+  float e[3], u, v, z;
+  dataset_to_engine_point(scale, off, p, e);
+  if (!project_engine_point(cam, e, u, v, z)) return;
   const uint32_t col = (uint32_t)rgb[3 * i] | ((uint32_t)rgb[3 * i + 1] << 8) | ((uint32_t)rgb[3 * i + 2] << 16);
   const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | col;
   const int x0 = (int)floorf(u - 0.5f * (float)point_size + 0.5f), y0 = (int)floorf(v - 0.5f * (float)point_size + 0.5f);

@@ -12,6 +12,7 @@
 
 #include "planner.hpp"
 #include "geometry_eval.hpp"
+#include "coverage_eval.hpp"
 #include "extras/pcd_io.hpp"
 #include "png_io.hpp"
 #include "prv_handles.hpp"
@@ -58,6 +59,7 @@ struct EngineConfig {
   bool select_surface = false;    // select_locator: surface -- prv_select_views_surface at select_level (read and policed by Share_Data)
   float select_level = 0.5f;
   GeometryEvalConfig geom;        // evaluate_geometry and its keys (geometry_eval.hpp)
+  CoverageEvalConfig cover;       // evaluate_coverage and its keys (coverage_eval.hpp)
 
   void apply_train_opts(prv_train_opts& to) const {
     if (train_deterministic) to.deterministic = 1;
@@ -123,6 +125,7 @@ inline EngineConfig engine_config(const FileStorage& fs, const Share_Data& sd, i
     c.select_level = (float)sd.select_level;
   }
   c.geom = geometry_eval_config(fs);
+  c.cover = coverage_eval_config(fs);
   return c;
 }
 
@@ -153,6 +156,7 @@ struct PlannerEngine {
   ~PlannerEngine() { // the caches of an object's life, in the order the shell has always released them
     data.drop();
     test.drop();
+    cover.drop();
     geom_ref.drop();
     references.reset();
   }
@@ -469,7 +473,9 @@ struct PlannerEngine {
 
   // the reference surface in the engine frame + its index; every failure is a message and an error BEFORE any training
   int geometry_setup(const Vec3& center, double size) {
-    const std::string problem = geometry_eval_problem(cfg.geom);
+    GeometryEvalConfig checked = cfg.geom; // (evaluate_coverage alone uses the same reference: the same keys are policed)
+    checked.on = true;
+    const std::string problem = geometry_eval_problem(checked);
     if (!problem.empty()) {
       std::cerr << "evaluate_geometry: " << problem << std::endl;
       return -80;
@@ -512,7 +518,7 @@ struct PlannerEngine {
       if (rc == PRV_OK) rc = prv_mesh_sample(m.get(), geom_ref.n, 1, geom_ref.points.get(), nullptr);
       m.reset(); // (before the index is built and any echo, as ever)
     }
-    if (rc == PRV_OK) rc = prv_nn_index_create(ctx, geom_ref.points.get(), geom_ref.n, nullptr, out_arg(geom_ref.index));
+    if (rc == PRV_OK && cfg.geom.on) rc = prv_nn_index_create(ctx, geom_ref.points.get(), geom_ref.n, nullptr, out_arg(geom_ref.index));
     if (rc != PRV_OK) {
       std::cerr << "evaluate_geometry: " << prv_last_error(ctx) << std::endl;
       geom_ref.drop();
@@ -548,6 +554,66 @@ struct PlannerEngine {
       return rc;
     }
     return write_text(path, geometry_metrics_text(gm, geom_ref.scale)) ? PRV_OK : PRV_E_IO;
+  }
+
+  // ================================================================================ coverage
+  // `evaluate_coverage: 1` (coverage_eval.hpp): how much of the reference surface (geom_ref.points: geometry_setup runs first) the
+  // views chosen so far see, and what the greedy choice of as many views of the whole view space would have seen.  The handle --
+  // which point is visible from which view of the space -- is built once per object; an iteration costs one curve and one greedy
+  // call on it.  Nothing here trains or renders a field.
+  struct CoverageState {
+    CoveragePtr handle;
+    uint64_t n_points = 0, n_coverable = 0;
+    int n_views = 0;
+    void drop() { handle.reset(); }
+  } cover;
+
+  int coverage_setup(std::vector<View>& views, const Vec3& center, double size) {
+    cover.drop();
+    if (!geom_ref.points.get()) return PRV_E_STATE;
+    const std::string all_json = sd->gt_path + "/" + std::to_string(sd->num_of_views) + "_coverage.json"; // every view of the space, candidate header
+    Value root = transforms_header(sd->color_intrinsics, sd->ray_casting_aabb_scale, size, center, sd->candidate_divisor);
+    for (size_t i = 0; i < views.size(); i++) {
+      Value v;
+      v["file_path"] = Value("rgbaClip_" + std::to_string(i) + ".png");
+      v["transform_matrix"] = matrix_json(view_transform_matrix(views[i], Mat4::Identity(), center));
+      root["frames"].append(v);
+    }
+    write_text(all_json, prvjson::to_styled_string(root));
+    CamsetPtr cams;
+    if (prv_cameras_from_json(ctx, all_json.c_str(), out_arg(cams)) != PRV_OK) {
+      std::cerr << "evaluate_coverage: " << prv_last_error(ctx) << std::endl;
+      return -84;
+    }
+    const prv_render_opts o = candidate_opts(cams.get()); // the candidates' size unless the config names one
+    prv_coverage_opts co;
+    prv_coverage_default_opts(&co);
+    co.point_size = cfg.cover.point_size;
+    co.depth_tol = (float)cfg.cover.depth_tol;
+    const int n = prv_camset_count(cams.get());
+    int rc = prv_coverage_create(ctx, geom_ref.points.get(), geom_ref.n, cams.get(), nullptr, n, cfg.cover.width > 0 ? cfg.cover.width : o.width,
+                                 cfg.cover.height > 0 ? cfg.cover.height : o.height, &co, nullptr, out_arg(cover.handle));
+    if (rc == PRV_OK) rc = prv_coverage_info(cover.handle.get(), &cover.n_points, &cover.n_views, &cover.n_coverable);
+    if (rc != PRV_OK) {
+      std::cerr << "evaluate_coverage: " << prv_last_error(ctx) << std::endl;
+      cover.drop();
+    }
+    return rc;
+  }
+
+  // the views chosen so far (ids of the view space = positions in the handle) -> `path`; n_views in the file = how many they are
+  int coverage_evaluate(const std::vector<int>& chosen, const std::string& path) {
+    if (!cfg.cover.on || !cover.handle || chosen.empty()) return PRV_OK;
+    const int k = (int)chosen.size();
+    std::vector<uint64_t> covered((size_t)k), greedy((size_t)k);
+    std::vector<int> picks((size_t)k);
+    int rc = prv_coverage_curve(cover.handle.get(), chosen.data(), k, covered.data(), nullptr);
+    if (rc == PRV_OK) rc = prv_coverage_greedy(cover.handle.get(), std::min(k, cover.n_views), picks.data(), greedy.data());
+    if (rc != PRV_OK) {
+      std::cerr << "evaluate_coverage: " << prv_last_error(ctx) << std::endl;
+      return rc;
+    }
+    return write_text(path, coverage_text(cover.n_points, cover.n_coverable, k, covered.back(), greedy[(size_t)std::min(k, cover.n_views) - 1])) ? PRV_OK : PRV_E_IO;
   }
 
   // ================================================================================ selection and scoring

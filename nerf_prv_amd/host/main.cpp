@@ -179,10 +179,22 @@ int PlanningJob::install_callbacks(const Vec3& center, double size) {
     }
     lab->evaluator = [e, center, size](const std::string& scene, double* p, double* q) { return e->evaluate(scene, center, size, p, q); };
   }
-  if (e->cfg.geom.on) { // the reference surface once per object; a run without a usable one stops here, before any training
+  if (e->cfg.cover.on) { // a bad key of the coverage evaluation is reported before anything is set up or trained
+    const std::string problem = coverage_eval_problem(e->cfg.cover);
+    if (!problem.empty()) {
+      std::cerr << "evaluate_coverage: " << problem << "; nothing was trained" << std::endl;
+      return -85;
+    }
+  }
+  if (e->cfg.geom.on || e->cfg.cover.on) { // the reference surface once per object; a run without a usable one stops here, before any training
     const int rc = e->geometry_setup(center, size);
     if (rc != PRV_OK) return rc;
-    lab->geometry_evaluator = [e](const std::string& path) { return e->geometry_evaluate(e->slot_of(0), path); };
+    if (e->cfg.geom.on) lab->geometry_evaluator = [e](const std::string& path) { return e->geometry_evaluate(e->slot_of(0), path); };
+  }
+  if (e->cfg.cover.on) { // which reference point each view of the space sees, once per object
+    const int rc = e->coverage_setup(lab->view_space->views, center, size);
+    if (rc != PRV_OK) return rc;
+    lab->coverage_evaluator = [e](const std::vector<int>& chosen, const std::string& path) { return e->coverage_evaluate(chosen, path); };
   }
   if (sd->views_per_iteration > 1)
     lab->selector = [e](int iteration, const std::string& scene, const std::string& render, const std::vector<int>& ids, int k,

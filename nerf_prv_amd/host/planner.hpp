@@ -193,6 +193,9 @@ public:
   Engine engine;      // the in-process run.py behind train_by_instantNGP's reference signature
   EvalFn evaluator;   // empty: `evaluate: 1` is ignored
   std::function<int(const std::string&)> geometry_evaluator; // `evaluate_geometry: 1`: writes the geometry file named, beside every metrics/<it>.txt
+  // `evaluate_coverage: 1`: (views chosen so far, file) -> metrics/<it>_coverage.txt, once per iteration (it needs no training,
+  // so it is written for every <it>, the ones with a metrics/<it>.txt among them)
+  std::function<int(const std::vector<int>&, const std::string&)> coverage_evaluator;
   std::vector<int> chosen_nbvs;
   std::vector<double> last_scores;
   // called after every scoring iteration with (iteration, unchosen view ids, their scores): logging / test dumps live in
@@ -397,6 +400,10 @@ public:
     run.render_json = sd.save_path + "/render_json/" + it + ".json";
     write_text(run.scene_json, prvjson::to_styled_string(now_nbvs_json));     // :1918-1920
     write_text(run.render_json, prvjson::to_styled_string(now_render_json)); // :1922-1924
+    if (coverage_evaluator) {
+      const int crc = coverage_evaluator(chosen_nbvs, sd.save_path + "/metrics/" + it + "_coverage.txt");
+      if (crc != 0) return crc < 0 ? crc : -13;
+    }
     // (views_per_iteration > 1: the loop ends at the same TOTAL number of views as the one-view loop, whatever the round count)
     const bool budget_spent = sd.views_per_iteration > 1 ? (int)chosen_nbvs.size() - 1 >= sd.num_of_max_iteration : run.iteration == sd.num_of_max_iteration;
     if (budget_spent || run.candidates.empty()) { // :1946-1966

@@ -1,5 +1,5 @@
 // prv_handles.hpp -- move-only owners of what the planner shell allocates through include/prv.h: device memory, camera
-// sets, the nearest-neighbour index, meshes and trainers.  A handle releases what it holds when it leaves its scope, so an
+// sets, the nearest-neighbour index, meshes, coverage handles and trainers.  A handle releases what it holds when it leaves its scope, so an
 // early return between two acquisitions leaks nothing.  prv_planner-private (the functions named here are libprv_hip's):
 // included by main.cpp's side only, never by a file of libprv_host.so.
 #pragma once
@@ -21,12 +21,16 @@ struct NnIndexDelete {
 struct MeshDelete {
   void operator()(prv_mesh* m) const { prv_mesh_destroy(m); }
 };
+struct CoverageDelete {
+  void operator()(prv_coverage* c) const { prv_coverage_destroy(c); }
+};
 struct TrainerDelete {
   void operator()(prv_trainer* t) const { prv_train_destroy(t); }
 };
 using CamsetPtr = std::unique_ptr<prv_camset, CamsetDelete>;
 using NnIndexPtr = std::unique_ptr<prv_nn_index, NnIndexDelete>;
 using MeshPtr = std::unique_ptr<prv_mesh, MeshDelete>;
+using CoveragePtr = std::unique_ptr<prv_coverage, CoverageDelete>;
 using TrainerPtr = std::unique_ptr<prv_trainer, TrainerDelete>;
 
 // the C ABI hands objects out through an out-parameter: `prv_cameras_from_json(ctx, path, out_arg(cams))` fills the handle
