@@ -272,6 +272,12 @@ int prv_render_depth(prv_ctx* ctx, int model_slot, const prv_camset* cs, const i
  *   NULL.  stats: as prv_render's for the same views.  No colour is evaluated: the density layers alone run. */
 int prv_render_entropy(prv_ctx* ctx, int model_slot, const prv_camset* cs, const int* view_ids, int n_views,
                        const prv_render_opts* opts, float* out_entropy_dev, float* out_alpha_dev, prv_stats* stats);
+/* prv_render_rgba8's byte rule alone, on n_pixels linear premultiplied RGBA float32 pixels (dev): composite over bg,
+ * un-premultiply (by the composite alpha, unless that is 0), sRGB, clamp, * 255 + 0.5, truncate; the alpha byte from the
+ * clamped composite alpha.  The clamp is fminf(fmaxf(v, 0), 1), and fmaxf returns its other operand when one is a NaN:
+ * a NaN (a NaN input, 0 * Inf, Inf - Inf, Inf / Inf along the way) gives byte 0, -0.0 and -Inf give 0, +Inf gives 255.
+ * The images of prv_score_psnr_images and prv_evaluate_images pass through the same clamp: a non-finite COLOUR counts as
+ * 0 (or 1), only a non-finite alpha reaches the coverage sums. */
 int prv_quantize_rgba8(prv_ctx* ctx, const float* rgba_dev, size_t n_pixels, const float bg[4],
                        uint8_t* out_rgba8_dev);
 /* Entropy, opacity and depth of the same views from ONE density-only launch (this build's own; what the selection stage below
