@@ -272,7 +272,12 @@ __device__ __forceinline__ uint32_t region_reserve(uint32_t* queue_count, uint32
     if (old + n <= seg_cap) return shard * seg_cap + old;
     if (old < seg_cap) c[1] = seg_cap - old; // this reservation straddles the end: [old, seg_cap) stays unwritten
   }
-  return 0u; // unreachable: the regions together hold every ray of the batch plus 64 slots each (prv_api.cpp: seg_cap)
+  // unreachable: a reservation fails only in a CLOSED region (count >= seg_cap, which stays so), and a closed region holds at least
+  // seg_cap - 63 records (the one straddling reservation, of <= 64, leaves at most 63 slots empty).  Had this wave found all n_seg
+  // regions closed, the queue would hold n_seg * (seg_cap - 63) > blocks * 256 records (seg_cap = ceil(blocks / n_seg) * 256 + 64,
+  // prv_api.cpp: MarchLayout) without this wave's own -- more than the launch has threads, one ray each
+  // (tests/test_queue_cases_host.py: test_capacity_invariant)
+  return 0u;
 }
 
 // the statistics: the march count (live samples before any early termination), one atomic per wave, on a counter sharded

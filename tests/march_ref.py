@@ -36,16 +36,17 @@ def forward_cos(cam, d):
     return f32(fmaf(d[0], fx, fmaf(d[1], fy, f32(d[2] * fz))) * inv)
 
 
-def rays(lib, cam, w, h, spp, pixel_stride=1):
-    """yields (k, y, x, o, d): sub-sample k's ray of every pixel whose row-major index is a multiple of pixel_stride.  o and d
-    are buffers the next ray overwrites"""
+def rays(lib, cam, w, h, spp, pixel_stride=1, pixels=None):
+    """yields (k, y, x, o, d): sub-sample k's ray of every pixel whose row-major index is a multiple of pixel_stride (pixels: of
+    these (y, x) only, whatever their index).  o and d are buffers the next ray overwrites"""
     o, d = np.zeros(3, np.float32), np.zeros(3, np.float32)
     ox, oy = C.c_float(), C.c_float()
+    chosen = None if pixels is None else {(int(y), int(x)) for y, x in pixels}
     for k in range(spp):
         lib.orc_spp_offset(k, C.byref(ox), C.byref(oy))
         for y in range(h):
             for x in range(w):
-                if (y * w + x) % pixel_stride:
+                if (y * w + x) % pixel_stride if chosen is None else (y, x) not in chosen:
                     continue
                 lib.orc_raygen(C.byref(cam), x, y, C.c_float(ox.value), C.c_float(oy.value), _p(o), _p(d))
                 yield k, y, x, o, d
