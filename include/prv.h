@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PRV_ABI_VERSION 5 /* 2: prv_field_desc.per_level_scale; 3: prv_render_opts.step_mode, prv_stats.samples_live; 4: prv_train_opts.patch_w / patch_h; 5: prv_train_opts.step_mode / deterministic (still 5: prv_train_create accepting lr = 0, which it refused, changes no layout and no call that worked; nor do the prv_coverage_* entry points: additive) */
+#define PRV_ABI_VERSION 5 /* 2: prv_field_desc.per_level_scale; 3: prv_render_opts.step_mode, prv_stats.samples_live; 4: prv_train_opts.patch_w / patch_h; 5: prv_train_opts.step_mode / deterministic (still 5: prv_train_create accepting lr = 0, which it refused, changes no layout and no call that worked; nor do the prv_coverage_* entry points: additive; nor prv_mesh_from_arrays, prv_mesh_depth and prv_coverage_create_occluded: additive too) */
 
 /* error codes (0 = ok, < 0 = error; message via prv_last_error) */
 #define PRV_OK 0
@@ -681,7 +681,9 @@ int prv_geometry_metrics_indexed(prv_ctx* ctx, const float* rec_xyz_dev, uint64_
  * Errors, PRV_E_INVALID with a message: a NULL or host pointer where a device pointer is required, point_size outside 1..64,
  * depth_tol negative or not finite, k < 1 or k > n_views (greedy), an order entry out of range, more than 2^31 points.
  * LIMITS: visibility comes from a POINT z-buffer, not from a rasterised surface -- holes between the points of a sparse cloud
- * let the far side through (raise point_size, or sample more points, until a pixel's footprint holds several), and depth_tol
+ * let the far side through.  The answer to that is the mesh occluder, prv_coverage_create_occluded below: where the surface is
+ * held as a mesh, its rasterised depth occludes and no hole is left; without a mesh, raise point_size, or sample more points,
+ * until a pixel's footprint holds several (fattened silhouettes, or memory).  depth_tol
  * trades the undercount at grazing angles (one pixel spans a range of depths there) against seeing through thin parts; its
  * default 0.02 is an option value, NOT a measured one.  There is no incidence-angle or distance weighting: a point seen
  * once, from whatever angle, counts as seen (the selection stage's "coverage is binary", priced here rather than lifted).
@@ -707,6 +709,56 @@ int prv_coverage_curve(prv_coverage* cov, const int* order, int k, uint64_t* cov
 /* chosen_out: k positions (host); covered_host: k cumulative counts (host, may be NULL) */
 int prv_coverage_greedy(prv_coverage* cov, int k, int* chosen_out, uint64_t* covered_host);
 void prv_coverage_destroy(prv_coverage* cov);
+
+/* ---- mesh depth and the mesh occluder: a rasterised surface ------------------- */
+/* replaces: nothing in the reference.  This build's own: the nearest depth of a triangle mesh per pixel and view -- the
+ * ground-truth depth image of a surface, and the occluder that closes the see-through LIMIT of the point z-buffer above.
+ * prv_mesh_from_arrays: a mesh from host arrays in the ENGINE frame (n_vertices * 3 float32, n_triangles * 3 uint32), the way
+ * in for a ground-truth or hand-made surface.  Normals read as 0 and there are no colours.  The result is an ordinary
+ * prv_mesh (prv_mesh_get, _components, _filter, _sample and _save work on it; inert, PRV_E_STATE, if it outlives its context).
+ * An empty mesh is allowed.  Errors, PRV_E_INVALID with a message: a coordinate that is not finite, a vertex id >= n_vertices,
+ * a NULL array with a non-zero count, more than 2^31 vertices or triangles.
+ * ARITHMETIC CONTRACT of prv_mesh_depth and of stage A of prv_coverage_create_occluded.  Every float32 or float64 operation
+ * below is one IEEE operation in the order written; the integers are exact.
+ *   vertices: each vertex goes through the projection of the coverage section (pinhole only: a camset with any non-zero lens
+ *     term among the views asked for is refused, PRV_E_INVALID -- a straight edge does not stay straight under a lens).  A
+ *     triangle is dropped for a view if any of its vertices fails the projection (c_2 > 1e-6f, c_2 < +Inf) or has
+ *     |u| >= 32768.0f or |v| >= 32768.0f (a NaN fails).
+ *   snap: X = (int64)rintf(u * 256.0f), Y = (int64)rintf(v * 256.0f) (round half to even), so |X|, |Y| <= 2^23.
+ *   edge functions: pixel (x, y) has its centre at Px = 256 x + 128, Py = 256 y + 128.
+ *     E_ab(P) = (Xb - Xa)(Py - Ya) - (Yb - Ya)(Px - Xa)       in int64 (below 2^49)
+ *     A2 = E_ab(c); A2 == 0: the triangle is dropped; A2 < 0: b and c are exchanged (and A2 = -A2).  Both windings are
+ *     rasterised: an occluder occludes from either side.
+ *   inside: w_a = E_bc(P) >= 0, w_b = E_ca(P) >= 0 and w_c = E_ab(P) >= 0.  Inclusive, no top-left rule: the buffer takes a
+ *     minimum, so a pixel on a shared edge hit twice is harmless and there are no cracks.
+ *   depth: i_k = 1.0 / (double)z_k;  iz = ((double)w_a * i_a + (double)w_b * i_b) + (double)w_c * i_c;
+ *     z = (float)((double)A2 / iz); the pixel takes min(pixel, bits of z) on the uint32 buffer of stage A, 0xFFFFFFFF at the start.
+ *     depth_out_dev: the buffers as float, 0 where no triangle fell (as prv_coverage_create resolves its own).
+ *   visibility (stage B with a mesh): the projection and the in-image test of stage B above, then
+ *         visible = empty pixel, or z <= zmin * tol1
+ *     with zmin the MESH buffer at the point's pixel: a point whose pixel holds no triangle is visible (nothing stands in
+ *     front of it), and a NaN z would fail.  opts->point_size is ignored.  Stage C is the coverage section's, untouched.
+ * HOW IT RUNS (no byte depends on it: the result is a minimum).  One lane per (triangle, view) walks the clipped pixel box of
+ * the snapped vertices (x from max(0, ceil((min X - 128) / 256)) to min(width - 1, floor((max X - 128) / 256)), y likewise) if it
+ * holds at most small_max pixels (64; PRV_RASTER_SMALL_PIXELS, read per call); larger boxes go to a list that a second kernel
+ * takes one workgroup per entry, in 16 x 16 tiles.  Triangles pass in chunks with chunk x views <= the list's capacity (2^22
+ * entries of 8 bytes; PRV_RASTER_LIST_ENTRIES, read per call), so the list cannot overflow.  The views are batched on the
+ * 256 MiB z-buffer budget of prv_coverage_create.  Two calls return identical bytes.  Synchronises.
+ * Errors, PRV_E_INVALID with a message: a NULL mesh, a mesh of another context, a lens camera, a NULL or host pointer where a
+ * device pointer is required, and what prv_coverage_create refuses.
+ * LIMITS: NO NEAR-PLANE CLIPPING -- a triangle with a vertex behind (or at) the camera is dropped whole for that view; the
+ * cameras of a view space stand outside the object, so no triangle of its surface straddles their near plane.  depth_tol still
+ * absorbs the depth range that one pixel spans on a slanted face (the point's own depth against the depth at the pixel's
+ * centre).  No lenses.  SINGLE-RANK, as the coverage stage is. */
+int prv_mesh_from_arrays(prv_ctx* ctx, const float* xyz_host, uint64_t n_vertices, const uint32_t* tri_host, uint64_t n_triangles,
+                         prv_mesh** out);
+/* depth_out_dev (device): n_views*h*w float32, nearest surface depth per pixel and view, 0 = no triangle, unflipped */
+int prv_mesh_depth(prv_ctx* ctx, const prv_mesh* m, const prv_camset* cs, const int* view_ids, int n_views, int width, int height,
+                   float* depth_out_dev);
+/* prv_coverage_create with the mesh, not the points, as what occludes; returns an ordinary prv_coverage */
+int prv_coverage_create_occluded(prv_ctx* ctx, const float* xyz_dev, uint64_t n_points, const prv_mesh* occluder, const prv_camset* cs,
+                                 const int* view_ids, int n_views, int width, int height, const prv_coverage_opts* opts,
+                                 float* depth_out_dev, prv_coverage** out);
 
 /* ---- several GPUs: view sharding + one all-gather ----------------------------- */
 /* replaces: nothing in the reference -- its loops over the candidates are serial (main.cpp:2045-2094, 2105-2158;
@@ -856,6 +908,9 @@ int prv_debug_raygen(prv_ctx* ctx, const prv_camset* cs, int view, int width, in
 int prv_debug_mesh_stages(prv_ctx* ctx, float ms[4]);
 /* hook + compress rounds the mesh's labelling took (0: no triangles); PRV_E_STATE before prv_mesh_components has run */
 int prv_debug_mesh_component_rounds(const prv_mesh* m, int* rounds);
+/* the last prv_mesh_depth / prv_coverage_create_occluded call: out[0] = (view, triangle) pairs rasterised, out[1] = those whose
+ * clipped pixel box held more than small_max pixels (the large path took them) */
+int prv_debug_raster_stats(prv_ctx* ctx, uint64_t out[2]);
 /* 32 fp16 features per position (bit patterns) */
 int prv_debug_encode(prv_ctx* ctx, int model_slot, const float* pos, int n, uint16_t* feat);
 /* per point: out[0]=sigma, out[1..3]=rgb, out[4..19]=density MLP outputs, out[20..35]=rgb MLP

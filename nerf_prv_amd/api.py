@@ -595,18 +595,49 @@ class Context:
             self._chk(self.lib.prv_geometry_metrics(self.handle, _ptr(a), a.shape[0], _ptr(b), b.shape[0], float(tau), C.byref(out)))
         return {name: getattr(out, name) for name, _ in L.GeomMetrics._fields_}
 
-    def coverage(self, points, camset, view_ids, width, height, point_size=1, depth_tol=0.02, want_depth=False):
+    def coverage(self, points, camset, view_ids, width, height, point_size=1, depth_tol=0.02, want_depth=False, occluder=None):
         """which of `points` ((n, 3), ENGINE frame) each of the views sees (prv_coverage_create) -> Coverage; want_depth: its
-        `.depth` is the views' nearest-depth buffers, float32 [n_views, h, w] on the device, 0 = empty"""
+        `.depth` is the views' nearest-depth buffers, float32 [n_views, h, w] on the device, 0 = empty.  occluder: a Mesh --
+        its rasterised surface, not the points, is what occludes (prv_coverage_create_occluded; point_size is ignored)"""
         t = self.torch
         pts = self._points(points)
         ids = self._ids(camset, view_ids)
         o = L.CoverageOpts(int(point_size), float(depth_tol))
         depth = t.empty((len(ids), int(height), int(width)), dtype=t.float32, device=self.device) if want_depth else None
         h = C.c_void_p()
-        self._chk(self.lib.prv_coverage_create(self.handle, _ptr(pts) if pts.shape[0] else None, pts.shape[0], camset.handle, _ptr(ids),
-                                               len(ids), int(width), int(height), C.byref(o), _ptr(depth), C.byref(h)))
+        xyz = _ptr(pts) if pts.shape[0] else None
+        if occluder is not None:
+            self._chk(self.lib.prv_coverage_create_occluded(self.handle, xyz, pts.shape[0], occluder.handle, camset.handle, _ptr(ids),
+                                                            len(ids), int(width), int(height), C.byref(o), _ptr(depth), C.byref(h)))
+        else:
+            self._chk(self.lib.prv_coverage_create(self.handle, xyz, pts.shape[0], camset.handle, _ptr(ids), len(ids), int(width),
+                                                   int(height), C.byref(o), _ptr(depth), C.byref(h)))
         return Coverage(self, h, depth)
+
+    # -- a rasterised surface (include/prv.h, mesh depth and the mesh occluder)
+    def mesh_from_arrays(self, vertices, triangles):
+        """a Mesh from host arrays in the ENGINE frame: vertices (n, 3) float32, triangles (m, 3) uint32 (prv_mesh_from_arrays)"""
+        v = np.ascontiguousarray(np.asarray(vertices, np.float32).reshape(-1, 3))
+        tr = np.ascontiguousarray(np.asarray(triangles, np.uint32).reshape(-1, 3))
+        h = C.c_void_p()
+        self._chk(self.lib.prv_mesh_from_arrays(self.handle, _ptr(v) if len(v) else None, len(v), _ptr(tr) if len(tr) else None, len(tr),
+                                                C.byref(h)))
+        return Mesh(self, h)
+
+    def mesh_depth(self, mesh, camset, view_ids, width, height):
+        """the nearest surface depth of `mesh` per pixel and view (prv_mesh_depth) -> float32 [n_views, h, w] on the device, 0 =
+        no triangle; pinhole cameras only"""
+        t = self.torch
+        ids = self._ids(camset, view_ids)
+        depth = t.empty((len(ids), int(height), int(width)), dtype=t.float32, device=self.device)
+        self._chk(self.lib.prv_mesh_depth(self.handle, mesh.handle, camset.handle, _ptr(ids), len(ids), int(width), int(height), _ptr(depth)))
+        return depth
+
+    def raster_stats(self):
+        """the last mesh_depth / mesh-occluded coverage call: (view, triangle) pairs rasterised, and those the large path took"""
+        out = (C.c_uint64 * 2)()
+        self._chk(self.lib.prv_debug_raster_stats(self.handle, out))
+        return dict(pairs=int(out[0]), large=int(out[1]))
 
     def mesh_stage_ms(self):
         """milliseconds of the last extraction's stages: density grid, classify + scans, emit, colours"""
@@ -666,6 +697,12 @@ class Mesh:
         self.colors = np.zeros((nv.value, 3), np.uint8)
         self.triangles = np.zeros((nt.value, 3), np.uint32)
         ctx._chk(ctx.lib.prv_mesh_get(handle, _ptr(self.vertices), _ptr(self.normals), _ptr(self.colors), _ptr(self.triangles)))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def counts(self):
         nv, nt = C.c_uint64(), C.c_uint64()
@@ -1331,16 +1368,17 @@ class Testbed:
             out[k] /= self.scale ** 2
         return out
 
-    def compute_coverage(self, reference_points, camset, chosen, width=None, height=None, point_size=1, depth_tol=0.02):
+    def compute_coverage(self, reference_points, camset, chosen, width=None, height=None, point_size=1, depth_tol=0.02, occluder=None):
         """how much of a reference surface the views `chosen` (camera ids of `camset`, in the order they were taken) see, against
         the greedy choice of as many views out of the WHOLE camset.  reference_points: (n, 3), dataset frame; the size defaults
-        to the camset's.  Needs no model: nothing is trained or rendered.
+        to the camset's.  Needs no model: nothing is trained or rendered.  occluder: a Mesh (ENGINE frame, as the library makes
+        them) whose rasterised surface occludes, not the points.
         -> dict(n_points, n_coverable, covered[k] cumulative, greedy_covered[k], greedy_chosen[k] camera ids)"""
         ref = np.asarray(reference_points, np.float64).reshape(-1, 3)
         w, h = camset.size
         chosen = [int(v) for v in chosen]
         with self.ctx.coverage(dataset_to_engine(ref, self.scale, self.offset).astype(np.float32), camset, None,
-                               int(width or w), int(height or h), point_size, depth_tol) as cov:
+                               int(width or w), int(height or h), point_size, depth_tol, occluder=occluder) as cov:
             info = cov.info()
             out = dict(n_points=info["n_points"], n_coverable=info["n_coverable"], covered=[], greedy_covered=[], greedy_chosen=[])
             if chosen:

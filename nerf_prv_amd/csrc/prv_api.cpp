@@ -23,6 +23,7 @@
 #include "prv_geom.hpp"
 #include "prv_select.hpp"
 #include "prv_coverage.hpp"
+#include "prv_raster.hpp"
 #include "prv_levels.hpp"
 #include "prv_ingp.hpp"
 #include "prv_train.hpp"
@@ -107,6 +108,7 @@ struct prv_ctx {
   std::vector<struct prv_mesh*> meshes;      // live meshes of this context (detached by prv_destroy)
   std::vector<struct prv_nn_index*> nn_indexes; // live nearest-neighbour indexes of this context (detached by prv_destroy)
   std::vector<struct prv_coverage*> coverages;  // live coverage handles of this context (detached by prv_destroy)
+  uint64_t raster_stats[2] = {0, 0};         // (view, triangle) pairs of the last rasterising call, and those its large path took (prv_debug_raster_stats)
   float mesh_ms[4] = {0, 0, 0, 0};           // stages of the last mesh extraction (prv_mesh_api.inc: prv_debug_mesh_stages)
   int queue_segments = 8; // ray-queue segments = XCDs (PRV_QUEUE_SEGMENTS: 1 = single shared head)
   int spatial_regions = 1; // a wave's records go to the region of its first live ray's octant (PRV_SPATIAL_REGIONS=0: block id % regions, rounds 1-5)
@@ -2292,4 +2294,5 @@ int prv_debug_field(prv_ctx* c, int slot, const float* pos, const float* dir, in
 #include "prv_mesh_api.inc"
 #include "prv_geom_api.inc"
 #include "prv_select_api.inc"
+#include "prv_raster_api.inc"
 #include "prv_coverage_api.inc"

@@ -41,20 +41,21 @@ int coverage_check_opts(prv_ctx* c, const prv_coverage_opts* o) {
   return PRV_OK;
 }
 
-// stages A and B, batch by batch, then the per-view counts and the union's
-int coverage_build(prv_ctx* c, prv_coverage* x, const float* xyz, const std::vector<CamDev>& cams, int W, int H, const prv_coverage_opts& o,
-                   float* depth_out) {
+// stages A and B, batch by batch, then the per-view counts and the union's.  occluder != nullptr: stage A rasterises that mesh
+// (prv_raster_api.inc) and stage B lets an empty pixel pass; nullptr: the points occlude each other
+int coverage_build(prv_ctx* c, prv_coverage* x, const float* xyz, const prv_mesh* occluder, const std::vector<CamDev>& cams, int W, int H,
+                   const prv_coverage_opts& o, float* depth_out) {
   int rc;
   const int V = x->n_views;
   const size_t npix = (size_t)W * (size_t)H;
-  size_t budget = kCoverageZBufBudget;
-  if (const char* e = getenv("PRV_COVERAGE_ZBUF_BYTES")) budget = (size_t)strtoull(e, nullptr, 10); // tests: several batches at a small size
-  const int per_batch = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)V, (size_t)kCoverageMaxBatch), budget / (npix * 4)));
+  const int per_batch = zbuf_views_per_batch(V, npix); // (PRV_COVERAGE_ZBUF_BYTES: several batches at a small size, for tests)
   struct Scratch {
     Buffer z;
     ~Scratch() { release(z); }
   } scratch;
+  RasterWork raster;
   if ((rc = ensure(c, scratch.z, (size_t)per_batch * npix * 4)) != PRV_OK) return rc;
+  if (occluder && (rc = raster_begin(c, raster, occluder, per_batch)) != PRV_OK) return rc;
   if ((rc = ensure(c, c->view_ids, (size_t)V * (sizeof(CamDev) + sizeof(int)))) != PRV_OK) return rc;
   HIPCHK(c, hipMemcpyAsync(c->view_ids.p, cams.data(), (size_t)V * sizeof(CamDev), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream)); // (the host vector may go away)
@@ -68,8 +69,13 @@ int coverage_build(prv_ctx* c, prv_coverage* x, const float* xyz, const std::vec
   for (int v0 = 0; v0 < V; v0 += per_batch) {
     const int nb = std::min(per_batch, V - v0);
     const CamDev* bc = (const CamDev*)c->view_ids.p + v0;
-    HIPCHK(c, launch_coverage_depth(xyz, (size_t)x->n, bc, nb, W, H, o.point_size, zbuf, c->stream));
-    HIPCHK(c, launch_coverage_visible(xyz, (size_t)x->n, bc, nb, W, H, zbuf, tol1, bits + (size_t)v0 * x->words, x->words, c->stream));
+    if (occluder) {
+      if ((rc = raster_fill(c, raster, occluder, bc, nb, W, H, zbuf)) != PRV_OK) return rc;
+      HIPCHK(c, launch_raster_visible(xyz, (size_t)x->n, bc, nb, W, H, zbuf, tol1, bits + (size_t)v0 * x->words, x->words, c->stream));
+    } else {
+      HIPCHK(c, launch_coverage_depth(xyz, (size_t)x->n, bc, nb, W, H, o.point_size, zbuf, c->stream));
+      HIPCHK(c, launch_coverage_visible(xyz, (size_t)x->n, bc, nb, W, H, zbuf, tol1, bits + (size_t)v0 * x->words, x->words, c->stream));
+    }
     if (depth_out) HIPCHK(c, launch_coverage_resolve(zbuf, (size_t)nb * npix, depth_out + (size_t)v0 * npix, c->stream));
   }
   // what each view sees on its own, and what any view sees
@@ -86,6 +92,34 @@ int coverage_build(prv_ctx* c, prv_coverage* x, const float* xyz, const std::vec
   HIPCHK(c, hipMemcpyAsync(&any, gain, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   x->n_coverable = (uint64_t)any;
+  return occluder ? raster_end(c, raster) : PRV_OK;
+}
+
+// prv_coverage_create and prv_coverage_create_occluded: one body, the occluder checked by the caller
+int coverage_create(prv_ctx* c, const float* xyz, uint64_t n, const prv_mesh* occluder, const prv_camset* cs, const int* view_ids, int n_views,
+                    int width, int height, const prv_coverage_opts& o, float* depth_out, prv_coverage** out) {
+  int rc;
+  if (!cs || n_views < 1) return fail(c, PRV_E_INVALID, "bad camset / view count");
+  if (width < 1 || height < 1 || width > 16384 || height > 16384) return fail(c, PRV_E_INVALID, "bad image size %dx%d", width, height);
+  if (n > kCoverageMaxPoints) return fail(c, PRV_E_INVALID, "%llu points exceed 2^31", (unsigned long long)n);
+  if (n > 0 && !xyz) return fail(c, PRV_E_INVALID, "xyz_dev is NULL");
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((n > 0 && (rc = check_device_ptr(c, xyz, "xyz_dev")) != PRV_OK) || (rc = check_device_ptr(c, depth_out, "depth_out_dev")) != PRV_OK) return rc;
+  std::vector<CamDev> cams((size_t)n_views);
+  if ((rc = gather_cams(c, cs, view_ids, n_views, width, height, cams.data())) != PRV_OK) return rc;
+  if (occluder && (rc = raster_refuse_lenses(c, cams)) != PRV_OK) return rc;
+  std::unique_ptr<prv_coverage> x(new prv_coverage());
+  x->ctx = c;
+  x->n = n;
+  x->n_views = n_views;
+  x->words = (size_t)((n + 63) / 64);
+  if ((rc = coverage_build(c, x.get(), xyz, occluder, cams, width, height, o, depth_out)) != PRV_OK) {
+    (void)hipStreamSynchronize(c->stream);
+    x->free_all();
+    return rc;
+  }
+  c->coverages.push_back(x.get());
+  *out = x.release();
   return PRV_OK;
 }
 
@@ -110,27 +144,21 @@ int prv_coverage_create(prv_ctx* c, const float* xyz, uint64_t n, const prv_cams
   if ((rc = coverage_check_opts(c, &o)) != PRV_OK) return rc;
   if (!c) return fail(nullptr, PRV_E_INVALID, "the context is NULL");
   if (!out) return fail(c, PRV_E_INVALID, "out is NULL");
-  if (!cs || n_views < 1) return fail(c, PRV_E_INVALID, "bad camset / view count");
-  if (width < 1 || height < 1 || width > 16384 || height > 16384) return fail(c, PRV_E_INVALID, "bad image size %dx%d", width, height);
-  if (n > kCoverageMaxPoints) return fail(c, PRV_E_INVALID, "%llu points exceed 2^31", (unsigned long long)n);
-  if (n > 0 && !xyz) return fail(c, PRV_E_INVALID, "xyz_dev is NULL");
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((n > 0 && (rc = check_device_ptr(c, xyz, "xyz_dev")) != PRV_OK) || (rc = check_device_ptr(c, depth_out, "depth_out_dev")) != PRV_OK) return rc;
-  std::vector<CamDev> cams((size_t)n_views);
-  if ((rc = gather_cams(c, cs, view_ids, n_views, width, height, cams.data())) != PRV_OK) return rc;
-  std::unique_ptr<prv_coverage> x(new prv_coverage());
-  x->ctx = c;
-  x->n = n;
-  x->n_views = n_views;
-  x->words = (size_t)((n + 63) / 64);
-  if ((rc = coverage_build(c, x.get(), xyz, cams, width, height, o, depth_out)) != PRV_OK) {
-    (void)hipStreamSynchronize(c->stream);
-    x->free_all();
-    return rc;
-  }
-  c->coverages.push_back(x.get());
-  *out = x.release();
-  return PRV_OK;
+  return coverage_create(c, xyz, n, nullptr, cs, view_ids, n_views, width, height, o, depth_out, out);
+} catch (...) { return caught(c); }
+
+int prv_coverage_create_occluded(prv_ctx* c, const float* xyz, uint64_t n, const prv_mesh* occluder, const prv_camset* cs, const int* view_ids,
+                                 int n_views, int width, int height, const prv_coverage_opts* opts, float* depth_out, prv_coverage** out) try {
+  if (out) *out = nullptr;
+  prv_coverage_opts o;
+  prv_coverage_default_opts(&o);
+  if (opts) o.depth_tol = opts->depth_tol; // (point_size is ignored: no point is splatted)
+  int rc;
+  if ((rc = coverage_check_opts(c, &o)) != PRV_OK) return rc;
+  if (!c) return fail(nullptr, PRV_E_INVALID, "the context is NULL");
+  if (!out) return fail(c, PRV_E_INVALID, "out is NULL");
+  if ((rc = raster_check_mesh(c, occluder, "occluder")) != PRV_OK) return rc;
+  return coverage_create(c, xyz, n, occluder, cs, view_ids, n_views, width, height, o, depth_out, out);
 } catch (...) { return caught(c); }
 
 int prv_coverage_info(const prv_coverage* x, uint64_t* n_points, int* n_views, uint64_t* n_coverable) {

@@ -455,8 +455,10 @@ struct PlannerEngine {
     DeviceArray<float> points;
     uint64_t n = 0;
     NnIndexPtr index;
+    MeshPtr mesh; // the ground-truth mesh, kept from geometry_setup to coverage_setup when `coverage_occluder: mesh` asks for it
     double scale = 1.0, size = 0.1; // engine units per dataset unit (the json's scale); the object size
     void drop() {
+      mesh.reset();
       index.reset();
       points.reset();
       n = 0;
@@ -516,6 +518,7 @@ struct PlannerEngine {
       geom_ref.n = cfg.geom.samples;
       if (rc == PRV_OK) rc = geom_ref.points.alloc(ctx, geom_ref.n * 12);
       if (rc == PRV_OK) rc = prv_mesh_sample(m.get(), geom_ref.n, 1, geom_ref.points.get(), nullptr);
+      if (rc == PRV_OK && cfg.cover.mesh_occluder()) geom_ref.mesh = std::move(m); // coverage_setup rasterises it, then lets it go
       m.reset(); // (before the index is built and any echo, as ever)
     }
     if (rc == PRV_OK && cfg.geom.on) rc = prv_nn_index_create(ctx, geom_ref.points.get(), geom_ref.n, nullptr, out_arg(geom_ref.index));
@@ -591,8 +594,19 @@ struct PlannerEngine {
     co.point_size = cfg.cover.point_size;
     co.depth_tol = (float)cfg.cover.depth_tol;
     const int n = prv_camset_count(cams.get());
-    int rc = prv_coverage_create(ctx, geom_ref.points.get(), geom_ref.n, cams.get(), nullptr, n, cfg.cover.width > 0 ? cfg.cover.width : o.width,
-                                 cfg.cover.height > 0 ? cfg.cover.height : o.height, &co, nullptr, out_arg(cover.handle));
+    const int cw = cfg.cover.width > 0 ? cfg.cover.width : o.width, ch = cfg.cover.height > 0 ? cfg.cover.height : o.height;
+    int rc;
+    if (cfg.cover.mesh_occluder()) {
+      if (!geom_ref.mesh) {
+        std::cerr << "evaluate_coverage: coverage_occluder: mesh, and no ground-truth mesh was kept" << std::endl;
+        return PRV_E_STATE;
+      }
+      rc = prv_coverage_create_occluded(ctx, geom_ref.points.get(), geom_ref.n, geom_ref.mesh.get(), cams.get(), nullptr, n, cw, ch, &co, nullptr,
+                                        out_arg(cover.handle));
+      geom_ref.mesh.reset(); // the handle keeps the bit matrix and nothing else
+    } else {
+      rc = prv_coverage_create(ctx, geom_ref.points.get(), geom_ref.n, cams.get(), nullptr, n, cw, ch, &co, nullptr, out_arg(cover.handle));
+    }
     if (rc == PRV_OK) rc = prv_coverage_info(cover.handle.get(), &cover.n_points, &cover.n_views, &cover.n_coverable);
     if (rc != PRV_OK) {
       std::cerr << "evaluate_coverage: " << prv_last_error(ctx) << std::endl;
@@ -613,7 +627,8 @@ struct PlannerEngine {
       std::cerr << "evaluate_coverage: " << prv_last_error(ctx) << std::endl;
       return rc;
     }
-    return write_text(path, coverage_text(cover.n_points, cover.n_coverable, k, covered.back(), greedy[(size_t)std::min(k, cover.n_views) - 1])) ? PRV_OK : PRV_E_IO;
+    return write_text(path, coverage_text(cover.n_points, cover.n_coverable, k, covered.back(), greedy[(size_t)std::min(k, cover.n_views) - 1],
+                                          cfg.cover.mesh_occluder())) ? PRV_OK : PRV_E_IO;
   }
 
   // ================================================================================ selection and scoring

@@ -180,7 +180,7 @@ int PlanningJob::install_callbacks(const Vec3& center, double size) {
     lab->evaluator = [e, center, size](const std::string& scene, double* p, double* q) { return e->evaluate(scene, center, size, p, q); };
   }
   if (e->cfg.cover.on) { // a bad key of the coverage evaluation is reported before anything is set up or trained
-    const std::string problem = coverage_eval_problem(e->cfg.cover);
+    const std::string problem = coverage_eval_problem(e->cfg.cover, !e->cfg.geom.reference.empty());
     if (!problem.empty()) {
       std::cerr << "evaluate_coverage: " << problem << "; nothing was trained" << std::endl;
       return -85;
