@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PRV_ABI_VERSION 5 /* 2: prv_field_desc.per_level_scale; 3: prv_render_opts.step_mode, prv_stats.samples_live; 4: prv_train_opts.patch_w / patch_h; 5: prv_train_opts.step_mode / deterministic (still 5: prv_train_create accepting lr = 0, which it refused, changes no layout and no call that worked; nor do the prv_coverage_* entry points: additive; nor prv_mesh_from_arrays, prv_mesh_depth and prv_coverage_create_occluded: additive too) */
+#define PRV_ABI_VERSION 5 /* 2: prv_field_desc.per_level_scale; 3: prv_render_opts.step_mode, prv_stats.samples_live; 4: prv_train_opts.patch_w / patch_h; 5: prv_train_opts.step_mode / deterministic (still 5: prv_train_create accepting lr = 0, which it refused, changes no layout and no call that worked; nor do the prv_coverage_* entry points: additive; nor prv_mesh_from_arrays, prv_mesh_depth and prv_coverage_create_occluded: additive too; nor prv_debug_live_bytes) */
 
 /* error codes (0 = ok, < 0 = error; message via prv_last_error) */
 #define PRV_OK 0
@@ -911,6 +911,10 @@ int prv_debug_mesh_component_rounds(const prv_mesh* m, int* rounds);
 /* the last prv_mesh_depth / prv_coverage_create_occluded call: out[0] = (view, triangle) pairs rasterised, out[1] = those whose
  * clipped pixel box held more than small_max pixels (the large path took them) */
 int prv_debug_raster_stats(prv_ctx* ctx, uint64_t out[2]);
+/* bytes of device memory the library holds in this process: every context's workspaces and models, every handle's arrays,
+ * what destroyed trainers left parked.  Not prv_malloc's memory (the caller's).  Back where it was once everything a piece of
+ * work created has been destroyed. */
+uint64_t prv_debug_live_bytes(void);
 /* 32 fp16 features per position (bit patterns) */
 int prv_debug_encode(prv_ctx* ctx, int model_slot, const float* pos, int n, uint16_t* feat);
 /* per point: out[0]=sigma, out[1..3]=rgb, out[4..19]=density MLP outputs, out[20..35]=rgb MLP

@@ -216,6 +216,7 @@ SIGNATURES = {
     "prv_mesh_depth": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "prv_coverage_create_occluded": (_i, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, _i, _i, _i, _P(CoverageOpts), _vp, _P(_vp)]),
     "prv_debug_raster_stats": (_i, [_vp, _vp]),
+    "prv_debug_live_bytes": (C.c_uint64, []),
     "prv_score_ensemble_images": (_i, [_vp, _i, _vp, _i, _i, C.c_size_t, _vp]),
     "prv_score_psnr_images": (_i, [_vp, _vp, _vp, _i, C.c_size_t, _vp, _vp]),
     "prv_evaluate_images": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

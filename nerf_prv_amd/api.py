@@ -106,9 +106,43 @@ def _ptr(a):
     return C.c_void_p(a.data_ptr())
 
 
-class CamSet:
+class _Handle:
+    """what the library's objects share on this side: the context, the C handle, the call that destroys it, the error lookup"""
+    _destroy = None  # the C function that destroys the handle
+
     def __init__(self, ctx, handle):
         self.ctx, self.handle = ctx, handle
+
+    def _chk(self, rc):
+        """a failed call's error: the message is the context's, or the thread's if the handle or its context is gone (or the
+        context has none)"""
+        if rc != 0:
+            lib = self.ctx.lib
+            msg = (lib.prv_last_error(self.ctx.handle) if self.ctx.handle else None) or b""
+            if not (self.handle and msg) or rc == L.PRV_E_STATE:
+                msg = lib.prv_last_error(None) or msg
+            raise PrvError(rc, msg.decode())
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if getattr(self, "handle", None):
+            getattr(self.ctx.lib, self._destroy)(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CamSet(_Handle):
+    _destroy = "prv_camset_destroy"
 
     def __len__(self):
         return self.ctx.lib.prv_camset_count(self.handle)
@@ -133,17 +167,6 @@ class CamSet:
         if self.ctx.lib.prv_camset_lens(self.handle, i, _ptr(lens)) != 0:
             raise PrvError(L.PRV_E_INVALID, "camera index out of range")
         return lens
-
-    def close(self):
-        if self.handle:
-            self.ctx.lib.prv_camset_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Context:
@@ -684,12 +707,14 @@ def write_mesh(path, vertices, triangles, normals=None, colors=None, scale=1.0, 
         _mesh_file_error(rc)
 
 
-class Mesh:
+class Mesh(_Handle):
     """a marching-cubes mesh (engine frame) owned by the library; the arrays are host copies taken at construction:
     vertices / normals (n, 3) float32, colors (n, 3) uint8, triangles (m, 3) uint32 (counter-clockwise seen from outside)"""
 
+    _destroy = "prv_mesh_destroy"
+
     def __init__(self, ctx, handle):
-        self.ctx, self.handle = ctx, handle
+        super().__init__(ctx, handle)
         nv, nt = C.c_uint64(), C.c_uint64()
         ctx._chk(ctx.lib.prv_mesh_counts(handle, C.byref(nv), C.byref(nt)))
         self.vertices = np.zeros((nv.value, 3), np.float32)
@@ -697,12 +722,6 @@ class Mesh:
         self.colors = np.zeros((nv.value, 3), np.uint8)
         self.triangles = np.zeros((nt.value, 3), np.uint32)
         ctx._chk(ctx.lib.prv_mesh_get(handle, _ptr(self.vertices), _ptr(self.normals), _ptr(self.colors), _ptr(self.triangles)))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def counts(self):
         nv, nt = C.c_uint64(), C.c_uint64()
@@ -728,12 +747,6 @@ class Mesh:
         if rc != 0:
             raise PrvError(rc, (self.ctx.lib.prv_last_error(self.ctx.handle if self.ctx.handle else None) or b"").decode())
         return (xyz, tri) if want_triangles else xyz
-
-    def _chk(self, rc):
-        """a mesh call's error: the message is the context's, or the thread's if the handle or its context is gone"""
-        if rc != 0:
-            own = self.handle and self.ctx.handle and rc != L.PRV_E_STATE
-            raise PrvError(rc, (self.ctx.lib.prv_last_error(self.ctx.handle if own else None) or b"").decode())
 
     def components(self):
         """the mesh's connected components (prv_mesh_components; labelled once, cached by the library) -> dict of numpy
@@ -769,30 +782,10 @@ class Mesh:
         self._chk(self.ctx.lib.prv_mesh_filter(self.handle, C.byref(o), C.byref(h)))
         return Mesh(self.ctx, h)
 
-    def close(self):
-        if self.handle:
-            self.ctx.lib.prv_mesh_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class NNIndex:
+class NNIndex(_Handle):
     """a nearest-neighbour index owned by the library (prv_nn_index)"""
-
-    def __init__(self, ctx, handle):
-        self.ctx, self.handle = ctx, handle
-
-    def _chk(self, rc):
-        if rc != 0:
-            msg = self.ctx.lib.prv_last_error(self.ctx.handle if self.ctx.handle else None) or b""
-            if not msg or rc == L.PRV_E_STATE:
-                msg = self.ctx.lib.prv_last_error(None) or msg
-            raise PrvError(rc, msg.decode())
+    _destroy = "prv_nn_index_destroy"
 
     def query(self, points):
         """-> (d2 float32 (m,), ids int32 (m,)) device tensors: squared distance to and id of each point's nearest reference
@@ -815,32 +808,16 @@ class NNIndex:
         self._chk(self.ctx.lib.prv_debug_nn_tests(self.handle, C.byref(v)))
         return v.value
 
-    def close(self):
-        if self.handle:
-            self.ctx.lib.prv_nn_index_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Coverage:
+class Coverage(_Handle):
     """the visibility bit matrix of a cloud under a list of views, owned by the library (prv_coverage).  Views are named by
     their POSITION in the list the handle was made with"""
 
+    _destroy = "prv_coverage_destroy"
+
     def __init__(self, ctx, handle, depth=None):
-        self.ctx, self.handle, self.depth = ctx, handle, depth
-
-    _chk = NNIndex._chk
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        super().__init__(ctx, handle)
+        self.depth = depth
 
     def info(self):
         n, v, cov = C.c_uint64(), C.c_int(), C.c_uint64()
@@ -878,17 +855,6 @@ class Coverage:
         chosen, covered = np.zeros(max(k, 0), np.int32), np.zeros(max(k, 0), np.uint64)
         self._chk(self.ctx.lib.prv_coverage_greedy(self.handle, k, _ptr(chosen), _ptr(covered)))
         return chosen, covered
-
-    def close(self):
-        if self.handle:
-            self.ctx.lib.prv_coverage_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def write_image_depth(path, image, scale):
@@ -939,13 +905,14 @@ def dataset_to_engine(xyz, scale, offset):
     return q[:, [1, 2, 0]]
 
 
-class Comm:
+class Comm(_Handle):
     """the ranks of one job as the C ABI sees them (include/prv.h, "several GPUs"): RCCL on device buffers, or the
     host-staged socket transport for ranks that share a GPU"""
 
+    _destroy = "prv_comm_destroy"
+
     def __init__(self, ctx, rank, world, transport=None, rendezvous=None):
-        self.ctx = ctx
-        self.handle = C.c_void_p()
+        super().__init__(ctx, C.c_void_p())
         ctx._chk(ctx.lib.prv_comm_create(ctx.handle, int(rank), int(world), transport.encode() if transport else None,
                                          rendezvous.encode() if rendezvous else None, C.byref(self.handle)))
         self.rank, self.world = int(rank), int(world)
@@ -988,17 +955,6 @@ class Comm:
     def exchange_models(self, n_members, desc):
         """member e trained in slot e of rank e % world -> slot e of every rank (device to device)"""
         self.ctx._chk(self.ctx.lib.prv_model_exchange(self.ctx.handle, self.handle, int(n_members), C.byref(desc)))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.ctx.lib.prv_comm_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def shard_views(n_views, rank, world, interleaved=False):
@@ -1048,12 +1004,15 @@ def train_opts(**kw):
     return o
 
 
-class Trainer:
+class Trainer(_Handle):
     """the in-process training step on one model slot (include/prv.h, training section)"""
+
+    _destroy = "prv_train_destroy"
 
     def __init__(self, ctx, slot, camset, images_u8, opts=None):
         t = ctx.torch
-        self.ctx, self.slot, self.camset = ctx, slot, camset
+        super().__init__(ctx, None)
+        self.slot, self.camset = slot, camset
         self.images = images_u8.to(device=ctx.device, dtype=t.uint8).contiguous()  # kept alive here
         n, h, w, ch = self.images.shape
         if ch != 4 or n != len(camset):
@@ -1088,17 +1047,6 @@ class Trainer:
 
     def refresh_occupancy(self):
         self.ctx._chk(self.ctx.lib.prv_train_refresh_occupancy(self.handle))
-
-    def close(self):
-        if self.handle:
-            self.ctx.lib.prv_train_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def train_many(trainers, n):

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "prv_buffer.hpp"
 #include "prv_json.hpp"
 #include "prv_kernels.hpp"
 #include "prv_mesh.hpp"
@@ -38,11 +39,6 @@ thread_local std::string g_create_error;
 std::atomic<int> g_live_contexts{0};        // prv_runtime_shutdown refuses while a context is alive
 std::atomic<unsigned long long> g_devices_used{0}; // bit d: a context was created on device d
 std::atomic<bool> g_rccl_loaded{false};            // librccl was dlopen'ed by a communicator: it stays loaded for the process
-
-struct Buffer {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
 
 struct Model {
   bool loaded = false;
@@ -66,11 +62,7 @@ struct prv_camset {
   bool dataset = false; // intrinsics are the dataset's (own principal point, fl_y, lens), not fov-at-centre
 };
 
-static void train_detach_all(struct prv_ctx* c);
-static void comm_detach_all(struct prv_ctx* c);
-static void mesh_detach_all(struct prv_ctx* c);
-static void nn_detach_all(struct prv_ctx* c);
-static void coverage_detach_all(struct prv_ctx* c);
+using prv_handle = prv::Handle<struct prv_ctx>; // trainers, communicators, meshes, nearest-neighbour indexes, coverage handles
 
 struct prv_ctx {
   int device = 0;
@@ -79,8 +71,7 @@ struct prv_ctx {
   hipStream_t stream = nullptr;
   std::vector<hipStream_t> idle_queues; // streams with a hardware queue of their own, parked by destroyed trainers (prv_train_api.inc)
   hipStream_t capture_stream = nullptr; // the trainers' step graphs are captured on it (non-blocking; nothing ever runs on it)
-  std::vector<Buffer> idle_buffers;     // ... and their device buffers, taken again by size (train_buffer)
-  size_t idle_bytes = 0;
+  BufferPool parked;                    // ... and their device buffers, taken again by size (train_buffer)
   std::string err;
   Model models[PRV_MAX_SLOTS];
   // grow-only workspaces
@@ -103,11 +94,7 @@ struct prv_ctx {
   hipEvent_t pin_ev = nullptr; // recorded after the upload: the staging is rewritten only once that copy has run
   int blocks_per_cu = -1; // persistent render blocks per CU (PRV_BLOCKS_PER_CU); -1 = by table and image size, see render_blocks
   int cell_cache = -1;    // render_queue64 per-lane corner cache (PRV_CELL_CACHE=0/1; -1 = by stepping rule and image size, see render_policy)
-  std::vector<struct prv_trainer*> trainers; // live trainers of this context (detached by prv_destroy)
-  std::vector<struct prv_comm*> comms;       // live communicators of this context (detached by prv_destroy)
-  std::vector<struct prv_mesh*> meshes;      // live meshes of this context (detached by prv_destroy)
-  std::vector<struct prv_nn_index*> nn_indexes; // live nearest-neighbour indexes of this context (detached by prv_destroy)
-  std::vector<struct prv_coverage*> coverages;  // live coverage handles of this context (detached by prv_destroy)
+  std::vector<prv_handle*> handles;          // the live handles of this context (made inert by prv_destroy)
   uint64_t raster_stats[2] = {0, 0};         // (view, triangle) pairs of the last rasterising call, and those its large path took (prv_debug_raster_stats)
   float mesh_ms[4] = {0, 0, 0, 0};           // stages of the last mesh extraction (prv_mesh_api.inc: prv_debug_mesh_stages)
   int queue_segments = 8; // ray-queue segments = XCDs (PRV_QUEUE_SEGMENTS: 1 = single shared head)
@@ -161,35 +148,18 @@ int caught(prv_ctx* c) noexcept {
     if (e__ != hipSuccess) return fail((c), PRV_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e__)); \
   } while (0)
 
-void release(Buffer& b);
-int ensure(prv_ctx* c, Buffer& b, size_t bytes) {
-  if (b.bytes >= bytes && b.p) return PRV_OK;
-  if (b.p) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipFree(b.p));
-    b.p = nullptr;
-    b.bytes = 0;
-  }
-  hipError_t e = hipMalloc(&b.p, bytes);
-  if (e == hipErrorOutOfMemory && !c->idle_buffers.empty()) {
-    // the context's own parked memory (destroyed trainers' buffers, up to 16 GiB: prv_train_api.inc) goes before anybody fails
-    (void)hipGetLastError();
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (Buffer& idle : c->idle_buffers) release(idle);
-    c->idle_buffers.clear();
-    c->idle_bytes = 0;
-    e = hipMalloc(&b.p, bytes);
-  }
-  if (e != hipSuccess) b.p = nullptr;
-  HIPCHK(c, e);
-  b.bytes = bytes;
+int ensure(prv_ctx* c, Buffer& b, size_t bytes) { // (prv_buffer.hpp has the contract)
+  const char* call = "";
+  const hipError_t e = prv::ensure(b, bytes, c->stream, c->parked, &call);
+  if (e != hipSuccess) return fail(c, PRV_E_HIP, "%s failed: %s", call, hipGetErrorString(e));
   return PRV_OK;
 }
 
-void release(Buffer& b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
+// the first check of every entry point that takes a mesh, an index or a coverage handle
+int handle_alive(const prv_handle* h, const char* name, const char* the_name) {
+  if (!h) return fail(nullptr, PRV_E_INVALID, "%s is NULL", name);
+  if (!h->ctx) return fail(nullptr, PRV_E_STATE, "%s's context has been destroyed", the_name);
+  return PRV_OK;
 }
 
 static_assert(kMaxFieldLevels == kMaxLevels, "level tables of the host and the kernels must agree");
@@ -1025,7 +995,7 @@ int render_ensemble_ngp(prv_ctx* c, const int* slots, int E, const prv_camset* c
                         (s_stride * (size_t)E > c->stage.bytes ? s_stride * (size_t)E - c->stage.bytes : 0);
     size_t free_b = 0, total_b = 0;
     // (the context's parked trainer buffers count as free: ensure() releases them before an allocation fails)
-    if (grow && (hipMemGetInfo(&free_b, &total_b) != hipSuccess || grow + ((size_t)2 << 30) > free_b + c->idle_bytes)) return PRV_OK;
+    if (grow && (hipMemGetInfo(&free_b, &total_b) != hipSuccess || grow + ((size_t)2 << 30) > free_b + c->parked.bytes)) return PRV_OK;
   }
 
   // the members' union box: clip range and cull rectangles (conservative for every member)
@@ -1183,49 +1153,33 @@ int prv_create(prv_ctx** out, int device_id) try {
   return PRV_OK;
 } catch (...) { return caught(nullptr); }
 
+// The end of a context, in the one order that is safe:
+//   1. its device is current and its stream has run dry;
+//   2. its handles give up what they hold and become inert (a trainer's stream is synchronised by its own detach);
+//   3. what destroyed trainers left with the context goes: parked queues, the capture stream, parked buffers;
+//   4. events, the pinned staging and the stream are destroyed;
+//   5. `delete c` frees every workspace and every model's arrays (Buffer's destructor: nothing here names them);
+//   6. only then is the context no longer counted as alive -- prv_runtime_shutdown resets a device only when no context
+//      is, so it can never reset one under a pending free.
 void prv_destroy(prv_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
-  train_detach_all(c); // trainers outliving their context become inert handles
-  comm_detach_all(c);  // ... and so do communicators
-  mesh_detach_all(c);  // ... and meshes
-  nn_detach_all(c);    // ... and nearest-neighbour indexes
-  coverage_detach_all(c); // ... and coverage handles
+  detach_handles(c);
+  for (hipStream_t q : c->idle_queues) (void)hipStreamDestroy(q);
+  if (c->capture_stream) (void)hipStreamDestroy(c->capture_stream);
+  c->parked.clear();
   for (hipEvent_t e : c->ev_render) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_march) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_free) (void)hipEventDestroy(e);
-  for (auto& m : c->models) {
-    release(m.table);
-    release(m.phys);
-    release(m.occ_coarse);
-    release(m.occ);
-    release(m.frags);
-    release(m.frags64);
-    release(m.mlp);
-  }
-  release(c->queue);
-  release(c->queue_ext);
-  release(c->stage);
-  release(c->stage_depth);
-  release(c->stage_foot);
-  release(c->stage_hit);
-  release(c->stage_bins);
-  release(c->term_planes);
-  for (Buffer* b : {&c->sel_planes, &c->sel_voxel, &c->sel_q, &c->sel_bits, &c->sel_sums}) release(*b);
-  release(c->counters);
   if (c->pin) (void)hipHostFree(c->pin);
   if (c->pin_ev) (void)hipEventDestroy(c->pin_ev);
-  release(c->view_ids);
-  release(c->img_f32);
-  release(c->partial);
-  release(c->records);
-  for (auto& b : c->dbg) release(b);
-  for (auto& b : c->img_u8) release(b);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
   g_live_contexts.fetch_sub(1);
 }
+
+uint64_t prv_debug_live_bytes(void) { return g_live_buffer_bytes.load(); }
 
 int prv_runtime_shutdown(void) {
   if (g_live_contexts.load() != 0) {

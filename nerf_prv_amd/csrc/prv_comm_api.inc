@@ -17,8 +17,19 @@
 
 #include "prv_star.hpp"
 
-struct prv_comm {
-  prv_ctx* ctx = nullptr;
+// a communicator that outlives its context (interpreter shutdown order) becomes an inert handle: every entry point
+// checks ctx, prv_comm_destroy then only frees host memory
+struct prv_comm : prv_handle {
+  using prv_handle::prv_handle;
+  ~prv_comm() override {
+    if (ctx) detach();
+  }
+  void detach() override {
+    if (nccl && CommDestroy) (void)CommDestroy(nccl);
+    nccl = nullptr;
+    send.reset();
+    recv.reset();
+  }
   int rank = 0, world = 1;
   bool rccl = false;
   prvstar::Star star;
@@ -39,19 +50,6 @@ struct prv_comm {
   std::vector<prv_score_record> host_records; // ... and its host end (grows with them)
   std::vector<uint8_t> host_a, host_b; // socket transport staging
 };
-
-// a communicator that outlives its context (interpreter shutdown order) becomes an inert handle: every entry point
-// checks ctx, prv_comm_destroy then only frees host memory
-static void comm_detach_all(prv_ctx* c) {
-  for (prv_comm* cm : c->comms) {
-    if (cm->nccl && cm->CommDestroy) (void)cm->CommDestroy(cm->nccl);
-    cm->nccl = nullptr;
-    release(cm->send);
-    release(cm->recv);
-    cm->ctx = nullptr;
-  }
-  c->comms.clear();
-}
 
 namespace {
 
@@ -180,8 +178,7 @@ int prv_comm_create(prv_ctx* c, int rank, int world, const char* transport, cons
   if (world < 1 || rank < 0 || rank >= world) return fail(c, PRV_E_INVALID, "rank %d / world %d make no sense", rank, world);
   std::string tr = transport && *transport ? transport : (getenv("PRV_COMM") ? getenv("PRV_COMM") : "rccl");
   if (tr != "rccl" && tr != "socket") return fail(c, PRV_E_INVALID, "unknown transport '%s' (rccl | socket)", tr.c_str());
-  std::unique_ptr<prv_comm> cm(new prv_comm());
-  cm->ctx = c;
+  std::unique_ptr<prv_comm> cm(new prv_comm(c));
   cm->rank = rank;
   cm->world = world;
   cm->rccl = tr == "rccl";
@@ -224,25 +221,12 @@ int prv_comm_create(prv_ctx* c, int rank, int world, const char* transport, cons
     if (!cm->star.broadcast(&id, sizeof(id), 0)) return fail(c, PRV_E_IO, "rendezvous: %s", cm->star.error.c_str());
     NCCLCHK(cm.get(), cm->CommInitRank(&cm->nccl, world, id, rank));
   }
-  c->comms.push_back(cm.get());
   *out = cm.release();
   return PRV_OK;
 } catch (...) { return caught(c); }
 
-void prv_comm_destroy(prv_comm* cm) {
-  if (!cm) return;
-  if (cm->ctx) {
-    auto& v = cm->ctx->comms;
-    v.erase(std::remove(v.begin(), v.end(), cm), v.end());
-    (void)hipSetDevice(cm->ctx->device);
-    (void)hipStreamSynchronize(cm->ctx->stream);
-    if (cm->nccl && cm->CommDestroy) (void)cm->CommDestroy(cm->nccl);
-    release(cm->send);
-    release(cm->recv);
-  }
-  // librccl stays loaded: unloading a library that owns device state at exit is asking for trouble
-  delete cm;
-}
+// (librccl stays loaded: unloading a library that owns device state at exit is asking for trouble)
+void prv_comm_destroy(prv_comm* cm) { destroy_handle(cm); }
 
 int prv_comm_rank(const prv_comm* cm) { return cm ? cm->rank : PRV_E_INVALID; }
 int prv_comm_world(const prv_comm* cm) { return cm ? cm->world : PRV_E_INVALID; }
@@ -323,11 +307,7 @@ int prv_score_views_sharded(prv_ctx* c, prv_comm* cm, int method, const int* mod
       for (int r = 0; r < world; r++)
         if (!ok[(size_t)r]) rc = fail(c, PRV_E_STATE, "rank %d could not allocate its buffers for the round", r);
   }
-  if (rc != PRV_OK) {
-    release(local_send);
-    release(local_recv);
-    return rc;
-  }
+  if (rc != PRV_OK) return rc;
   hipError_t e = hipMemsetAsync(send.p, 0, (size_t)per * sizeof(prv_score_record), c->stream); // padding slots of a ragged shard
   if (e != hipSuccess) rc = fail(c, PRV_E_HIP, "memset: %s", hipGetErrorString(e));
   if (rc == PRV_OK)
@@ -345,8 +325,6 @@ int prv_score_views_sharded(prv_ctx* c, prv_comm* cm, int method, const int* mod
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) rc = fail(c, PRV_E_HIP, "record copy: %s", hipGetErrorString(e));
   }
-  release(local_send);
-  release(local_recv);
   if (shard_rc != PRV_OK) {
     c->err = shard_err; // this rank's own failure is the message its caller wants
     return shard_rc;

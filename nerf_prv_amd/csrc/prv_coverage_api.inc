@@ -1,7 +1,10 @@
 // prv_coverage_api.inc -- C ABI of the surface coverage stage (prv_coverage.hip); compiled as part of prv_api.cpp
 
-struct prv_coverage {
-  prv_ctx* ctx = nullptr; // nullptr: the context was destroyed, the handle is inert
+struct prv_coverage : prv_handle {
+  using prv_handle::prv_handle;
+  void detach() override {
+    for (Buffer* b : {&bits, &covered, &gain, &done}) b->reset();
+  }
   uint64_t n = 0;         // points
   int n_views = 0;
   size_t words = 0;       // ceil(n / 64): words per view
@@ -11,24 +14,9 @@ struct prv_coverage {
   Buffer done;            // uint32 per view
   std::vector<uint64_t> visible; // points each view sees on its own
   uint64_t n_coverable = 0;      // points at least one view sees
-  void free_all() {
-    for (Buffer* b : {&bits, &covered, &gain, &done}) release(*b);
-  }
 };
 
-static void coverage_detach_all(prv_ctx* c) {
-  for (prv_coverage* x : c->coverages) {
-    x->free_all();
-    x->ctx = nullptr;
-  }
-  c->coverages.clear();
-}
-
-static int coverage_alive(const prv_coverage* x) {
-  if (!x) return fail(nullptr, PRV_E_INVALID, "the coverage handle is NULL");
-  if (!x->ctx) return fail(nullptr, PRV_E_STATE, "the coverage handle's context has been destroyed");
-  return PRV_OK;
-}
+static int coverage_alive(const prv_coverage* x) { return handle_alive(x, "the coverage handle", "the coverage handle"); }
 
 namespace {
 
@@ -49,12 +37,9 @@ int coverage_build(prv_ctx* c, prv_coverage* x, const float* xyz, const prv_mesh
   const int V = x->n_views;
   const size_t npix = (size_t)W * (size_t)H;
   const int per_batch = zbuf_views_per_batch(V, npix); // (PRV_COVERAGE_ZBUF_BYTES: several batches at a small size, for tests)
-  struct Scratch {
-    Buffer z;
-    ~Scratch() { release(z); }
-  } scratch;
+  Buffer z;
   RasterWork raster;
-  if ((rc = ensure(c, scratch.z, (size_t)per_batch * npix * 4)) != PRV_OK) return rc;
+  if ((rc = ensure(c, z, (size_t)per_batch * npix * 4)) != PRV_OK) return rc;
   if (occluder && (rc = raster_begin(c, raster, occluder, per_batch)) != PRV_OK) return rc;
   if ((rc = ensure(c, c->view_ids, (size_t)V * (sizeof(CamDev) + sizeof(int)))) != PRV_OK) return rc;
   HIPCHK(c, hipMemcpyAsync(c->view_ids.p, cams.data(), (size_t)V * sizeof(CamDev), hipMemcpyHostToDevice, c->stream));
@@ -64,7 +49,7 @@ int coverage_build(prv_ctx* c, prv_coverage* x, const float* xyz, const prv_mesh
   }
   if ((rc = ensure(c, x->gain, (size_t)V * 8)) != PRV_OK || (rc = ensure(c, x->done, (size_t)V * 4)) != PRV_OK) return rc;
   const float tol1 = 1.0f + o.depth_tol; // formed once, in float32
-  uint32_t* zbuf = (uint32_t*)scratch.z.p;
+  uint32_t* zbuf = (uint32_t*)z.p;
   unsigned long long* bits = (unsigned long long*)x->bits.p;
   for (int v0 = 0; v0 < V; v0 += per_batch) {
     const int nb = std::min(per_batch, V - v0);
@@ -108,17 +93,14 @@ int coverage_create(prv_ctx* c, const float* xyz, uint64_t n, const prv_mesh* oc
   std::vector<CamDev> cams((size_t)n_views);
   if ((rc = gather_cams(c, cs, view_ids, n_views, width, height, cams.data())) != PRV_OK) return rc;
   if (occluder && (rc = raster_refuse_lenses(c, cams)) != PRV_OK) return rc;
-  std::unique_ptr<prv_coverage> x(new prv_coverage());
-  x->ctx = c;
+  std::unique_ptr<prv_coverage> x(new prv_coverage(c));
   x->n = n;
   x->n_views = n_views;
   x->words = (size_t)((n + 63) / 64);
   if ((rc = coverage_build(c, x.get(), xyz, occluder, cams, width, height, o, depth_out)) != PRV_OK) {
-    (void)hipStreamSynchronize(c->stream);
-    x->free_all();
+    (void)hipStreamSynchronize(c->stream); // (before the handle's buffers go)
     return rc;
   }
-  c->coverages.push_back(x.get());
   *out = x.release();
   return PRV_OK;
 }
@@ -263,15 +245,6 @@ int prv_coverage_greedy(prv_coverage* x, int k, int* chosen_out, uint64_t* cover
   return PRV_OK;
 } catch (...) { return caught(x && x->ctx ? x->ctx : nullptr); }
 
-void prv_coverage_destroy(prv_coverage* x) {
-  if (!x) return;
-  if (prv_ctx* c = x->ctx) {
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    x->free_all();
-    c->coverages.erase(std::remove(c->coverages.begin(), c->coverages.end(), x), c->coverages.end());
-  }
-  delete x;
-}
+void prv_coverage_destroy(prv_coverage* x) { destroy_handle(x); }
 
 } // extern "C"

@@ -17,15 +17,7 @@ struct NNSet { // a binned (grid) or packed (brute force) reference set
 
 struct NNWork { // per-call scratch, kept by its owner between calls (grow-only)
   Buffer box, keys, count, rec, scan, misc;
-  void free_all() {
-    for (Buffer* b : {&box, &keys, &count, &rec, &scan, &misc}) release(*b);
-  }
 };
-
-void nn_set_release(NNSet& s) {
-  release(s.rec);
-  release(s.cell_end);
-}
 
 // finite coordinates (PRV_E_INVALID otherwise) and, with box, the points' bounding box; synchronises
 int nn_validate(prv_ctx* c, NNWork& w, const float* xyz, uint64_t n, const char* what, float box[6]) {
@@ -176,27 +168,18 @@ int geom_points_arg(prv_ctx* c, const float* p, uint64_t n, const char* what) {
 
 } // namespace
 
-struct prv_nn_index {
-  prv_ctx* ctx = nullptr; // nullptr: the context was destroyed, the handle is inert
+struct prv_nn_index : prv_handle {
+  using prv_handle::prv_handle;
+  void detach() override {
+    set = NNSet{};
+    work = NNWork{};
+  }
   NNSet set;
   NNWork work;
   uint64_t last_tests = 0;
 };
 
-static void nn_detach_all(prv_ctx* c) {
-  for (prv_nn_index* x : c->nn_indexes) {
-    nn_set_release(x->set);
-    x->work.free_all();
-    x->ctx = nullptr;
-  }
-  c->nn_indexes.clear();
-}
-
-static int nn_alive(const prv_nn_index* x) {
-  if (!x) return fail(nullptr, PRV_E_INVALID, "index is NULL");
-  if (!x->ctx) return fail(nullptr, PRV_E_STATE, "the index's context has been destroyed");
-  return PRV_OK;
-}
+static int nn_alive(const prv_nn_index* x) { return handle_alive(x, "index", "the index"); }
 
 static int geometry_metrics(prv_ctx* c, const float* rec, uint64_t n_rec, const float* ref, uint64_t n_ref, float tau, prv_nn_index* ref_index,
                             prv_geom_metrics* out) {
@@ -206,17 +189,10 @@ static int geometry_metrics(prv_ctx* c, const float* rec, uint64_t n_rec, const 
   int rc;
   if ((rc = geom_points_arg(c, rec, n_rec, "rec_xyz_dev")) != PRV_OK || (rc = geom_points_arg(c, ref, n_ref, "ref_xyz_dev")) != PRV_OK) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  struct Scratch {
+  struct {
     NNSet set;
     NNWork work;
     Buffer d2, ids, partial;
-    ~Scratch() {
-      nn_set_release(set);
-      work.free_all();
-      release(d2);
-      release(ids);
-      release(partial);
-    }
   } s;
   const uint64_t n_max = std::max(n_rec, n_ref);
   if ((rc = ensure(c, s.d2, n_max * 4)) != PRV_OK || (rc = ensure(c, s.ids, n_max * 4)) != PRV_OK ||
@@ -268,14 +244,6 @@ int prv_mesh_sample(const prv_mesh* m, uint64_t n, uint64_t seed, float* out_xyz
   if (m->nt == 0) return fail(c, PRV_E_STATE, "the mesh has no triangles: nothing to sample");
   HIPCHK(c, hipSetDevice(c->device));
   Buffer scan, scratch, total;
-  struct Guard {
-    Buffer *a, *b, *c;
-    ~Guard() {
-      release(*a);
-      release(*b);
-      release(*c);
-    }
-  } guard{&scan, &scratch, &total};
   if ((rc = ensure(c, scan, m->nt * 8)) != PRV_OK || (rc = ensure(c, scratch, mesh_scan_scratch(m->nt) * 8)) != PRV_OK ||
       (rc = ensure(c, total, 8)) != PRV_OK)
     return rc;
@@ -308,15 +276,9 @@ int prv_nn_index_create(prv_ctx* c, const float* xyz, uint64_t n, const prv_nn_o
   int rc;
   if ((rc = geom_points_arg(c, xyz, n, "xyz_dev")) != PRV_OK) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  std::unique_ptr<prv_nn_index> x(new prv_nn_index());
-  x->ctx = c;
-  if ((rc = nn_build(c, x->work, xyz, n, algorithm, x->set)) != PRV_OK) {
-    nn_set_release(x->set);
-    x->work.free_all();
-    return rc;
-  }
-  release(x->work.keys); // the build's point keys; a query sizes its own
-  c->nn_indexes.push_back(x.get());
+  std::unique_ptr<prv_nn_index> x(new prv_nn_index(c));
+  if ((rc = nn_build(c, x->work, xyz, n, algorithm, x->set)) != PRV_OK) return rc;
+  x->work.keys.reset(); // the build's point keys; a query sizes its own
   *out = x.release();
   return PRV_OK;
 } catch (...) { return caught(c); }
@@ -349,17 +311,7 @@ int prv_debug_nn_tests(const prv_nn_index* x, uint64_t* tests) {
   return PRV_OK;
 }
 
-void prv_nn_index_destroy(prv_nn_index* x) {
-  if (!x) return;
-  if (prv_ctx* c = x->ctx) {
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    nn_set_release(x->set);
-    x->work.free_all();
-    c->nn_indexes.erase(std::remove(c->nn_indexes.begin(), c->nn_indexes.end(), x), c->nn_indexes.end());
-  }
-  delete x;
-}
+void prv_nn_index_destroy(prv_nn_index* x) { destroy_handle(x); }
 
 int prv_geometry_metrics(prv_ctx* c, const float* rec, uint64_t n_rec, const float* ref, uint64_t n_ref, float tau,
                          prv_geom_metrics* out) try {

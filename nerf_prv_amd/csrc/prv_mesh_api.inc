@@ -1,8 +1,11 @@
 // prv_mesh_api.inc -- C ABI of mesh extraction (prv_mesh.hip); compiled as part of prv_api.cpp (shares its context types)
 #include <cctype>
 
-struct prv_mesh {
-  prv_ctx* ctx = nullptr; // nullptr: the context was destroyed, the handle is inert
+struct prv_mesh : prv_handle {
+  using prv_handle::prv_handle;
+  void detach() override {
+    for (Buffer* b : {&xyz, &nrm, &rgb, &tri, &vcomp, &tcomp}) b->reset();
+  }
   uint64_t nv = 0, nt = 0;
   bool colors = false;
   Buffer xyz, nrm, rgb, tri;
@@ -12,23 +15,6 @@ struct prv_mesh {
   Buffer vcomp, tcomp; // component id per vertex / per triangle
   std::vector<prv_mesh_component> comps;
 };
-
-static void mesh_release(prv_mesh* m) {
-  release(m->xyz);
-  release(m->nrm);
-  release(m->rgb);
-  release(m->tri);
-  release(m->vcomp);
-  release(m->tcomp);
-}
-
-static void mesh_detach_all(prv_ctx* c) {
-  for (prv_mesh* m : c->meshes) {
-    mesh_release(m);
-    m->ctx = nullptr;
-  }
-  c->meshes.clear();
-}
 
 namespace {
 
@@ -54,12 +40,11 @@ int mesh_grid(prv_ctx* c, const prv_mesh_opts* o, MeshGrid& g) {
   return PRV_OK;
 }
 
-struct MeshWork { // the extraction's scratch, released on every way out
+struct MeshWork { // the extraction's scratch and its events
   Buffer sigma, flags, cases, wave_v, wave_t, scratch, totals;
   // stage brackets: [0, 1] density grid, [1, 2] classify + scans, [3, 4] emit, [4, 5] colours (the readback sits in [2, 3])
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   ~MeshWork() {
-    for (Buffer* b : {&sigma, &flags, &cases, &wave_v, &wave_t, &scratch, &totals}) release(*b);
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
   }
@@ -83,17 +68,14 @@ int mesh_extract(prv_ctx* c, const float* sigma, const MeshGrid& g, float thr, c
   HIPCHK(c, hipMemcpyAsync(totals, tot, 16, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (totals[0] >= (1ull << 32)) return fail(c, PRV_E_INTERNAL, "%llu vertices do not fit 32-bit ids", (unsigned long long)totals[0]);
-  std::unique_ptr<prv_mesh> m(new prv_mesh());
-  m->ctx = c;
+  std::unique_ptr<prv_mesh> m(new prv_mesh(c)); // an early return below frees what it holds by then
   m->nv = totals[0];
   m->nt = totals[1];
   m->colors = fd != nullptr;
   if (m->nv > 0) {
     if ((rc = ensure(c, m->xyz, m->nv * 12)) != PRV_OK || (rc = ensure(c, m->nrm, m->nv * 12)) != PRV_OK ||
-        (fd && (rc = ensure(c, m->rgb, m->nv * 3)) != PRV_OK) || (rc = ensure(c, m->tri, std::max<uint64_t>(1, m->nt) * 12)) != PRV_OK) {
-      mesh_release(m.get());
+        (fd && (rc = ensure(c, m->rgb, m->nv * 3)) != PRV_OK) || (rc = ensure(c, m->tri, std::max<uint64_t>(1, m->nt) * 12)) != PRV_OK)
       return rc;
-    }
     HIPCHK(c, hipEventRecord(w.ev[3], c->stream));
     hipError_t e = launch_mesh_vertices(sigma, g, thr, (const uint8_t*)w.flags.p, (const uint64_t*)w.wave_v.p, (float*)m->xyz.p,
                                         (float*)m->nrm.p, c->stream);
@@ -104,10 +86,7 @@ int mesh_extract(prv_ctx* c, const float* sigma, const MeshGrid& g, float thr, c
     if (e == hipSuccess && fd) e = launch_mesh_colors(*fd, (const float*)m->xyz.p, (const float*)m->nrm.p, m->nv, (uint8_t*)m->rgb.p, c->stream);
     if (e == hipSuccess) e = hipEventRecord(w.ev[5], c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-      mesh_release(m.get());
-      return fail(c, PRV_E_HIP, "mesh emit failed: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(c, PRV_E_HIP, "mesh emit failed: %s", hipGetErrorString(e));
   } else {
     for (int k = 3; k < 6; k++) HIPCHK(c, hipEventRecord(w.ev[k], c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -117,7 +96,6 @@ int mesh_extract(prv_ctx* c, const float* sigma, const MeshGrid& g, float thr, c
   for (int k = 0; k < 4; k++)
     if (hipEventElapsedTime(&ms[k], w.ev[from[k]], w.ev[from[k] + 1]) != hipSuccess) (void)hipGetLastError();
   memcpy(c->mesh_ms, ms, sizeof(ms));
-  c->meshes.push_back(m.get());
   *out = m.release();
   return PRV_OK;
 }
@@ -127,18 +105,11 @@ int mesh_events(prv_ctx* c, MeshWork& w) {
   return PRV_OK;
 }
 
-int mesh_alive(const prv_mesh* m) {
-  if (!m) return fail(nullptr, PRV_E_INVALID, "mesh is NULL");
-  if (!m->ctx) return fail(nullptr, PRV_E_STATE, "the mesh's context has been destroyed");
-  return PRV_OK;
-}
+int mesh_alive(const prv_mesh* m) { return handle_alive(m, "mesh", "the mesh"); }
 
 // ---- connected components
-struct CompWork { // labelling / filter scratch, released on every way out
+struct CompWork { // labelling / filter scratch
   Buffer parent, wave_v, wave_t, scratch, misc, table, keep, vmap;
-  ~CompWork() {
-    for (Buffer* b : {&parent, &wave_v, &wave_t, &scratch, &misc, &table, &keep, &vmap}) release(*b);
-  }
 };
 
 float comp_key_float(uint32_t k) { // undoes the kernels' order-preserving image
@@ -507,8 +478,7 @@ int prv_mesh_filter(prv_mesh* m, const prv_mesh_filter_opts* o, prv_mesh** out) 
       nv += m->comps[i].n_vertices;
       nt += m->comps[i].n_triangles;
     }
-  std::unique_ptr<prv_mesh> f(new prv_mesh());
-  f->ctx = c;
+  std::unique_ptr<prv_mesh> f(new prv_mesh(c)); // an early return below frees what it holds by then
   f->nv = nv;
   f->nt = nt;
   f->colors = m->colors;
@@ -537,10 +507,8 @@ int prv_mesh_filter(prv_mesh* m, const prv_mesh_filter_opts* o, prv_mesh** out) 
       return fail(c, PRV_E_INTERNAL, "filter counts disagree: table %llu / %llu, scan %llu / %llu", (unsigned long long)nv, (unsigned long long)nt,
                   (unsigned long long)totals[0], (unsigned long long)totals[1]);
     if ((rc = ensure(c, f->xyz, nv * 12)) != PRV_OK || (rc = ensure(c, f->nrm, nv * 12)) != PRV_OK ||
-        (f->colors && (rc = ensure(c, f->rgb, nv * 3)) != PRV_OK) || (rc = ensure(c, f->tri, std::max<uint64_t>(1, nt) * 12)) != PRV_OK) {
-      mesh_release(f.get());
+        (f->colors && (rc = ensure(c, f->rgb, nv * 3)) != PRV_OK) || (rc = ensure(c, f->tri, std::max<uint64_t>(1, nt) * 12)) != PRV_OK)
       return rc;
-    }
     hipError_t e = launch_mesh_comp_gather_vertices((const uint32_t*)m->vcomp.p, m->nv, keep_dev, (const uint64_t*)w.wave_v.p, (const float*)m->xyz.p,
                                                     (const float*)m->nrm.p, f->colors ? (const uint8_t*)m->rgb.p : nullptr, (float*)f->xyz.p,
                                                     (float*)f->nrm.p, (uint8_t*)f->rgb.p, (uint32_t*)w.vmap.p, c->stream);
@@ -548,12 +516,8 @@ int prv_mesh_filter(prv_mesh* m, const prv_mesh_filter_opts* o, prv_mesh** out) 
       e = launch_mesh_comp_gather_triangles((const uint32_t*)m->tcomp.p, m->nt, keep_dev, (const uint64_t*)w.wave_t.p, (const uint32_t*)m->tri.p,
                                             (const uint32_t*)w.vmap.p, (uint32_t*)f->tri.p, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-      mesh_release(f.get());
-      return fail(c, PRV_E_HIP, "mesh filter failed: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(c, PRV_E_HIP, "mesh filter failed: %s", hipGetErrorString(e));
   }
-  c->meshes.push_back(f.get());
   *out = f.release();
   return PRV_OK;
 } catch (...) { return caught(m && m->ctx ? m->ctx : nullptr); }
@@ -567,15 +531,6 @@ int prv_debug_mesh_component_rounds(const prv_mesh* m, int* rounds) {
   return PRV_OK;
 }
 
-void prv_mesh_destroy(prv_mesh* m) {
-  if (!m) return;
-  if (prv_ctx* c = m->ctx) {
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    mesh_release(m);
-    c->meshes.erase(std::remove(c->meshes.begin(), c->meshes.end(), m), c->meshes.end());
-  }
-  delete m;
-}
+void prv_mesh_destroy(prv_mesh* m) { destroy_handle(m); }
 
 } // extern "C"

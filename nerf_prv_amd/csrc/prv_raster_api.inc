@@ -32,10 +32,6 @@ struct RasterWork {
   size_t capacity = 0;
   int small_max = kRasterSmallPixels;
   uint64_t pairs = 0; // (view, triangle) pairs rasterised so far
-  ~RasterWork() {
-    release(list);
-    release(counters);
-  }
 };
 
 int raster_begin(prv_ctx* c, RasterWork& w, const prv_mesh* m, int views_per_batch) {
@@ -99,29 +95,22 @@ int prv_mesh_from_arrays(prv_ctx* c, const float* xyz, uint64_t nv, const uint32
     if (tri[i] >= nv)
       return fail(c, PRV_E_INVALID, "triangle %llu: vertex id %u out of range (%llu vertices)", (unsigned long long)(i / 3), tri[i], (unsigned long long)nv);
   HIPCHK(c, hipSetDevice(c->device));
-  std::unique_ptr<prv_mesh> m(new prv_mesh());
-  m->ctx = c;
+  std::unique_ptr<prv_mesh> m(new prv_mesh(c)); // an early return below frees what it holds by then
   m->nv = nv;
   m->nt = nt;
   m->colors = false;
   if (nv > 0) { // (as the extraction allocates: nothing for a mesh without vertices, one triangle's room for one without triangles)
     int rc;
     if ((rc = ensure(c, m->xyz, nv * 12)) != PRV_OK || (rc = ensure(c, m->nrm, nv * 12)) != PRV_OK ||
-        (rc = ensure(c, m->tri, std::max<uint64_t>(1, nt) * 12)) != PRV_OK) {
-      mesh_release(m.get());
+        (rc = ensure(c, m->tri, std::max<uint64_t>(1, nt) * 12)) != PRV_OK)
       return rc;
-    }
     hipError_t e = hipMemcpyAsync(m->xyz.p, xyz, nv * 12, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(m->nrm.p, 0, nv * 12, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(m->tri.p, 0, std::max<uint64_t>(1, nt) * 12, c->stream);
     if (e == hipSuccess && nt > 0) e = hipMemcpyAsync(m->tri.p, tri, nt * 12, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // (the host arrays may go away)
-    if (e != hipSuccess) {
-      mesh_release(m.get());
-      return fail(c, PRV_E_HIP, "mesh upload failed: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(c, PRV_E_HIP, "mesh upload failed: %s", hipGetErrorString(e));
   }
-  c->meshes.push_back(m.get());
   *out = m.release();
   return PRV_OK;
 } catch (...) { return caught(c); }
@@ -140,16 +129,13 @@ int prv_mesh_depth(prv_ctx* c, const prv_mesh* m, const prv_camset* cs, const in
   if ((rc = gather_cams(c, cs, view_ids, n_views, width, height, cams.data())) != PRV_OK || (rc = raster_refuse_lenses(c, cams)) != PRV_OK) return rc;
   const size_t npix = (size_t)width * (size_t)height;
   const int per_batch = zbuf_views_per_batch(n_views, npix);
-  struct Scratch {
-    Buffer z;
-    ~Scratch() { release(z); }
-  } scratch;
+  Buffer z;
   RasterWork w;
-  if ((rc = ensure(c, scratch.z, (size_t)per_batch * npix * 4)) != PRV_OK || (rc = raster_begin(c, w, m, per_batch)) != PRV_OK) return rc;
+  if ((rc = ensure(c, z, (size_t)per_batch * npix * 4)) != PRV_OK || (rc = raster_begin(c, w, m, per_batch)) != PRV_OK) return rc;
   if ((rc = ensure(c, c->view_ids, (size_t)n_views * (sizeof(CamDev) + sizeof(int)))) != PRV_OK) return rc;
   HIPCHK(c, hipMemcpyAsync(c->view_ids.p, cams.data(), (size_t)n_views * sizeof(CamDev), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream)); // (the host vector may go away)
-  uint32_t* zbuf = (uint32_t*)scratch.z.p;
+  uint32_t* zbuf = (uint32_t*)z.p;
   for (int v0 = 0; v0 < n_views; v0 += per_batch) {
     const int nb = std::min(per_batch, n_views - v0);
     if ((rc = raster_fill(c, w, m, (const CamDev*)c->view_ids.p + v0, nb, width, height, zbuf)) != PRV_OK) break;

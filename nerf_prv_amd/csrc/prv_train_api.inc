@@ -1,7 +1,11 @@
 // prv_train_api.inc -- C ABI of the training step; compiled as part of prv_api.cpp (shares its context types)
 
-struct prv_trainer {
-  prv_ctx* ctx = nullptr;
+struct prv_trainer : prv_handle {
+  using prv_handle::prv_handle;
+  ~prv_trainer() override { close(); }
+  void close();             // the step graphs and the stream go
+  void detach() override;   // the context goes first
+  void retire() override;   // destroyed under a live context: the stream and the buffers are parked there
   int slot = 0;
   prv_field_desc desc{};
   uint64_t generation = 0; // the slot's parameter generation this trainer's masters were widened from
@@ -29,6 +33,10 @@ struct prv_trainer {
   bool side_by_side = false; // this call steps several trainers (prv_train_steps_multi): one backward block per CU (bwd_blocks)
   int graph_bwd_blocks[2] = {0, 0}; // the backward block count each captured step graph was recorded with
   bool patch_ray_jitter = false; // dev only (PRV_TRAIN_PATCH_JITTER=ray at creation): every ray of a patch its own jitter; the oracle has no such mode
+  std::vector<Buffer*> buffers() {
+    return {&cams, &tab_wmv, &tab_g, &mlp_w, &mlp_m, &mlp_v, &mlp_g, &mlp_f, &ema, &rays, &samples, &logits, &seeds, &ray_loss, &ray_used,
+            &scal, &losses, &dw_part, &loss_part, &frags, &act, &slot_of, &frag_pos, &tab_gq, &block_tot, &tile_live};
+  }
 };
 
 namespace {
@@ -335,66 +343,36 @@ int train_finish(prv_trainer* t, int n_steps, float* losses_host) {
 // has to start at zero).
 static int train_buffer(prv_ctx* c, Buffer& b, size_t bytes) {
   if (b.p && b.bytes >= bytes) return PRV_OK;
-  if (!b.p)
-    for (size_t i = 0; i < c->idle_buffers.size(); i++)
-      if (c->idle_buffers[i].bytes == bytes) {
-        b = c->idle_buffers[i];
-        c->idle_bytes -= b.bytes;
-        c->idle_buffers.erase(c->idle_buffers.begin() + (long)i);
-        return PRV_OK;
-      }
+  if (!b.p && c->parked.take(b, bytes)) return PRV_OK;
   return ensure(c, b, bytes);
-}
-
-// park: the trainer's stream (idle by now) stays with the context for the next trainer -- creating a stream with a queue of its
-// own takes 11 ms, and the planner loop creates five trainers per round
-void train_release(prv_trainer* t, bool park = false) {
-  for (hipGraphExec_t& g : t->step_graph) {
-    if (g) (void)hipGraphExecDestroy(g);
-    g = nullptr;
-  }
-  if (t->stream && park && t->own_queue && t->ctx && t->ctx->idle_queues.size() < 16) t->ctx->idle_queues.push_back(t->stream);
-  else if (t->stream) (void)hipStreamDestroy(t->stream);
-  t->stream = nullptr;
-  Buffer* all[] = {&t->cams, &t->tab_wmv, &t->tab_g, &t->mlp_w, &t->mlp_m, &t->mlp_v, &t->mlp_g,
-                   &t->mlp_f, &t->ema, &t->rays, &t->samples, &t->logits, &t->seeds, &t->ray_loss, &t->ray_used,
-                   &t->scal, &t->losses, &t->dw_part, &t->loss_part, &t->frags, &t->act, &t->slot_of, &t->frag_pos, &t->tab_gq, &t->block_tot, &t->tile_live};
-  for (Buffer* b : all) {
-    // (parked memory is bounded: 16 GiB of the device's 288, 512 buffers; the oldest go first, so sizes nobody asks for
-    // any more do not stay for the life of the context)
-    constexpr size_t kParkBytes = (size_t)16 << 30, kParkCount = 512;
-    if (park && b->p && t->ctx && b->bytes <= kParkBytes) {
-      prv_ctx* c = t->ctx;
-      while (!c->idle_buffers.empty() && (c->idle_buffers.size() >= kParkCount || c->idle_bytes + b->bytes > kParkBytes)) {
-        c->idle_bytes -= c->idle_buffers.front().bytes;
-        release(c->idle_buffers.front());
-        c->idle_buffers.erase(c->idle_buffers.begin());
-      }
-      c->idle_buffers.push_back(*b);
-      c->idle_bytes += b->bytes;
-      *b = Buffer{};
-    } else {
-      release(*b);
-    }
-  }
 }
 
 } // namespace
 
-static void train_detach_all(prv_ctx* c) {
-  for (prv_trainer* t : c->trainers) {
-    if (t->stream) (void)hipStreamSynchronize(t->stream);
-    train_release(t);
-    t->ctx = nullptr;
+void prv_trainer::close() {
+  for (hipGraphExec_t& g : step_graph) {
+    if (g) (void)hipGraphExecDestroy(g);
+    g = nullptr;
   }
-  c->trainers.clear();
-  for (hipStream_t q : c->idle_queues) (void)hipStreamDestroy(q);
-  c->idle_queues.clear();
-  if (c->capture_stream) (void)hipStreamDestroy(c->capture_stream);
-  c->capture_stream = nullptr;
-  for (Buffer& b : c->idle_buffers) release(b);
-  c->idle_buffers.clear();
-  c->idle_bytes = 0;
+  if (stream) (void)hipStreamDestroy(stream);
+  stream = nullptr;
+}
+
+void prv_trainer::detach() {
+  if (stream) (void)hipStreamSynchronize(stream);
+  close();
+  for (Buffer* b : buffers()) b->reset();
+}
+
+// the trainer's stream (idle by now) stays with the context for the next trainer -- creating a stream with a queue of its own
+// takes 11 ms, and the planner loop creates five trainers per round -- and so do its buffers (train_buffer)
+void prv_trainer::retire() {
+  if (stream) (void)hipStreamSynchronize(stream);
+  hipStream_t keep = stream && own_queue && ctx->idle_queues.size() < 16 ? stream : nullptr;
+  if (keep) stream = nullptr;
+  close();
+  if (keep) ctx->idle_queues.push_back(keep);
+  for (Buffer* b : buffers()) ctx->parked.park(std::move(*b));
 }
 
 extern "C" {
@@ -460,16 +438,8 @@ int prv_train_create(prv_ctx* c, int slot, const prv_camset* cs, const uint8_t* 
   if ((rc = check_device_ptr(c, images_rgba8_dev, "images_rgba8_dev")) != PRV_OK) return rc;
   HIPCHK(c, prv::train_prepare_kernels());
   Model& m = c->models[slot];
-  // owns the half-built trainer until the very end: every early return (and an exception) releases it
-  struct Drop {
-    void operator()(prv_trainer* p) const {
-      train_release(p);
-      delete p;
-    }
-  };
-  std::unique_ptr<prv_trainer, Drop> owner(new prv_trainer());
+  std::unique_ptr<prv_trainer> owner(new prv_trainer(c)); // until the very end: an early return (and an exception) frees what it holds
   prv_trainer* t = owner.get();
-  t->ctx = c;
   t->slot = slot;
   t->desc = m.desc;
   t->generation = m.generation;
@@ -494,7 +464,7 @@ int prv_train_create(prv_ctx* c, int slot, const prv_camset* cs, const uint8_t* 
   // PRV_TRAIN_OWN_QUEUE=0 (dev) keeps the pooled stream for an A/B on one box.
   const bool own_queue = !(getenv("PRV_TRAIN_OWN_QUEUE") && atoi(getenv("PRV_TRAIN_OWN_QUEUE")) == 0);
   hipError_t se = hipErrorUnknown;
-  if (own_queue && !c->idle_queues.empty()) { // a destroyed trainer's (train_release)
+  if (own_queue && !c->idle_queues.empty()) { // a destroyed trainer's (prv_trainer::retire)
     t->stream = c->idle_queues.back();
     c->idle_queues.pop_back();
     t->own_queue = true;
@@ -568,7 +538,6 @@ int prv_train_create(prv_ctx* c, int slot, const prv_camset* cs, const uint8_t* 
   if (e == hipSuccess) e = prv::launch_frag_positions(m.desc.n_features, (int*)t->frag_pos.p, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) return fail(c, PRV_E_HIP, "trainer setup: %s", hipGetErrorString(e));
-  c->trainers.push_back(t);
   *out = owner.release();
   return PRV_OK;
 } catch (...) { return caught(c); }
@@ -680,28 +649,15 @@ int prv_train_master(prv_trainer* t, float* table_host, float* mlp_host) try {
     if (e == hipSuccess) e = hipMemcpyAsync(table_host, flat.p, t->n_table * 4, hipMemcpyDeviceToHost, t->stream);
     if (e != hipSuccess) {
       (void)hipStreamSynchronize(t->stream);
-      release(flat);
       return fail(c, PRV_E_HIP, "master weights: %s", hipGetErrorString(e));
     }
   }
   hipError_t e = mlp_host ? hipMemcpyAsync(mlp_host, t->mlp_w.p, PRV_MLP_HALFS * 4, hipMemcpyDeviceToHost, t->stream) : hipSuccess;
-  const hipError_t e2 = hipStreamSynchronize(t->stream);
-  release(flat);
+  const hipError_t e2 = hipStreamSynchronize(t->stream); // (before `flat` goes)
   if (e != hipSuccess || e2 != hipSuccess) return fail(c, PRV_E_HIP, "master weights: %s", hipGetErrorString(e != hipSuccess ? e : e2));
   return PRV_OK;
 } catch (...) { return caught(t ? t->ctx : nullptr); }
 
-void prv_train_destroy(prv_trainer* t) {
-  if (!t) return;
-  if (t->ctx) {
-    auto& v = t->ctx->trainers;
-    v.erase(std::remove(v.begin(), v.end(), t), v.end());
-    (void)hipSetDevice(t->ctx->device);
-    (void)hipStreamSynchronize(t->ctx->stream);
-    if (t->stream) (void)hipStreamSynchronize(t->stream);
-  }
-  train_release(t, t->ctx != nullptr);
-  delete t;
-}
+void prv_train_destroy(prv_trainer* t) { destroy_handle(t); }
 
 } // extern "C"
