@@ -18,6 +18,9 @@ constexpr int kNumFrags = 24;      // MFMA A-operand fragments of the two MLPs
 constexpr int kFragHalfs = 64 * 8; // one fragment: 64 lanes x 8 halfs
 constexpr int kTile = 16;          // rays are dealt in 16x16-pixel chunks
 constexpr int kChunkRays = kTile * kTile;
+// instant-ngp's stepping rule (PRV_STEP_NGP; SURVEY App. E, what run.py:245-247, 304 renders with): fixed step
+// dt = sqrt(3)/1024 from the AABB entry, sample i at t0 + (i + 1/2) dt while inside the box, at most 1024 (the diagonal)
+constexpr float kNgpDt = 1.7320508075688772f / 1024.0f; // = sqrtf(3.0f) / 1024.0f, the oracle's value bit for bit
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));

@@ -36,10 +36,6 @@ __device__ __forceinline__ void morton16(uint32_t i, uint32_t& x, uint32_t& y) {
   y = ((i >> 1) & 1u) | ((i >> 2) & 2u) | ((i >> 3) & 4u) | ((i >> 4) & 8u);
 }
 
-// instant-ngp's stepping rule (PRV_STEP_NGP; SURVEY App. E, what run.py:245-247, 304 renders with): fixed step
-// dt = sqrt(3)/1024 from the AABB entry, sample i at t0 + (i + 1/2) dt while inside the box, at most 1024 (the diagonal)
-constexpr float kNgpDt = 1.7320508075688772f / 1024.0f; // = sqrtf(3.0f) / 1024.0f, the oracle's value bit for bit
-
 // NGP march of one ray: up to 32 mask words (1024 steps) into the lane's column of the block's LDS scratch `mw`
 // ([word][thread]; only words [k_lo, k_hi) are written, the others are empty).  One DILATED coarse lookup clears a whole
 // 32-step word: its samples lie within 16 dt = 0.027 of the word's middle, less than one coarse cell (4 / occ_res) for
@@ -730,42 +726,36 @@ __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
 // (the hardware log takes no denormals), and so does p = 0
 __device__ __forceinline__ float entropy_add(float p, float H) { return p >= 1.17549435e-38f ? fmaf(p, -__builtin_amdgcn_logf(p), H) : H; }
 
-// The body of render_queue64_kernel (kRenderColour, X null) and render_planes_kernel (the other modes; X: its planes).
+// The body of render_queue64_kernel (kRenderColour, X null) and render_planes_kernel (the other modes; X: its planes).  Which
+// words of a ray's state tail merge and pool move between lanes, per mode: RenderMode (prv_kernels.hpp).
 // kRenderDepth: the ray also sums D = sum_i w_i t_i (w_i = the
 // sample's compositing weight, t_i its ray parameter) and writes z = D * dot(d, f) to X->out_depth[pix] when it ends
-// (f = the view's normalised forward axis, column 2 of its c2w: z-depth along the optical axis, premultiplied by opacity);
-// the ray's dynamic state that tail merge and pool move between lanes gains a 7th word, D.
+// (f = the view's normalised forward axis, column 2 of its c2w: z-depth along the optical axis, premultiplied by opacity).
 // kRenderEntropy: the density layers alone (mlp_density2: the colour kernel's first 16 MFMAs in its order, so sigma, alpha
 // and T are its bits), no SH rows, no colour sums; the ray sums H = sum_i h(w_i) and adds h(T) when it ends, and writes H and
-// 1 - T to X->out_entropy[pix] / X->out_alpha[pix].  Its movable state is four words, {record, next sample, T, H}; only
-// the 8 density fragment sets are staged in LDS.  P.out_f32 / out_u8 are not touched.
+// 1 - T to X->out_entropy[pix] / X->out_alpha[pix].  Only the 8 density fragment sets are staged in LDS.  P.out_f32 / out_u8 are not touched.
 // kRenderFootprint (prv_render_footprint): the entropy mode plus the depth mode's one FMA per sample -- D = fmaf(w, t, D) in the
 // depth mode's place, t kept live across mlp_density2 -- and z = D * dot(d, f) to X->out_depth[pix] at ray end, formed as
 // kRenderDepth forms it.  sigma, alpha and T are the colour kernel's bits in density-only mode already, so H and 1 - T are
-// the entropy mode's bits and z is the depth mode's.  Movable state: five words, {record, next sample, T, H, D}.
+// the entropy mode's bits and z is the depth mode's.
 // kRenderSurface (prv_render_surface): the entropy mode plus a first-crossing locator -- Dm = the ray parameter of the first
 // sample after which T <= X->T_cross (0 while the ray has not got there: t > 0 for every sample), one compare-and-select where
 // the footprint mode has its FMA, t kept live across mlp_density2 as there -- and at ray end z = Dm * dot(d, f) to
 // X->out_depth[pix], with the depth mode's cosine, and Dm > 0 as 1.0 / 0.0 to X->out_hit[pix].  H and 1 - T are the entropy
-// mode's bits.  Movable state: five words, {record, next sample, T, H, Dm}; Dm lives in the footprint mode's D.
+// mode's bits.  Dm lives in the footprint mode's D.
 // kRenderTermination (prv_render_termination): density-only like the entropy mode, but no H: the ray's compositing weights go to
 // a histogram over X->n_bins depth bins of its unit-cube span.  Sample i falls in bin (i * X->bin_mul) >> 16 (the host:
 // bin_mul = floor(n_bins * 65536 / n_max), n_max = the most steps a ray can have under the rule, so the bin never reaches n_bins
 // and depends on the ray and the rule alone).  The lane keeps the open bin and its sum (one float add per sample, depth order);
 // when the bin changes the sum goes to X->out_bins[bin * X->plane_stride + pix] with one store and restarts at 0, the open bin is
 // flushed at ray end beside 1 - T to X->out_alpha[pix] (the entropy mode's bits).  A bin address is written at most once per
-// ray, by whichever lane holds the ray then: no atomics, nothing read back.  Movable state: five words, {record, next sample,
-// T, sum, bin}; the sum lives in the entropy mode's H.
+// ray, by whichever lane holds the ray then: no atomics, nothing read back.  The sum lives in the entropy mode's H.
 template <int F, int NDENSE, bool NGP, bool CACHE, int MODE>
 __device__ __forceinline__ void render_queue64_body(RenderParams P, const RenderPlanesParams* X) {
-  constexpr bool FOOT = MODE == kRenderFootprint, SURF = MODE == kRenderSurface, TERM = MODE == kRenderTermination;
-  constexpr bool DEPTH = MODE == kRenderDepth || FOOT, ENTROPY = MODE == kRenderEntropy || FOOT || SURF || TERM; // DEPTH: the D sum; ENTROPY: density layers only, the H sum (TERM: the open bin's sum in its place)
-  constexpr bool DSTATE = DEPTH || SURF;                        // the ray carries D (SURF: Dm) and keeps its sample's t across the MLP
-  constexpr int kDWord = ENTROPY ? 4 : 6;                       // where D sits in the movable state
-  constexpr int kMoveWords = (ENTROPY ? 4 : 6) + (DSTATE || TERM ? 1 : 0); // {record, next sample, T, r, g, b (, D)} or {record, next sample, T, H (, D)}; TERM: {.., sum, bin}
-  constexpr int kFrags = ENTROPY ? 8 : kNumFrags;       // fragment sets staged in LDS: the density layers', or both MLPs'
+  using M = RenderMode<MODE>; // what the mode sums and which words move with a ray (prv_kernels.hpp)
+  constexpr int kDWord = M::kDWord, kMoveWords = M::kMoveWords, kFrags = M::kFrags;
   __shared__ half8 wl[kFrags * 64];
-  __shared__ uint32_t mv[4][32][kMoveWords]; // tail merges: {record, next sample, T, r, g, b (, D)} of the rays that change slots, per wave
+  __shared__ uint32_t mv[4][32][kMoveWords]; // tail merges: the moved words (RenderMode) of the rays that change slots, per wave
   constexpr uint32_t kPoolCap = 192;
   __shared__ uint32_t pool[kPoolCap][kMoveWords]; // the block's tail pool: rays a group gave up, waiting for an idle slot of ANY of the block's waves
   __shared__ uint32_t pool_n, pool_lock;
@@ -901,15 +891,15 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
           e[0] = rec_i;
           e[1] = base + (uint32_t)__builtin_ctz(cur); // the next sample to take
           e[2] = __float_as_uint(T);
-          if constexpr (ENTROPY) {
+          if constexpr (M::ENTROPY) {
             e[3] = __float_as_uint(Hs);
           } else {
             e[3] = __float_as_uint(cr);
             e[4] = __float_as_uint(cg);
             e[5] = __float_as_uint(cb);
           }
-          if constexpr (DSTATE) e[kDWord] = __float_as_uint(D);
-          if constexpr (TERM) e[4] = tbin;
+          if constexpr (M::DSTATE) e[kDWord] = __float_as_uint(D);
+          if constexpr (M::TERM) e[4] = tbin;
           active = false;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -919,20 +909,20 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
         if (!((a_dst >> r) & 1u) && kth < n_src) { // BOTH lanes of the slot: the slot's SH rows go to both halves
           const uint32_t* e = slot[kth];
           const uint32_t ri = e[0];
-          if constexpr (!ENTROPY) {
+          if constexpr (!M::ENTROPY) {
             const half8 sh = reinterpret_cast<const half8*>(queue + (size_t)ri * kRecordWords)[4 + g];
             if (src == 0) shB = sh;
             else shA = sh;
           }
           if (g != src) { // the destination lane itself takes the ray over
             T = __uint_as_float(e[2]);
-            if constexpr (ENTROPY) {
+            if constexpr (M::ENTROPY) {
               Hs = __uint_as_float(e[3]);
             } else {
               cr = __uint_as_float(e[3]); cg = __uint_as_float(e[4]); cb = __uint_as_float(e[5]);
             }
-            if constexpr (DSTATE) D = __uint_as_float(e[kDWord]);
-            if constexpr (TERM) tbin = e[4];
+            if constexpr (M::DSTATE) D = __uint_as_float(e[kDWord]);
+            if constexpr (M::TERM) tbin = e[4];
             take_ray(ri, e[1]);
           }
         }
@@ -959,15 +949,15 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
             e[0] = rec_i;
             e[1] = base + (uint32_t)__builtin_ctz(cur);
             e[2] = __float_as_uint(T);
-            if constexpr (ENTROPY) {
+            if constexpr (M::ENTROPY) {
               e[3] = __float_as_uint(Hs);
             } else {
               e[3] = __float_as_uint(cr);
               e[4] = __float_as_uint(cg);
               e[5] = __float_as_uint(cb);
             }
-            if constexpr (DSTATE) e[kDWord] = __float_as_uint(D);
-            if constexpr (TERM) e[4] = tbin;
+            if constexpr (M::DSTATE) e[kDWord] = __float_as_uint(D);
+            if constexpr (M::TERM) e[4] = tbin;
             active = false;
           }
           if (fits && lane == 0) *(volatile uint32_t*)&pool_n = at + n_g;
@@ -994,20 +984,20 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
         if (lane == 0) *(volatile uint32_t*)&pool_n = from;
         pool_release();
         if (mine) {
-          if constexpr (!ENTROPY) {
+          if constexpr (!M::ENTROPY) {
             const half8 sh = reinterpret_cast<const half8*>(queue + (size_t)ent[0] * kRecordWords)[4 + g];
             if (grp == 0) shA = sh;
             else shB = sh;
           }
           if (g == grp) {
             T = __uint_as_float(ent[2]);
-            if constexpr (ENTROPY) {
+            if constexpr (M::ENTROPY) {
               Hs = __uint_as_float(ent[3]);
             } else {
               cr = __uint_as_float(ent[3]); cg = __uint_as_float(ent[4]); cb = __uint_as_float(ent[5]);
             }
-            if constexpr (DSTATE) D = __uint_as_float(ent[kDWord]);
-            if constexpr (TERM) tbin = ent[4];
+            if constexpr (M::DSTATE) D = __uint_as_float(ent[kDWord]);
+            if constexpr (M::TERM) tbin = ent[4];
             take_ray(ent[0], ent[1]);
           }
         }
@@ -1037,16 +1027,16 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
         }
         const uint32_t avail = min(32u, q_end - q_cur);
         if ((uint32_t)r < avail) { // both lane halves: the group's SH rows go to every lane, the ray itself to its own lane
-          if constexpr (!ENTROPY) {
+          if constexpr (!M::ENTROPY) {
             const half8 sh = reinterpret_cast<const half8*>(queue + (size_t)(q_cur + (uint32_t)r) * kRecordWords)[4 + g];
             if (grp == 0) shA = sh;
             else shB = sh;
           }
           if (g == grp) {
             T = 1.f; cr = 0.f; cg = 0.f; cb = 0.f;
-            if constexpr (DSTATE) D = 0.f;
-            if constexpr (ENTROPY) Hs = 0.f;
-            if constexpr (TERM) tbin = 0u; // (a first sample in a later bin stores bin 0's empty sum: the 0 the plane holds)
+            if constexpr (M::DSTATE) D = 0.f;
+            if constexpr (M::ENTROPY) Hs = 0.f;
+            if constexpr (M::TERM) tbin = 0u; // (a first sample in a later bin stores bin 0's empty sum: the 0 the plane holds)
             take_ray(q_cur + (uint32_t)r, 0u);
           }
         }
@@ -1086,8 +1076,8 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
         }
       }
       const float t = fmaf((float)i + 0.5f, dt, t0);
-      if constexpr (DSTATE) ts = t;
-      if constexpr (TERM) sbin = min((i * X->bin_mul) >> 16, X->n_bins - 1u); // (the min changes no bin of a ray within n_max steps: it keeps any other inside the planes)
+      if constexpr (M::DSTATE) ts = t;
+      if constexpr (M::TERM) sbin = min((i * X->bin_mul) >> 16, X->n_bins - 1u); // (the min changes no bin of a ray within n_max steps: it keeps any other inside the planes)
       encode_sample<F, NDENSE, CACHE>(P.field.table, lvl, hc, fmaf(t, d[0], o[0]), fmaf(t, d[1], o[1]), fmaf(t, d[2], o[2]), f, cc);
     }
     // f[2s] | f[2s+1] = k rows [16s, 16s+8) | [16s+8, 16s+16) of the lane's own sample -> B operands of the two groups
@@ -1095,13 +1085,13 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
     swap_halves(f[2], f[3]);
     const half8 fA[2] = {f[0], f[2]}, fB[2] = {f[1], f[3]};
     MlpOut2 mo;
-    if constexpr (ENTROPY) mlp_density2(wl, lane, fA, fB, mo.densA, mo.densB);
+    if constexpr (M::ENTROPY) mlp_density2(wl, lane, fA, fB, mo.densA, mo.densB);
     else mo = mlp_forward2(wl, lane, fA, fB, shA, shB);
     // the lane's own sample: group A's results sit in lane half 0 (rows 0..2 = registers 0..2), group B's copies in the
     // padding rows 20..22 = lane half 1, registers 8..10
     const float dens = g ? mo.densB[8] : mo.densA[0];
     float lr = 0.f, lg = 0.f, lb = 0.f;
-    if constexpr (!ENTROPY) {
+    if constexpr (!M::ENTROPY) {
       lr = g ? mo.rgbB[8] : mo.rgbA[0];
       lg = g ? mo.rgbB[9] : mo.rgbA[1];
       lb = g ? mo.rgbB[10] : mo.rgbA[2];
@@ -1112,47 +1102,47 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
       const float sigma = fast_exp(dens + P.field.density_bias);
       const float alpha = 1.0f - fast_exp(-(sigma * dt));
       const float wgt = alpha * T;
-      if constexpr (TERM) {
+      if constexpr (M::TERM) {
         if (sbin != tbin) {
           X->out_bins[(size_t)tbin * X->plane_stride + pix] = Hs;
           Hs = 0.f;
           tbin = sbin;
         }
         Hs = Hs + wgt;
-      } else if constexpr (ENTROPY) {
+      } else if constexpr (M::ENTROPY) {
         Hs = entropy_add(wgt, Hs);
       } else {
         cr = fmaf(wgt, fast_sigmoid(lr), cr);
         cg = fmaf(wgt, fast_sigmoid(lg), cg);
         cb = fmaf(wgt, fast_sigmoid(lb), cb);
       }
-      if constexpr (DEPTH) D = fmaf(wgt, ts, D);
+      if constexpr (M::DEPTH) D = fmaf(wgt, ts, D);
       T = T * (1.0f - alpha);
-      if constexpr (SURF) {
+      if constexpr (M::SURF) {
         if (D == 0.f && T <= X->T_cross) D = ts;
       }
       done = last || T < P.min_T;
     }
     if (done) {
-      if constexpr (!ENTROPY) {
+      if constexpr (!M::ENTROPY) {
         const float4 v = make_float4(cr, cg, cb, 1.0f - T);
         reinterpret_cast<float4*>(P.out_f32)[pix] = v;
         if (P.last_pass && P.out_u8) P.out_u8[pix] = quantize_rgba8(v.x, v.y, v.z, v.w, P.bg);
       }
-      if constexpr (TERM) {
+      if constexpr (M::TERM) {
         X->out_bins[(size_t)tbin * X->plane_stride + pix] = Hs; // the open bin
         X->out_alpha[pix] = 1.0f - T;
-      } else if constexpr (ENTROPY) {
+      } else if constexpr (M::ENTROPY) {
         X->out_entropy[pix] = entropy_add(T, Hs); // + h(T_end): the ray escapes with what is left
         X->out_alpha[pix] = 1.0f - T;
       }
-      if constexpr (DSTATE) {
+      if constexpr (M::DSTATE) {
         // image pix / npix of the launch is a sub-sample of view (pix / npix) % nb
         const CamDev& cam = X->cams[X->view_ids[(pix / X->npix) % X->nb]];
         const float fx = cam.c2w[2], fy = cam.c2w[6], fz = cam.c2w[10];
         const float inv = 1.0f / sqrtf(fmaf(fx, fx, fmaf(fy, fy, fz * fz)));
         X->out_depth[pix] = D * (fmaf(d[0], fx, fmaf(d[1], fy, d[2] * fz)) * inv);
-        if constexpr (SURF) X->out_hit[pix] = D > 0.f ? 1.0f : 0.0f;
+        if constexpr (M::SURF) X->out_hit[pix] = D > 0.f ? 1.0f : 0.0f;
       }
       active = false;
     }

@@ -109,6 +109,21 @@ struct RenderParams {
 // what a launch renders: the colour image, or scalar planes (render_planes_kernel's MODE)
 enum : int { kRenderColour = 0, kRenderDepth = 1, kRenderEntropy = 2, kRenderFootprint = 3, kRenderSurface = 4, kRenderTermination = 5 };
 
+// what a mode computes per sample, and the words of a ray's state that tail merge and pool move between lanes through LDS:
+// {record, next sample, T, r, g, b (, D)}, or density-only {record, next sample, T, H (, D | Dm | bin)} (render_queue64_body)
+template <int MODE>
+struct RenderMode {
+  static constexpr bool FOOT = MODE == kRenderFootprint, SURF = MODE == kRenderSurface, TERM = MODE == kRenderTermination;
+  static constexpr bool DEPTH = MODE == kRenderDepth || FOOT;                             // the sum D = sum_i w_i t_i
+  static constexpr bool ENTROPY = MODE == kRenderEntropy || FOOT || SURF || TERM;          // density layers only; the sum H (TERM: the open bin's sum in its place)
+  static constexpr bool DSTATE = DEPTH || SURF;                                           // the ray carries D (SURF: Dm) and keeps its sample's t across the MLP
+  static constexpr int kDWord = ENTROPY ? 4 : 6;                                          // where D sits in the moved words (TERM: the bin)
+  static constexpr int kMoveWords = kDWord + (DSTATE || TERM ? 1 : 0);
+  static constexpr int kFrags = ENTROPY ? 8 : kNumFrags;                                  // fragment sets staged in LDS: the density layers', or both MLPs'
+};
+static_assert(RenderMode<kRenderColour>::kMoveWords == 6 && RenderMode<kRenderDepth>::kMoveWords == 7 && RenderMode<kRenderEntropy>::kMoveWords == 4, "moved words");
+static_assert(RenderMode<kRenderFootprint>::kMoveWords == 5 && RenderMode<kRenderSurface>::kMoveWords == 5 && RenderMode<kRenderTermination>::kMoveWords == 5, "moved words");
+
 // the plane-writing renders (render_planes_kernel): the colour launch's parameters, untouched, plus one float per pixel of
 // the launch's images (r.out_f32 / 4) per plane.  A plane starts zeroed, which is what a dead ray contributes.
 //   kRenderDepth (prv_render_depth):         the colour image and out_depth

@@ -116,7 +116,6 @@ __device__ __forceinline__ bool rays_step(const TrainRaysParams& P, uint32_t bx,
   return (unsigned long long)bx * 4ull < (unsigned long long)n_active;
 }
 
-constexpr float kTrainNgpDt = 1.7320508075688772f / 1024.0f; // = sqrtf(3.0f) / 1024.0f, the oracle's value bit for bit (as prv_kernels.hip)
 // a block's range of the sample list (thread 0 calls): ONE returning atomic on the step's counter.  A deterministic batch
 // (tests) is listed in block order without any block waiting for another: the ray kernel runs twice around a scan.  PASS is
 // the kernel's compile-time parameter -- 0: the product's kernel, and the only one inside adam_table_kernel; 1: the count pass
@@ -179,7 +178,7 @@ __device__ __forceinline__ void train_rays_block(const TrainRaysParams& P, uint3
   int n_words = 0; // wave-uniform: rounds of 64 steps that can hold a live sample
   if (in_budget && ray_aabb(r.o, r.d, t0, t1)) {
     r.t0 = t0;
-    r.dt = NGP ? kTrainNgpDt : (t1 - t0) / (float)P.S;
+    r.dt = NGP ? kNgpDt : (t1 - t0) / (float)P.S;
     if (NGP) { // steps beyond the exit are dead: (t1 - t0) / dt + 2 bounds them (the exact `t < t1` test below decides)
       const int inside = (int)fminf((t1 - t0) * (1024.0f / 1.7320508075688772f) + 2.0f, (float)P.S);
       n_words = (min(inside, P.S) + 63) >> 6;

@@ -202,6 +202,28 @@ def test_placement_switches_change_no_byte(ctx, oracle, switched, run):
         assert np.array_equal(img2.view(np.uint32), img.view(np.uint32)), shape
 
 
+@pytest.mark.parametrize("run", [r for r in RUNS if r[0] in ("skew", "gaps")], ids=_run_id)
+def test_footprint_planes_do_not_depend_on_placement(ctx, oracle, switched, run):
+    """the footprint mode's five moved words {record, next sample, T, H, D} through tail merge and pool (PRV_MERGE_MAX=31 PRV_POOL=1,
+    and every other switch): the stragglers of `skew`, and `gaps`' rays taken over in a later chunk, leave the three planes and
+    the counts what the default placement gives, bit for bit"""
+    name, mode = run
+    case = qc.get(name)
+    for shape in SHAPES:
+        outs = []
+        for c, slot in ((ctx, SLOT), (switched, 0)):
+            _load(c, oracle, slot, case, shape).close()
+            cs = case.cams(c)
+            ent, alpha, depth, st = c.render_footprint(slot, cs, None, case.opts(mode))
+            cs.close()
+            outs.append(([t.cpu().numpy() for t in (ent, alpha, depth)], (int(st.samples_live), int(st.samples_evaluated))))
+        (want, n_want), (got, n_got) = outs
+        assert n_got == n_want, (shape, n_want, n_got)
+        for plane, g, w in zip(("entropy", "alpha", "depth"), got, want):
+            assert np.array_equal(g.view(np.uint32), w.view(np.uint32)), (shape, plane)
+        assert (want[1] > 0).any() and (want[2] > 0).any()
+
+
 # ---- 4. counts
 @pytest.mark.parametrize("shape", list(SHAPES))
 @pytest.mark.parametrize("mode", [qc.FIXED, qc.NGP], ids=["S128", "ngp"])
