@@ -28,6 +28,7 @@
 #include "prv_levels.hpp"
 #include "prv_ingp.hpp"
 #include "prv_train.hpp"
+#include "prv_train_switches.hpp"
 
 using namespace prv;
 

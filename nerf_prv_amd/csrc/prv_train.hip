@@ -2013,13 +2013,21 @@ hipError_t train_prepare_kernels() {
   return hipSuccess;
 }
 
-hipError_t launch_train_tiles(const TrainTileParams& P0, bool forward, int n_blocks, hipStream_t s, bool finish_reduce, int* n_slots_out) {
-  TrainTileParams P = P0;
+static TrainTileParams all_tiles(TrainTileParams P) {
   P.tile_begin = 0;
   P.tile_limit = ~0u;
   P.slot_base = 0;
+  return P;
+}
+
+hipError_t launch_train_forward(const TrainTileParams& P0, int n_blocks, hipStream_t s) {
+  const TrainTileParams P = all_tiles(P0);
+  return P.n_features == 4 ? launch_tile<4, true>(P, n_blocks, s) : launch_tile<2, true>(P, n_blocks, s);
+}
+
+hipError_t launch_train_backward(const TrainTileParams& P0, int n_blocks, DwReduce reduce, int* n_slots_out, hipStream_t s) {
+  TrainTileParams P = all_tiles(P0);
   const bool f4 = P.n_features == 4;
-  if (forward) return f4 ? launch_tile<4, true>(P, n_blocks, s) : launch_tile<2, true>(P, n_blocks, s);
   hipError_t e;
   const int n_lds74 = n_blocks;
   int n_slots = n_blocks;
@@ -2047,23 +2055,20 @@ hipError_t launch_train_tiles(const TrainTileParams& P0, bool forward, int n_blo
     n_slots = n_lds74;
   }
   if (e != hipSuccess) return e;
-  // the stage buffer sits behind the slots (train_dw_slots(n_blocks) slots + kDwGroups group sums)
-  float* stage = P.mlp_grad_partial + (size_t)train_dw_slots(n_blocks) * PRV_MLP_HALFS;
-  if (n_slots_out) { // the caller's next launch (the table's Adam pass) carries the first stage of the reduction
+  if (reduce == DwReduce::AdamPasses) { // the caller's next launch (the table's Adam pass) carries the first stage of the reduction
     *n_slots_out = n_slots;
     return hipGetLastError();
   }
+  float* stage = train_dw_stage(P.mlp_grad_partial, n_blocks); // (kDwGroups group sums)
   hipLaunchKernelGGL(train_reduce_dw_kernel, dim3(kDwBlocksX, kDwGroups), dim3(256), 0, s, P.mlp_grad_partial, n_slots, stage);
-  if (finish_reduce) hipLaunchKernelGGL(train_reduce_dw2_kernel, dim3((PRV_MLP_HALFS + 255) / 256), dim3(256), 0, s, stage, P.mlp_grad);
+  hipLaunchKernelGGL(train_reduce_dw2_kernel, dim3((PRV_MLP_HALFS + 255) / 256), dim3(256), 0, s, stage, P.mlp_grad);
   return hipGetLastError();
 }
 
-hipError_t launch_prepack_frags(const uint16_t* mlp, int n_features, uint16_t* frags, const AdamParams* end_of_step,
-                                uint32_t* sample_count, float lr, hipStream_t s) {
-  AdamParams P{};
-  if (end_of_step) P = *end_of_step; // state != NULL: this launch closes the step and opens the next
-  hipLaunchKernelGGL(prepack_frags_kernel, dim3(((kNumFrags + kBwdFrags) * kFragHalfs + 255) / 256), dim3(256), 0, s, mlp, n_features, frags, P,
-                     sample_count, lr);
+hipError_t launch_prepack_frags(const uint16_t* mlp, int n_features, uint16_t* frags, hipStream_t s) {
+  const AdamParams no_step{}; // (state == NULL: the kernel closes no step)
+  hipLaunchKernelGGL(prepack_frags_kernel, dim3(((kNumFrags + kBwdFrags) * kFragHalfs + 255) / 256), dim3(256), 0, s, mlp, n_features, frags, no_step,
+                     (uint32_t*)nullptr, 0.f);
   return hipGetLastError();
 }
 
@@ -2100,18 +2105,17 @@ hipError_t launch_grad_q_to_f32(long long* q, size_t n, float* out, hipStream_t 
   return hipGetLastError();
 }
 
-hipError_t launch_adam_table(const AdamParams& P, size_t n, float* grad, float* wmv, uint16_t* w16, hipStream_t s, const float* dw_partial,
-                             int dw_slots, float* dw_stage, const TrainRaysParams* next_rays, long long* grad_q) {
-  const unsigned n_adam = (unsigned)((n + 1023) / 1024), n_dw = dw_partial ? (unsigned)(kDwBlocksX * kDwGroups) : 0u;
+hipError_t launch_adam_table(const AdamParams& P, const AdamTableArgs& A, hipStream_t s) {
+  const unsigned n_adam = (unsigned)((A.n + 1023) / 1024), n_dw = A.dw_partial ? (unsigned)(kDwBlocksX * kDwGroups) : 0u;
   TrainRaysParams R{};
   unsigned n_rays_blocks = 0u;
-  if (next_rays) {
-    if (next_rays->block_tot) return hipErrorInvalidValue; // a deterministic batch is launches of its own (launch_train_rays)
-    R = *next_rays;
+  if (A.next_rays) {
+    if (A.next_rays->block_tot) return hipErrorInvalidValue; // a deterministic batch is launches of its own (launch_train_rays)
+    R = *A.next_rays;
     n_rays_blocks = (unsigned)((R.n_rays + 3) / 4);
   }
-  hipLaunchKernelGGL(adam_table_kernel, dim3(n_adam + n_dw + n_rays_blocks), dim3(256), 0, s, P, n, grad, wmv, w16, n_adam, dw_partial, dw_slots,
-                     dw_stage, n_dw, R, grad_q);
+  hipLaunchKernelGGL(adam_table_kernel, dim3(n_adam + n_dw + n_rays_blocks), dim3(256), 0, s, P, A.n, A.grad, A.wmv, A.w16, n_adam, A.dw_partial,
+                     A.dw_slots, A.dw_stage, n_dw, R, A.grad_q);
   return hipGetLastError();
 }
 
@@ -2125,11 +2129,9 @@ hipError_t launch_narrow_table(const float* wmv, size_t n, float* out, hipStream
   return hipGetLastError();
 }
 
-hipError_t launch_adam_mlp(const AdamParams& P, float l2_reg, float* grad, float* w, float* m, float* v, uint16_t* w16,
-                           float* w16_as_f32, const float* stage, int end_of_step, hipStream_t s, uint16_t* frags, const int* frag_pos,
-                           uint32_t* sample_count, float lr) {
-  hipLaunchKernelGGL(adam_mlp_kernel, dim3((PRV_MLP_HALFS + 255) / 256), dim3(256), 0, s, P, l2_reg, grad, w, m, v, w16,
-                     w16_as_f32, stage, end_of_step, frags, frag_pos, sample_count, lr);
+hipError_t launch_adam_mlp(const AdamParams& P, const AdamMlpArgs& A, hipStream_t s) {
+  hipLaunchKernelGGL(adam_mlp_kernel, dim3((PRV_MLP_HALFS + 255) / 256), dim3(256), 0, s, P, A.l2_reg, A.grad, A.w, A.m, A.v, A.w16,
+                     A.w16_as_f32, A.stage, A.end_of_step, A.frags, A.frag_pos, A.sample_count, A.lr);
   return hipGetLastError();
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/prv.h"
 #include "prv_device.hpp"
+#include <cstddef>
 
 namespace prv {
 
@@ -32,7 +33,20 @@ struct TrainState {
                   // end_step already writes the next step's lr_t
   uint32_t overflow; // sticky: a ray batch did not fit the sample list (PRV_STEP_NGP's 2^24 cap); every later kernel sees an empty batch
 };
-static_assert(sizeof(TrainState) == 32, "scal: TrainState sits at [32, 64)");
+
+// a trainer's block of device scalars (prv_trainer::scal); all of it starts at zero
+struct TrainScal {
+  uint32_t sample_count[2]; // live samples of a step's ray batch: a step lists into the word of its parity
+  unsigned long long used;  // samples the step composited (AdamParams::used)
+  float loss;               // prv_train_gradients points TrainState::losses here
+  uint32_t pad, ticket;     // ticket: once the loss ticket; no kernel touches it now
+  uint32_t listed;          // dev (PRV_TRAIN_TIMING): the finished step's listed-sample count; end_step writes it as sample_count[7]
+  TrainState state;
+  unsigned long long stamps[64]; // dev only (TrainTileParams::stamps)
+};
+static_assert(offsetof(TrainScal, used) == 8 && offsetof(TrainScal, loss) == 16 && offsetof(TrainScal, state) == 32, "TrainScal layout");
+static_assert(offsetof(TrainScal, listed) == 7 * sizeof(uint32_t), "end_step writes sample_count[7]");
+static_assert(offsetof(TrainScal, stamps) == 64 && sizeof(TrainScal) == 64 + 64 * 8, "TrainScal layout");
 
 struct TrainRaysParams {
   const CamDev* cams;    // n_img dataset cameras at (W, H)
@@ -87,7 +101,7 @@ struct TrainTileParams {
   uint4* act;
   uint32_t act_cap; // samples covered by `act` (a multiple of 32)
   uint32_t sample_cap; // the most samples a step can list (n_rays x n_samples): act_cap >= sample_cap = no tile is ever recomputed
-  // set by launch_train_tiles: the tiles [tile_begin, min(tile_limit, all)) are this launch's, block b owns slot
+  // set by launch_train_forward / launch_train_backward: the tiles [tile_begin, min(tile_limit, all)) are this launch's, block b owns slot
   // slot_base + b of mlp_grad_partial (the backward pass is two launches when activations are kept: the tiles the
   // buffer covers, and -- nearly always none -- the tiles beyond it, which recompute their forward pass)
   uint32_t tile_begin, tile_limit;
@@ -117,7 +131,9 @@ constexpr int kGradQBits = 40;
 constexpr size_t kActTileBytes = (16 * 64 + 32) * 16; // kept activations of a 32-sample tile: 16 slots x 64 lanes x 16 B, then 32 positions
 constexpr int kBwdFrags = 20; // R3: 2 row tiles | R2: 2 x 4 k-steps | R1: 4 k-steps | D2: 2 row tiles | D1: 4 k-steps
 // slots of mlp_grad_partial for a backward pass launched with n_blocks blocks (the stage of the reduction sits behind them)
-inline int train_dw_slots(int n_blocks) { return n_blocks + n_blocks / 2; } // first launch + the tail launch (launch_train_tiles)
+inline int train_dw_slots(int n_blocks) { return n_blocks + n_blocks / 2; } // first launch + the tail launch (launch_train_backward)
+// the reduction's stage buffer (its 16 group sums) sits behind those slots
+inline float* train_dw_stage(float* mlp_grad_partial, int n_blocks) { return mlp_grad_partial + (size_t)train_dw_slots(n_blocks) * PRV_MLP_HALFS; }
 
 struct TrainCompositeParams {
   TrainRay* rays;
@@ -156,28 +172,51 @@ struct DensityParams {
 size_t train_tile_lds_bytes(bool fwd, int mode);
 hipError_t train_prepare_kernels();
 hipError_t launch_train_rays(const TrainRaysParams& P, hipStream_t s);
-// backward: finish_reduce = false leaves the second stage of the dW reduction to adam_mlp_kernel (stage = slots + n_blocks)
-// n_slots_out != NULL: NO reduction launch at all -- the count of written slots is returned and the table's Adam launch does the
-// first stage beside its own work (launch_adam_table's dw_* arguments)
-hipError_t launch_train_tiles(const TrainTileParams& P, bool forward, int n_blocks, hipStream_t s, bool finish_reduce = true, int* n_slots_out = nullptr);
-hipError_t launch_prepack_frags(const uint16_t* mlp, int n_features, uint16_t* frags, const AdamParams* end_of_step,
-                                uint32_t* sample_count, float lr, hipStream_t s);
+hipError_t launch_train_forward(const TrainTileParams& P, int n_blocks, hipStream_t s); // the plain path's (f32 tiles)
+// who sums the backward blocks' dW slots into mlp_grad
+enum class DwReduce {
+  Here,      // two reduction launches behind the backward pass (prv_train_gradients)
+  AdamPasses // no reduction launch: *n_slots_out = the count of written slots, the table's Adam launch does the first stage beside its
+             // own work (AdamTableArgs::dw_*) and adam_mlp_kernel the second (AdamMlpArgs::stage)
+};
+hipError_t launch_train_backward(const TrainTileParams& P, int n_blocks, DwReduce reduce, int* n_slots_out, hipStream_t s);
+hipError_t launch_prepack_frags(const uint16_t* mlp, int n_features, uint16_t* frags, hipStream_t s); // a trainer's first fragments
 hipError_t launch_train_forward_fast(const TrainTileParams& P, const half8* frags, int n_blocks, hipStream_t s);
 hipError_t launch_train_composite(const TrainCompositeParams& P, hipStream_t s);
 hipError_t launch_train_begin(TrainState* state, uint32_t* sample_count, float lr, float beta1, float beta2, hipStream_t s);
 // wmv: one {w[4], m[4], v[4]} record (48 B) per group of four table scalars, ceil(n / 4) records
 // next_rays != NULL (single-pixel batches only: the patch kernel has another block size; never a deterministic batch): the NEXT
 // step's ray batch as further extra blocks of the same launch (TrainRaysParams::next = 1)
-hipError_t launch_adam_table(const AdamParams& P, size_t n, float* grad, float* wmv, uint16_t* w16, hipStream_t s, const float* dw_partial = nullptr,
-                             int dw_slots = 0, float* dw_stage = nullptr, const TrainRaysParams* next_rays = nullptr, long long* grad_q = nullptr);
+struct AdamTableArgs {
+  size_t n; // table scalars
+  float* grad;
+  float* wmv;
+  uint16_t* w16;
+  const float* dw_partial; // the backward launch's dW slots: first stage of their reduction as extra blocks (NULL: none)
+  int dw_slots;
+  float* dw_stage;
+  const TrainRaysParams* next_rays;
+  long long* grad_q; // deterministic trainers: TrainTileParams::table_grad_q
+};
+hipError_t launch_adam_table(const AdamParams& P, const AdamTableArgs& A, hipStream_t s);
 hipError_t launch_grad_q_to_f32(long long* q, size_t n, float* out, hipStream_t s); // deterministic trainers: fixed-point gradient -> f32, cleared
 hipError_t launch_widen_table(const uint16_t* in, size_t n, float* wmv, hipStream_t s);
 hipError_t launch_narrow_table(const float* wmv, size_t n, float* out, hipStream_t s); // the records' w parts, contiguous
 // frags != NULL: the step's last kernel -- every thread also puts its fresh fp16 weight into its place of the forward and of the
 // backward MFMA fragments (frag_pos: launch_frag_positions) and thread 0 closes the step (end_step with sample_count / lr)
-hipError_t launch_adam_mlp(const AdamParams& P, float l2_reg, float* grad, float* w, float* m, float* v, uint16_t* w16,
-                           float* w16_as_f32, const float* stage, int end_of_step, hipStream_t s, uint16_t* frags = nullptr,
-                           const int* frag_pos = nullptr, uint32_t* sample_count = nullptr, float lr = 0.f);
+struct AdamMlpArgs {
+  float l2_reg;
+  float *grad, *w, *m, *v;
+  uint16_t* w16;
+  float* w16_as_f32;
+  const float* stage; // second stage of the dW reduction: train_dw_stage()
+  int end_of_step;    // the plain path (frags == NULL): thread 0 closes the step
+  uint16_t* frags;
+  const int* frag_pos;
+  uint32_t* sample_count;
+  float lr;
+};
+hipError_t launch_adam_mlp(const AdamParams& P, const AdamMlpArgs& A, hipStream_t s);
 // frag_pos[w] / frag_pos[PRV_MLP_HALFS + w]: where canonical weight w sits in the forward / backward fragments (each map is a bijection)
 hipError_t launch_frag_positions(int n_features, int* frag_pos, hipStream_t s);
 hipError_t launch_widen(const uint16_t* in, size_t n, float* out, hipStream_t s);

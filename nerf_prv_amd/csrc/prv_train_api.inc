@@ -19,24 +19,22 @@ struct prv_trainer : prv_handle {
   bool own_queue = false;       // ... created with a CU mask: it owns a hardware queue, and is parked in the context when the trainer goes (prv_ctx::idle_queues)
   hipGraphExec_t step_graph[2] = {nullptr, nullptr}; // one optimiser step behind its ray batch, captured once per variant ([1]: it also lists the next step's batch), replayed every step
   bool rays_listed = false;             // the batch of the next step to run is there already (the previous step's Adam launch listed it)
-  bool use_graph = true;
+  prv::TrainSwitches sw;     // the PRV_TRAIN_* environment, as it was when the trainer was created
+  bool graph_failed = false; // a step graph could not be captured: plain launches for good
   prv::LevelCanon levels[kMaxLevels];
-  Buffer tile_live; // one byte per 32-sample tile of the list (prv_train.hpp: TrainTileParams::tile_live)
-  Buffer tab_gq; // deterministic trainers: the table gradient in 64-bit fixed point (prv_train.hip: table_grad_add)
-  Buffer block_tot; // deterministic trainers: a word per block of the ray launch (prv_train.hpp: TrainRaysParams::block_tot)
   uint32_t list_cap = 0; // samples the step's list holds (n_rays x n_samples; PRV_STEP_NGP: at most 2^24)
-  Buffer cams, tab_wmv, tab_g, mlp_w, mlp_m, mlp_v, mlp_g, mlp_f, ema, rays, samples, logits, seeds,
-      ray_loss, ray_used, scal, losses, dw_part, loss_part, frags, act, slot_of, frag_pos;
-  uint32_t act_cap = 0;     // samples the kept-activation buffer covers (0: the backward pass recomputes the forward pass)
-  bool reg_chain = true;    // backward dX chain register-resident on bf16-split MFMAs (PRV_TRAIN_REG_CHAIN=0: the LDS / f32-MFMA chain)
-  bool fast_forward = true; // forward logits through the f16-MFMA path of the render kernel (PRV_TRAIN_FAST_FWD=0: f32 tiles)
+  uint32_t act_cap = 0;  // samples the kept-activation buffer covers (0: the backward pass recomputes the forward pass)
   bool side_by_side = false; // this call steps several trainers (prv_train_steps_multi): one backward block per CU (bwd_blocks)
   int graph_bwd_blocks[2] = {0, 0}; // the backward block count each captured step graph was recorded with
-  bool patch_ray_jitter = false; // dev only (PRV_TRAIN_PATCH_JITTER=ray at creation): every ray of a patch its own jitter; the oracle has no such mode
-  std::vector<Buffer*> buffers() {
-    return {&cams, &tab_wmv, &tab_g, &mlp_w, &mlp_m, &mlp_v, &mlp_g, &mlp_f, &ema, &rays, &samples, &logits, &seeds, &ray_loss, &ray_used,
-            &scal, &losses, &dw_part, &loss_part, &frags, &act, &slot_of, &frag_pos, &tab_gq, &block_tot, &tile_live};
-  }
+  // the device buffers: each is named here and once in buffer_table(), which is all that allocates, zeroes, parks and frees them
+  Buffer cams, tab_wmv, tab_g, mlp_w, mlp_m, mlp_v, mlp_g, mlp_f, ema, rays, samples, logits, seeds,
+      ray_loss, ray_used, scal, losses, dw_part, loss_part, frags, slot_of, frag_pos, tab_gq, block_tot, tile_live, act;
+  struct BufferRow {
+    Buffer prv_trainer::*buf;
+    size_t bytes; // what this trainer needs when it is created (0: nothing)
+    bool zeroed;  // starts at zero, all of it, whoever held the memory before
+  };
+  std::vector<BufferRow> buffer_table() const;
 };
 
 namespace {
@@ -50,10 +48,8 @@ constexpr int kBwdBlocksPerCu = 2;
 // launches share the CUs and one's table adds meet the other's tile work (measured, the planner loop's batch: round of five
 // 0.570 -> 0.531 ms, of two 0.246 -> 0.233; one trainer alone 0.166 -> 0.181, hence the rule).  PRV_TRAIN_BWD_BLOCKS (dev) overrides.
 static int bwd_blocks(const prv_trainer* t) {
-  const char* const env = getenv("PRV_TRAIN_BWD_BLOCKS"); // read per call: tests change it between trainers
-  const int over = env ? atoi(env) : 0;
   const int full = t->ctx->n_cu * kBwdBlocksPerCu;
-  if (over > 0) return std::min(over, full);
+  if (t->sw.bwd_blocks > 0) return std::min(t->sw.bwd_blocks, full);
   return t->side_by_side ? t->ctx->n_cu : full;
 }
 
@@ -71,11 +67,8 @@ int train_check(prv_trainer* t) {
   return PRV_OK;
 }
 
-// scal: [0] sample_count u32 x 2 (a step lists into the word of its parity) | [8] used u64 | [16] loss f32 (scratch of prv_train_gradients) | [24] loss ticket u32 |
-//       [32] TrainState |
-//       [64, 576) dev-only phase stamps
-static prv::TrainState* train_state(prv_trainer* t) { return (prv::TrainState*)((char*)t->scal.p + 32); }
-constexpr size_t kScalBytes = 64 + 64 * 8;
+// the trainer's scalars on the device: a device pointer, only ever used to take a field's address
+static prv::TrainScal* train_scal(const prv_trainer* t) { return (prv::TrainScal*)t->scal.p; }
 
 // the ray batch of the step in flight (next = false) or of the one after it (true: launched beside the table's Adam pass)
 prv::TrainRaysParams train_rays_params(prv_trainer* t, bool next) {
@@ -91,11 +84,11 @@ prv::TrainRaysParams train_rays_params(prv_trainer* t, bool next) {
   rp.n_rays = t->o.n_rays;
   rp.occ_res = t->desc.occ_res;
   rp.random_bg = t->o.random_bg;
-  rp.state = train_state(t);
+  rp.state = &train_scal(t)->state;
   rp.seed = t->o.seed;
   rp.rays = (prv::TrainRay*)t->rays.p;
   rp.samples = (uint2*)t->samples.p;
-  rp.sample_count = (uint32_t*)t->scal.p;
+  rp.sample_count = train_scal(t)->sample_count;
   rp.next = next ? 1 : 0;
   rp.target_samples = t->o.target_samples;
   rp.loss_part = (const double*)t->loss_part.p;
@@ -103,25 +96,29 @@ prv::TrainRaysParams train_rays_params(prv_trainer* t, bool next) {
   rp.patch_w = patches ? t->o.patch_w : 1;
   rp.patch_h = patches ? t->o.patch_h : 1;
   rp.slot_of = patches ? (uint32_t*)t->slot_of.p : nullptr;
-  rp.patch_ray_jitter = t->patch_ray_jitter ? 1 : 0;
+  rp.patch_ray_jitter = t->sw.patch_ray_jitter ? 1 : 0;
   rp.step_mode = t->o.step_mode;
   rp.sample_cap = t->list_cap;
   rp.block_tot = t->o.deterministic ? (uint32_t*)t->block_tot.p : nullptr;
   return rp;
 }
 
-// forward -> compositing (+ loss) -> backward of the step in flight; with_rays = false: its ray batch is there already (the
-// previous step's Adam launch listed it)
-int train_batch(prv_trainer* t, bool backward, bool finish_reduce = true, int* dw_slots_out = nullptr, bool with_rays = true) {
+// Opens the step in flight: its ray batch.  The step's scalars are set by the previous step's last kernel (or by
+// train_begin_call); the plain path has a kernel of its own for that, which also clears the step's counter: it runs before the rays.
+int train_open_step(prv_trainer* t) {
+  prv::TrainScal* const sc = train_scal(t);
+  if (!t->sw.fast_forward) HIPCHK(t->ctx, prv::launch_train_begin(&sc->state, sc->sample_count, t->o.lr, t->o.beta1, t->o.beta2, t->stream));
+  HIPCHK(t->ctx, prv::launch_train_rays(train_rays_params(t, false), t->stream));
+  return PRV_OK;
+}
+
+// forward -> compositing (+ loss) -> backward of the step in flight, whose ray batch is there (train_open_step, or the previous
+// step's Adam launch listed it)
+int train_forward_backward(prv_trainer* t, prv::DwReduce reduce, int* dw_slots_out) {
   prv_ctx* c = t->ctx;
   Model& m = c->models[t->slot];
-  uint32_t* sample_count = (uint32_t*)t->scal.p;
+  prv::TrainScal* const sc = train_scal(t);
   const prv::TrainRaysParams rp = train_rays_params(t, false);
-  if (with_rays) {
-    // the step is opened by the previous step's last kernel (or by train_begin_call); the plain path opens it here
-    if (!t->fast_forward) HIPCHK(c, prv::launch_train_begin(train_state(t), sample_count, t->o.lr, t->o.beta1, t->o.beta2, t->stream));
-    HIPCHK(c, prv::launch_train_rays(rp, t->stream));
-  }
   prv::TrainTileParams tp{};
   tp.table = (const uint16_t*)m.table.p;
   tp.mlp = (const float*)t->mlp_f.p;
@@ -130,30 +127,28 @@ int train_batch(prv_trainer* t, bool backward, bool finish_reduce = true, int* d
   tp.n_features = t->desc.n_features;
   tp.rays = rp.rays;
   tp.samples = rp.samples;
-  tp.sample_count = sample_count;
-  tp.state = train_state(t);
+  tp.sample_count = sc->sample_count;
+  tp.state = &sc->state;
   tp.logits = (float4*)t->logits.p;
   tp.seeds = (const float4*)t->seeds.p;
   tp.table_grad = (float*)t->tab_g.p;
   tp.mlp_grad = (float*)t->mlp_g.p;
   tp.mlp_grad_partial = (float*)t->dw_part.p;
-  tp.stamps = (unsigned long long*)((char*)t->scal.p + 64); // dev only
-  tp.act = t->fast_forward && t->act_cap ? (uint4*)t->act.p : nullptr;
-  tp.bwd_frags = tp.act && t->reg_chain ? (const uint4*)((const uint16_t*)t->frags.p + (size_t)kNumFrags * kFragHalfs) : nullptr;
+  tp.stamps = sc->stamps; // dev only
+  tp.act = t->sw.fast_forward && t->act_cap ? (uint4*)t->act.p : nullptr;
+  tp.bwd_frags = tp.act && t->sw.reg_chain ? (const uint4*)((const uint16_t*)t->frags.p + (size_t)kNumFrags * kFragHalfs) : nullptr;
   tp.act_cap = t->act_cap;
   tp.sample_cap = t->list_cap;
   tp.table_grad_q = t->o.deterministic ? (long long*)t->tab_gq.p : nullptr;
-  static const bool live_off = getenv("PRV_TRAIN_TILE_SKIP") && atoi(getenv("PRV_TRAIN_TILE_SKIP")) == 0; // dev: A/B on one box
-  tp.tile_live = live_off ? nullptr : (uint8_t*)t->tile_live.p;
+  tp.tile_live = t->sw.tile_skip ? (uint8_t*)t->tile_live.p : nullptr;
   tp.scatter_ways = t->o.patch_w * t->o.patch_h > 1 ? 4 : 1;
-  static const int fwd_over = getenv("PRV_TRAIN_FWD_BLOCKS") ? atoi(getenv("PRV_TRAIN_FWD_BLOCKS")) : 0; // dev only
   // two blocks per CU (eight waves: a batch of 33 K samples is 1,040 wave-rounds): four per CU staged the 24 KB of fragments twice as often
   // for nothing -- round of five 0.4990 -> 0.4968 / 0.4970 -> 0.4914 ms on two boxes, of four 0.3746 -> 0.3658, one trainer and the 2^16-ray batch unchanged
-  if (t->fast_forward) HIPCHK(c, prv::launch_train_forward_fast(tp, (const half8*)t->frags.p, fwd_over > 0 ? fwd_over : c->n_cu * 2, t->stream));
-  else HIPCHK(c, prv::launch_train_tiles(tp, true, c->n_cu * 4, t->stream));
+  if (t->sw.fast_forward) HIPCHK(c, prv::launch_train_forward_fast(tp, (const half8*)t->frags.p, t->sw.fwd_blocks > 0 ? t->sw.fwd_blocks : c->n_cu * 2, t->stream));
+  else HIPCHK(c, prv::launch_train_forward(tp, c->n_cu * 4, t->stream));
   prv::TrainCompositeParams cp{};
   cp.rays = rp.rays;
-  cp.state = train_state(t);
+  cp.state = &sc->state;
   cp.n_rays = t->o.n_rays;
   cp.logits = tp.logits;
   cp.seeds = (float4*)t->seeds.p;
@@ -170,7 +165,7 @@ int train_batch(prv_trainer* t, bool backward, bool finish_reduce = true, int* d
   tp.ray_used = cp.ray_used;
   tp.n_rays = t->o.n_rays;
   tp.loss_part = (double*)t->loss_part.p; // its slices are added up by the step's last kernel (end_step) or launch_train_loss_finish
-  if (backward) HIPCHK(c, prv::launch_train_tiles(tp, false, bwd_blocks(t), t->stream, finish_reduce, dw_slots_out));
+  HIPCHK(c, prv::launch_train_backward(tp, bwd_blocks(t), reduce, dw_slots_out, t->stream));
   return PRV_OK;
 }
 
@@ -188,7 +183,7 @@ int train_density_refresh(prv_trainer* t) {
   dp.ema = (float*)t->ema.p;
   dp.occ = (uint32_t*)m.occ.p;
   // (eight persistent blocks per CU; 2, 4, 16 and 64 per CU measured the same in the round of five)
-  if (t->fast_forward) HIPCHK(c, prv::launch_density_refresh_fast(dp, t->desc.n_features, (const half8*)t->frags.p, c->n_cu * 8, t->stream));
+  if (t->sw.fast_forward) HIPCHK(c, prv::launch_density_refresh_fast(dp, t->desc.n_features, (const half8*)t->frags.p, c->n_cu * 8, t->stream));
   else HIPCHK(c, prv::launch_density_refresh(dp, t->desc.n_features, t->stream));
   return PRV_OK;
 }
@@ -203,9 +198,10 @@ int train_publish(prv_trainer* t) {
 // patch kernel has another block size; the plain path opens a step with a kernel of its own), and never a deterministic
 // trainer's: its batch is three launches of its own (prv::launch_train_rays), so the shared launch orders nothing.
 static bool can_list_ahead(const prv_trainer* t) {
-  static const bool off = getenv("PRV_TRAIN_LIST_AHEAD") && atoi(getenv("PRV_TRAIN_LIST_AHEAD")) == 0; // dev: A/B on one box
-  return !off && t->fast_forward && t->o.patch_w * t->o.patch_h <= 1 && !t->o.deterministic;
+  return t->sw.list_ahead && t->sw.fast_forward && t->o.patch_w * t->o.patch_h <= 1 && !t->o.deterministic;
 }
+
+static bool use_graph(const prv_trainer* t) { return t->sw.use_graph && !t->graph_failed; }
 
 // The launches of one optimiser step behind its ray batch (everything that varies per step is read from TrainState on the
 // device): forward, compositing, backward (+ loss slices), the table's Adam pass (+ the dW reduction's first stage,
@@ -215,26 +211,47 @@ int train_step_launches(prv_trainer* t, bool list_next) {
   Model& m = c->models[t->slot];
   int rc;
   int dw_slots = 0; // the backward launch's written dW slots: their first reduction stage rides on the table's Adam launch
-  if ((rc = train_batch(t, true, false, &dw_slots, false)) != PRV_OK) return rc;
+  if ((rc = train_forward_backward(t, prv::DwReduce::AdamPasses, &dw_slots)) != PRV_OK) return rc;
+  prv::TrainScal* const sc = train_scal(t);
   prv::AdamParams ap;
-  ap.state = train_state(t);
+  ap.state = &sc->state;
   ap.beta1 = t->o.beta1;
   ap.beta2 = t->o.beta2;
   ap.eps = t->o.eps;
-  ap.used = (unsigned long long*)((char*)t->scal.p + 8);
+  ap.used = &sc->used;
   ap.loss_part = (const double*)t->loss_part.p;
   ap.target_samples = t->o.target_samples;
   ap.n_rays = t->o.n_rays;
   const prv::TrainRaysParams next = train_rays_params(t, true);
-  HIPCHK(c, prv::launch_adam_table(ap, t->n_table, (float*)t->tab_g.p, (float*)t->tab_wmv.p, (uint16_t*)m.table.p, t->stream,
-                                   (const float*)t->dw_part.p, dw_slots, (float*)t->dw_part.p + (size_t)prv::train_dw_slots(bwd_blocks(t)) * PRV_MLP_HALFS,
-                                   list_next ? &next : nullptr, t->o.deterministic ? (long long*)t->tab_gq.p : nullptr));
+  float* const dw_stage = prv::train_dw_stage((float*)t->dw_part.p, bwd_blocks(t));
+  prv::AdamTableArgs at{};
+  at.n = t->n_table;
+  at.grad = (float*)t->tab_g.p;
+  at.wmv = (float*)t->tab_wmv.p;
+  at.w16 = (uint16_t*)m.table.p;
+  at.dw_partial = (const float*)t->dw_part.p;
+  at.dw_slots = dw_slots;
+  at.dw_stage = dw_stage;
+  at.next_rays = list_next ? &next : nullptr;
+  at.grad_q = t->o.deterministic ? (long long*)t->tab_gq.p : nullptr;
+  HIPCHK(c, prv::launch_adam_table(ap, at, t->stream));
   // the step's last kernel: the MLP's Adam pass; on the fast path every thread also writes its weight into the MFMA fragments of
   // the next forward / backward pass and thread 0 closes the step
-  HIPCHK(c, prv::launch_adam_mlp(ap, t->o.l2_reg, (float*)t->mlp_g.p, (float*)t->mlp_w.p, (float*)t->mlp_m.p,
-                                 (float*)t->mlp_v.p, (uint16_t*)m.mlp.p, (float*)t->mlp_f.p,
-                                 (const float*)t->dw_part.p + (size_t)prv::train_dw_slots(bwd_blocks(t)) * PRV_MLP_HALFS, t->fast_forward ? 0 : 1, t->stream,
-                                 t->fast_forward ? (uint16_t*)t->frags.p : nullptr, (const int*)t->frag_pos.p, (uint32_t*)t->scal.p, t->o.lr));
+  prv::AdamMlpArgs am{};
+  am.l2_reg = t->o.l2_reg;
+  am.grad = (float*)t->mlp_g.p;
+  am.w = (float*)t->mlp_w.p;
+  am.m = (float*)t->mlp_m.p;
+  am.v = (float*)t->mlp_v.p;
+  am.w16 = (uint16_t*)m.mlp.p;
+  am.w16_as_f32 = (float*)t->mlp_f.p;
+  am.stage = dw_stage;
+  am.end_of_step = t->sw.fast_forward ? 0 : 1;
+  am.frags = t->sw.fast_forward ? (uint16_t*)t->frags.p : nullptr;
+  am.frag_pos = (const int*)t->frag_pos.p;
+  am.sample_count = sc->sample_count;
+  am.lr = t->o.lr;
+  HIPCHK(c, prv::launch_adam_mlp(ap, am, t->stream));
   return PRV_OK;
 }
 
@@ -248,19 +265,13 @@ int train_enqueue_step(prv_trainer* t, bool last_of_call) {
   int rc;
   const bool refresh_follows = t->o.occ_every > 0 && (t->step + 1u) % (uint32_t)t->o.occ_every == 0;
   const bool list_next = can_list_ahead(t) && !last_of_call && !refresh_follows;
-  if (!t->rays_listed) {
-    const prv::TrainRaysParams rp = train_rays_params(t, false);
-    if (!t->fast_forward) { // (the plain path's opening kernel clears the step's counter: it must run before the rays)
-      HIPCHK(c, prv::launch_train_begin(train_state(t), (uint32_t*)t->scal.p, t->o.lr, t->o.beta1, t->o.beta2, t->stream));
-    }
-    HIPCHK(c, prv::launch_train_rays(rp, t->stream));
-  }
+  if (!t->rays_listed && (rc = train_open_step(t)) != PRV_OK) return rc;
   hipGraphExec_t& graph = t->step_graph[list_next ? 1 : 0];
-  if (t->use_graph && graph && t->graph_bwd_blocks[list_next ? 1 : 0] != bwd_blocks(t)) { // alone before, side by side now (or back): the count is baked into the graph
+  if (use_graph(t) && graph && t->graph_bwd_blocks[list_next ? 1 : 0] != bwd_blocks(t)) { // alone before, side by side now (or back): the count is baked into the graph
     (void)hipGraphExecDestroy(graph);
     graph = nullptr;
   }
-  if (t->use_graph && !graph) {
+  if (use_graph(t) && !graph) {
     t->graph_bwd_blocks[list_next ? 1 : 0] = bwd_blocks(t);
     hipGraph_t g = nullptr;
     // Captured on a stream of the context's that exists for nothing else, replayed on the trainer's own: a stream created with a
@@ -274,7 +285,7 @@ int train_enqueue_step(prv_trainer* t, bool last_of_call) {
       c->capture_stream = nullptr;
     }
     if (!c->capture_stream || hipStreamBeginCapture(c->capture_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-      t->use_graph = false;
+      t->graph_failed = true;
     } else {
       t->stream = c->capture_stream; // (the launchers below enqueue on t->stream)
       rc = train_step_launches(t, list_next);
@@ -282,12 +293,12 @@ int train_enqueue_step(prv_trainer* t, bool last_of_call) {
       const hipError_t e = hipStreamEndCapture(c->capture_stream, &g);
       if (rc != PRV_OK || e != hipSuccess || !g || hipGraphInstantiate(&graph, g, nullptr, nullptr, 0) != hipSuccess) {
         graph = nullptr;
-        t->use_graph = false; // fall back to plain launches for good
+        t->graph_failed = true; // fall back to plain launches for good
       }
       if (g) (void)hipGraphDestroy(g);
     }
   }
-  if (t->use_graph && graph) HIPCHK(c, hipGraphLaunch(graph, t->stream));
+  if (use_graph(t) && graph) HIPCHK(c, hipGraphLaunch(graph, t->stream));
   else if ((rc = train_step_launches(t, list_next)) != PRV_OK) return rc;
   t->rays_listed = list_next;
   t->step += 1; // mirrors TrainState::step, which the step's last kernel advances on the device
@@ -306,9 +317,9 @@ int train_begin_call(prv_trainer* t, float* losses_dev) {
     const double n = (double)t->step + 1.0;
     st.lr_t = (float)((double)t->o.lr * std::sqrt(1.0 - std::pow((double)t->o.beta2, n)) / (1.0 - std::pow((double)t->o.beta1, n)));
   }
-  HIPCHK(t->ctx, hipMemsetAsync(t->scal.p, 0, 8, t->stream)); // the two sample counters (a step lists into the word of its parity)
+  HIPCHK(t->ctx, hipMemsetAsync(train_scal(t)->sample_count, 0, sizeof(prv::TrainScal::sample_count), t->stream));
   t->rays_listed = false;
-  HIPCHK(t->ctx, hipMemcpyAsync(train_state(t), &st, sizeof(st), hipMemcpyHostToDevice, t->stream));
+  HIPCHK(t->ctx, hipMemcpyAsync(&train_scal(t)->state, &st, sizeof(st), hipMemcpyHostToDevice, t->stream));
   HIPCHK(t->ctx, hipStreamSynchronize(t->stream)); // `st` is a stack object
   return PRV_OK;
 }
@@ -319,11 +330,12 @@ int train_finish(prv_trainer* t, int n_steps, float* losses_host) {
   unsigned long long used = 0;
   if (losses_host) HIPCHK(c, hipMemcpyAsync(losses_host, t->losses.p, (size_t)n_steps * 4, hipMemcpyDeviceToHost, t->stream));
   prv::TrainState st{};
-  HIPCHK(c, hipMemcpyAsync(&used, (char*)t->scal.p + 8, 8, hipMemcpyDeviceToHost, t->stream));
-  HIPCHK(c, hipMemcpyAsync(&st, train_state(t), sizeof(st), hipMemcpyDeviceToHost, t->stream));
+  prv::TrainScal* const sc = train_scal(t);
+  HIPCHK(c, hipMemcpyAsync(&used, &sc->used, sizeof(used), hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(c, hipMemcpyAsync(&st, &sc->state, sizeof(st), hipMemcpyDeviceToHost, t->stream));
   uint32_t listed = 0;
-  const bool timing = getenv("PRV_TRAIN_TIMING") != nullptr;
-  if (timing) HIPCHK(c, hipMemcpyAsync(&listed, (char*)t->scal.p + 28, 4, hipMemcpyDeviceToHost, t->stream));
+  const bool timing = t->sw.timing;
+  if (timing) HIPCHK(c, hipMemcpyAsync(&listed, &sc->listed, sizeof(listed), hipMemcpyDeviceToHost, t->stream));
   HIPCHK(c, hipStreamSynchronize(t->stream));
   if (timing) // dev: how many of the samples the forward pass evaluated lie beyond their ray's termination (zero gradient seeds)
     fprintf(stderr, "prv_train_steps: last batch of slot %d: %u samples listed (forward pass), %llu composited before termination\n", t->slot, listed, used);
@@ -358,10 +370,45 @@ void prv_trainer::close() {
   stream = nullptr;
 }
 
+// Rows in allocation order: the parked pool hands its buffers out by size, oldest first, so the order decides which one a request gets.
+std::vector<prv_trainer::BufferRow> prv_trainer::buffer_table() const {
+  using T = prv_trainer;
+  const size_t ns = list_cap, n_rays = (size_t)o.n_rays, R = (size_t)desc.occ_res, pp = (size_t)std::max(o.patch_w * o.patch_h, 1);
+  return {
+      {&T::cams, sizeof(CamDev) * (size_t)n_img, false},
+      {&T::tab_wmv, (n_table + 3) / 4 * 48, true}, // {w[4], m[4], v[4]} per group of four scalars
+      {&T::tab_g, n_table * 4, true},
+      {&T::mlp_w, PRV_MLP_HALFS * 4, false},
+      {&T::mlp_m, PRV_MLP_HALFS * 4, true},
+      {&T::mlp_v, PRV_MLP_HALFS * 4, true},
+      {&T::mlp_g, PRV_MLP_HALFS * 4, true},
+      {&T::mlp_f, PRV_MLP_HALFS * 4, false},
+      {&T::ema, R * R * R * 4, true},
+      {&T::rays, sizeof(prv::TrainRay) * n_rays, false},
+      {&T::samples, ns * 8, false},
+      {&T::logits, ns * 16, false},
+      {&T::seeds, ns * 16, false},
+      {&T::ray_loss, n_rays * 4, false},
+      {&T::ray_used, n_rays * 4, false},
+      {&T::scal, sizeof(prv::TrainScal), true},
+      {&T::losses, 0, false}, // a call's per-step losses: grown by prv_train_steps_multi
+      {&T::dw_part, ((size_t)prv::train_dw_slots(ctx->n_cu * kBwdBlocksPerCu) + 16) * PRV_MLP_HALFS * 4, false}, // slots + the reduction's 16 group sums
+      {&T::loss_part, (n_rays + 1023) / 1024 * 16, false},
+      {&T::frags, (size_t)(kNumFrags + prv::kBwdFrags) * kFragHalfs * 2, false}, // forward fragments, then the backward ones
+      {&T::slot_of, pp > 1 ? ns * 4 : 0, false}, // patches: list position of (ray, k-th live sample)
+      {&T::frag_pos, (size_t)2 * PRV_MLP_HALFS * sizeof(int), false}, // every weight's place in the forward / backward fragments
+      {&T::tab_gq, o.deterministic ? n_table * 8 : 0, true}, // the table gradient in 64-bit fixed point (prv_train.hip: table_grad_add)
+      // a word per block of the ray launch, whichever kernel lists the batch (four rays, or a patch, per block: TrainRaysParams::block_tot)
+      {&T::block_tot, o.deterministic ? std::max((n_rays + 3) / 4, (n_rays + pp - 1) / pp) * 4 : 0, true},
+      {&T::tile_live, (ns + 31) / 32 + 64, true}, // one byte per 32-sample tile of the list (TrainTileParams::tile_live)
+      {&T::act, (size_t)act_cap / 32 * prv::kActTileBytes, false}, // the forward pass's kept activations
+  };
+}
+
 void prv_trainer::detach() {
   if (stream) (void)hipStreamSynchronize(stream);
   close();
-  for (Buffer* b : buffers()) b->reset();
+  for (const BufferRow& r : buffer_table()) (this->*r.buf).reset();
 }
 
 // the trainer's stream (idle by now) stays with the context for the next trainer -- creating a stream with a queue of its own
@@ -372,7 +419,7 @@ void prv_trainer::retire() {
   if (keep) stream = nullptr;
   close();
   if (keep) ctx->idle_queues.push_back(keep);
-  for (Buffer* b : buffers()) ctx->parked.park(std::move(*b));
+  for (const BufferRow& r : buffer_table()) ctx->parked.park(std::move(this->*r.buf));
 }
 
 extern "C" {
@@ -453,23 +500,19 @@ int prv_train_create(prv_ctx* c, int slot, const prv_camset* cs, const uint8_t* 
   t->n_table = m.table_halfs;
   t->n_active = (uint32_t)o->n_rays;
   if (o->target_samples > 0) t->n_active = std::min<uint32_t>(t->n_active, std::max<uint32_t>(1u, (uint32_t)o->target_samples / (uint32_t)o->n_samples));
-  if (const char* e = getenv("PRV_TRAIN_GRAPH")) t->use_graph = atoi(e) != 0;
-  if (const char* e = getenv("PRV_TRAIN_FAST_FWD")) t->fast_forward = atoi(e) != 0;
-  if (const char* e = getenv("PRV_TRAIN_REG_CHAIN")) t->reg_chain = atoi(e) != 0;
-  if (const char* e = getenv("PRV_TRAIN_PATCH_JITTER")) t->patch_ray_jitter = !strcmp(e, "ray");
+  t->sw = prv::train_switches_from_env();
   // The trainer's stream gets a hardware queue of its own.  Streams from hipStreamCreate share the runtime's pool of four
   // queues: five members stepping side by side sat on three of them, two pairs taking turns inside their queue.  A stream
   // created with a CU mask owns its queue -- the mask names every CU (restricting a member to a share of the CUs was measured
   // too, and is slower in every split: profiles/NOTES.md, round 5): round of five 0.548 -> 0.527 ms on one box.
   // PRV_TRAIN_OWN_QUEUE=0 (dev) keeps the pooled stream for an A/B on one box.
-  const bool own_queue = !(getenv("PRV_TRAIN_OWN_QUEUE") && atoi(getenv("PRV_TRAIN_OWN_QUEUE")) == 0);
   hipError_t se = hipErrorUnknown;
-  if (own_queue && !c->idle_queues.empty()) { // a destroyed trainer's (prv_trainer::retire)
+  if (t->sw.own_queue && !c->idle_queues.empty()) { // a destroyed trainer's (prv_trainer::retire)
     t->stream = c->idle_queues.back();
     c->idle_queues.pop_back();
     t->own_queue = true;
     se = hipSuccess;
-  } else if (own_queue) {
+  } else if (t->sw.own_queue) {
     const std::vector<uint32_t> every_cu((size_t)(c->n_cu + 31) / 32, 0xffffffffu); // bits beyond the CU count are ignored
     se = hipExtStreamCreateWithCUMask(&t->stream, (uint32_t)every_cu.size(), every_cu.data());
     t->own_queue = se == hipSuccess;
@@ -484,57 +527,34 @@ int prv_train_create(prv_ctx* c, int slot, const prv_camset* cs, const uint8_t* 
   uint64_t total = 0;
   compute_levels(m.desc, lv, &total);
   for (int l = 0; l < m.desc.n_levels; l++) t->levels[l] = prv::LevelCanon{lv[l].scale, lv[l].res, lv[l].offset, lv[l].size, lv[l].hashed};
-  const size_t R = (size_t)m.desc.occ_res, n_cells = R * R * R;
   // the step's sample list: every ray's every sample under the fixed rule; under the engine's rule a ray may list 1024 steps but
   // the budget keeps a step near target_samples -- 2^24 (64 x the default budget), and a batch beyond it fails loudly (TrainState::overflow)
   size_t ns = (size_t)o->n_rays * (size_t)o->n_samples;
   if (o->step_mode == PRV_STEP_NGP) ns = std::min<size_t>(ns, prv::kNgpListCap);
   if (ns > 0xffffffffull) return fail(c, PRV_E_INVALID, "n_rays x n_samples must stay below 2^32");
   t->list_cap = (uint32_t)ns;
-  struct { Buffer* b; size_t n; } need[] = {
-      {&t->cams, sizeof(CamDev) * cs->cams.size()}, {&t->tab_wmv, (t->n_table + 3) / 4 * 48}, // {w[4], m[4], v[4]} per group of four scalars
-      {&t->tab_g, t->n_table * 4}, {&t->mlp_w, PRV_MLP_HALFS * 4},
-      {&t->mlp_m, PRV_MLP_HALFS * 4}, {&t->mlp_v, PRV_MLP_HALFS * 4}, {&t->mlp_g, PRV_MLP_HALFS * 4},
-      {&t->mlp_f, PRV_MLP_HALFS * 4}, {&t->ema, n_cells * 4}, {&t->rays, sizeof(prv::TrainRay) * (size_t)o->n_rays},
-      {&t->samples, ns * 8}, {&t->logits, ns * 16}, {&t->seeds, ns * 16}, {&t->ray_loss, (size_t)o->n_rays * 4},
-      {&t->ray_used, (size_t)o->n_rays * 4}, {&t->scal, kScalBytes}, {&t->dw_part, ((size_t)prv::train_dw_slots(c->n_cu * kBwdBlocksPerCu) + 16) * PRV_MLP_HALFS * 4}, // slots + the reduction's 16 group sums
-      {&t->loss_part, (size_t)((o->n_rays + 1023) / 1024) * 16}, {&t->frags, (size_t)(kNumFrags + prv::kBwdFrags) * kFragHalfs * 2}}; // forward fragments, then the backward ones
-  for (auto& n : need)
-    if ((rc = train_buffer(c, *n.b, n.n)) != PRV_OK) return rc;
-  if (t->o.patch_w * t->o.patch_h > 1 && (rc = train_buffer(c, t->slot_of, ns * 4)) != PRV_OK) return rc; // list position of (ray, k-th live sample)
-  if ((rc = train_buffer(c, t->frag_pos, (size_t)2 * PRV_MLP_HALFS * sizeof(int))) != PRV_OK) return rc; // every weight's place in the forward / backward fragments
-  if (o->deterministic && (rc = train_buffer(c, t->tab_gq, t->n_table * 8)) != PRV_OK) return rc;
-  if (o->deterministic) { // a word per block of the ray launch, whichever kernel lists the batch (four rays, or a patch, per block)
-    const size_t pp = (size_t)std::max(t->o.patch_w * t->o.patch_h, 1), nr = (size_t)o->n_rays;
-    if ((rc = train_buffer(c, t->block_tot, std::max((nr + 3) / 4, (nr + pp - 1) / pp) * 4)) != PRV_OK) return rc;
-  }
-  if ((rc = train_buffer(c, t->tile_live, ((size_t)t->list_cap + 31) / 32 + 64)) != PRV_OK) return rc;
   // The forward pass keeps its activations for the backward pass (528 B per sample: 512 of activations + the position; PRV_TRAIN_KEEP_ACT=0: recompute).
   // Sized for the step the sample budget aims at, with room for the adaptive ray count to overshoot (it may double from
   // one step to the next); tiles beyond the buffer -- the all-occupied first steps of a large n_rays -- are recomputed.
-  t->act_cap = 0;
-  bool keep_act = t->fast_forward;
-  if (const char* e = getenv("PRV_TRAIN_KEEP_ACT")) keep_act = keep_act && atoi(e) != 0;
-  if (keep_act) {
+  if (t->sw.fast_forward && t->sw.keep_act) {
     size_t cap = o->target_samples > 0 ? std::max<size_t>((size_t)4 * (size_t)o->target_samples, (size_t)1 << 20) : (size_t)1 << 22;
-    if (const char* e = getenv("PRV_TRAIN_ACT_CAP")) cap = (size_t)std::max(32, atoi(e)); // tests: force the two-launch backward pass
-    cap = std::min(std::min(cap, (size_t)1 << 22), (ns + 31) / 32 * 32) / 32 * 32;
-    if ((rc = train_buffer(c, t->act, cap / 32 * prv::kActTileBytes)) != PRV_OK) return rc;
-    t->act_cap = (uint32_t)cap;
+    if (t->sw.act_cap) cap = (size_t)t->sw.act_cap; // tests: force the two-launch backward pass
+    t->act_cap = (uint32_t)(std::min(std::min(cap, (size_t)1 << 22), (ns + 31) / 32 * 32) / 32 * 32);
   }
+  // a buffer a destroyed trainer of this context left behind (same size), else a new allocation (train_buffer); what has to
+  // start at zero is zeroed whole, not only the bytes asked for
+  const std::vector<prv_trainer::BufferRow> table = t->buffer_table();
+  for (const auto& r : table)
+    if (r.bytes && (rc = train_buffer(c, t->*r.buf, r.bytes)) != PRV_OK) return rc;
   std::vector<CamDev> cams(cs->cams.size());
   for (size_t i = 0; i < cams.size(); i++) cams[i] = cam_at(cs, (int)i, width, height);
   hipError_t e = hipMemcpyAsync(t->cams.p, cams.data(), sizeof(CamDev) * cams.size(), hipMemcpyHostToDevice, c->stream);
-  Buffer* zero[] = {&t->tab_wmv, &t->tab_g, &t->mlp_m, &t->mlp_v, &t->mlp_g, &t->ema, &t->scal}; // scal: the loss ticket starts at 0
-  for (Buffer* b : zero)
-    if (e == hipSuccess) e = hipMemsetAsync(b->p, 0, b->bytes, c->stream);
-  if (e == hipSuccess && t->tab_gq.p) e = hipMemsetAsync(t->tab_gq.p, 0, t->tab_gq.bytes, c->stream);
-  if (e == hipSuccess && t->block_tot.p) e = hipMemsetAsync(t->block_tot.p, 0, t->block_tot.bytes, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(t->tile_live.p, 0, t->tile_live.bytes, c->stream);
+  for (const auto& r : table)
+    if (e == hipSuccess && r.bytes && r.zeroed) e = hipMemsetAsync((t->*r.buf).p, 0, (t->*r.buf).bytes, c->stream);
   if (e == hipSuccess) e = prv::launch_widen_table((const uint16_t*)m.table.p, t->n_table, (float*)t->tab_wmv.p, c->stream);
   if (e == hipSuccess) e = prv::launch_widen((const uint16_t*)m.mlp.p, PRV_MLP_HALFS, (float*)t->mlp_w.p, c->stream);
   if (e == hipSuccess) e = prv::launch_widen((const uint16_t*)m.mlp.p, PRV_MLP_HALFS, (float*)t->mlp_f.p, c->stream);
-  if (e == hipSuccess) e = prv::launch_prepack_frags((const uint16_t*)m.mlp.p, m.desc.n_features, (uint16_t*)t->frags.p, nullptr, nullptr, 0.f, c->stream);
+  if (e == hipSuccess) e = prv::launch_prepack_frags((const uint16_t*)m.mlp.p, m.desc.n_features, (uint16_t*)t->frags.p, c->stream);
   if (e == hipSuccess) e = prv::launch_frag_positions(m.desc.n_features, (int*)t->frag_pos.p, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) return fail(c, PRV_E_HIP, "trainer setup: %s", hipGetErrorString(e));
@@ -566,7 +586,7 @@ int prv_train_steps_multi(prv_trainer** ts, int n_trainers, int n_steps, float* 
   for (int k = 0; k < n_trainers; k++) ts[k]->side_by_side = n_trainers > 1;
   for (int k = 0; k < n_trainers; k++)
     if ((rc = train_begin_call(ts[k], (float*)ts[k]->losses.p)) != PRV_OK) return rc;
-  const bool timing = getenv("PRV_TRAIN_TIMING") != nullptr; // dev: is the host or the GPU the slower side?
+  const bool timing = ts[0]->sw.timing; // dev: is the host or the GPU the slower side?
   const auto t0 = std::chrono::steady_clock::now();
   for (int i = 0; i < n_steps; i++)
     for (int k = 0; k < n_trainers; k++)
@@ -589,20 +609,21 @@ int prv_train_gradients(prv_trainer* t, float* table_grad_host, float* mlp_grad_
   prv_ctx* c = t->ctx;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  float* loss_dev = (float*)((char*)t->scal.p + 16);
-  if ((rc = train_begin_call(t, loss_dev)) != PRV_OK) return rc;
-  if ((rc = train_batch(t, true)) != PRV_OK) return rc;
-  HIPCHK(c, prv::launch_train_loss_finish((const double*)t->loss_part.p, t->o.n_rays, train_state(t), (unsigned long long*)((char*)t->scal.p + 8), t->stream));
+  prv::TrainScal* const sc = train_scal(t);
+  if ((rc = train_begin_call(t, &sc->loss)) != PRV_OK) return rc;
+  if ((rc = train_open_step(t)) != PRV_OK) return rc;
+  if ((rc = train_forward_backward(t, prv::DwReduce::Here, nullptr)) != PRV_OK) return rc;
+  HIPCHK(c, prv::launch_train_loss_finish((const double*)t->loss_part.p, t->o.n_rays, &sc->state, &sc->used, t->stream));
   unsigned long long used = 0;
   if (t->o.deterministic) HIPCHK(c, prv::launch_grad_q_to_f32((long long*)t->tab_gq.p, t->n_table, (float*)t->tab_g.p, t->stream));
   if (table_grad_host) HIPCHK(c, hipMemcpyAsync(table_grad_host, t->tab_g.p, t->n_table * 4, hipMemcpyDeviceToHost, t->stream));
   if (mlp_grad_host) HIPCHK(c, hipMemcpyAsync(mlp_grad_host, t->mlp_g.p, PRV_MLP_HALFS * 4, hipMemcpyDeviceToHost, t->stream));
-  if (loss) HIPCHK(c, hipMemcpyAsync(loss, loss_dev, 4, hipMemcpyDeviceToHost, t->stream));
-  HIPCHK(c, hipMemcpyAsync(&used, (char*)t->scal.p + 8, 8, hipMemcpyDeviceToHost, t->stream));
+  if (loss) HIPCHK(c, hipMemcpyAsync(loss, &sc->loss, sizeof(float), hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(c, hipMemcpyAsync(&used, &sc->used, sizeof(used), hipMemcpyDeviceToHost, t->stream));
   HIPCHK(c, hipMemsetAsync(t->tab_g.p, 0, t->n_table * 4, t->stream));
   HIPCHK(c, hipMemsetAsync(t->mlp_g.p, 0, PRV_MLP_HALFS * 4, t->stream));
   prv::TrainState st{};
-  HIPCHK(c, hipMemcpyAsync(&st, train_state(t), sizeof(st), hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(c, hipMemcpyAsync(&st, &sc->state, sizeof(st), hipMemcpyDeviceToHost, t->stream));
   HIPCHK(c, hipStreamSynchronize(t->stream));
   t->samples_last = used;
   if (st.overflow) return fail(c, PRV_E_STATE, "the ray batch listed more than %u samples (the sample list's capacity)", t->list_cap);
@@ -622,7 +643,7 @@ int prv_train_refresh_occupancy(prv_trainer* t) try {
 int prv_train_debug_stamps(prv_trainer* t, unsigned long long* out64) try {
   if (!t || !t->ctx || !out64) return PRV_E_INVALID;
   prv_ctx* c = t->ctx;
-  HIPCHK(c, hipMemcpy(out64, (char*)t->scal.p + 64, 64 * 8, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(out64, train_scal(t)->stamps, sizeof(prv::TrainScal::stamps), hipMemcpyDeviceToHost));
   return PRV_OK;
 } catch (...) { return caught(t ? t->ctx : nullptr); }
 

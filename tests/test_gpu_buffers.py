@@ -84,6 +84,43 @@ def test_a_context_destroyed_first_leaves_inert_handles_and_nothing_else(oracle)
     assert held() == start
 
 
+def test_a_trainer_built_from_parked_buffers_equals_one_built_from_fresh_memory(oracle):
+    """A destroyed trainer's buffers wait in its context for the next trainer, which takes them by size: whatever has to start
+    at zero is zeroed when a trainer is created, wherever its memory comes from.  Context A runs a patch trainer on slot 0 first
+    (its slot_of, tile_live, ray_loss, ... are parked with their last contents), then a deterministic trainer on slot 1, whose
+    tab_gq, block_tot and tile_live come out of that pool; context B runs the deterministic trainer alone, on fresh
+    allocations.  Deterministic training is reproducible bit for bit, so the two must agree in every bit."""
+    d = api.field_desc(**FIELD)
+    tms, scale, offset = util.hemisphere_transforms(oracle, util.fibonacci_hemisphere(4))
+    pixels = np.random.default_rng(11).integers(0, 256, (4, H, W, 4), dtype=np.uint8)
+    shape = dict(n_rays=256, n_samples=24, step_mode=L.STEP_FIXED_S)
+
+    def run(parked_first):
+        start = held()
+        c = api.Context(0)
+        for slot in (0, 1):
+            c.fresh_model(slot, d, util.SEED_A)
+        cams = c.cameras_from_matrices(tms, util.FOV_X, W, H, scale, offset)
+        imgs = c.torch.from_numpy(pixels)
+        if parked_first:
+            first = api.Trainer(c, 0, cams, imgs, api.train_opts(patch_w=2, patch_h=2, **shape))
+            assert np.isfinite(first.steps(2)).all()
+            first.close()
+        tr = api.Trainer(c, 1, cams, imgs, api.train_opts(deterministic=1, occ_every=4, **shape))
+        losses = tr.steps(4)
+        got = [losses, *tr.master(), *c.export_model(1, d), np.uint64(tr.info()["samples_last"])]
+        assert np.isfinite(losses).all() and tr.info()["samples_last"] > 0
+        tr.close()
+        cams.close()
+        c.close()
+        assert held() == start
+        return [np.ascontiguousarray(a).tobytes() for a in got]
+
+    from_pool, fresh = run(True), run(False)
+    for name, a, b in zip(("losses", "master table", "master MLP", "fp16 table", "fp16 MLP", "occupancy", "samples_last"), from_pool, fresh):
+        assert a == b, name
+
+
 def test_a_refused_call_holds_nothing_afterwards(oracle):
     """ordinary error returns that come after an allocation can have happened, as the suites of their families make them"""
     start = held()
