@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PRV_ABI_VERSION 5 /* 2: prv_field_desc.per_level_scale; 3: prv_render_opts.step_mode, prv_stats.samples_live; 4: prv_train_opts.patch_w / patch_h; 5: prv_train_opts.step_mode / deterministic (still 5: prv_train_create accepting lr = 0, which it refused, changes no layout and no call that worked; nor do the prv_coverage_* entry points: additive; nor prv_mesh_from_arrays, prv_mesh_depth and prv_coverage_create_occluded: additive too; nor prv_debug_live_bytes) */
+#define PRV_ABI_VERSION 5 /* 2: prv_field_desc.per_level_scale; 3: prv_render_opts.step_mode, prv_stats.samples_live; 4: prv_train_opts.patch_w / patch_h; 5: prv_train_opts.step_mode / deterministic (still 5: prv_train_create accepting lr = 0, which it refused, changes no layout and no call that worked; nor do the prv_coverage_* entry points: additive; nor prv_mesh_from_arrays, prv_mesh_depth and prv_coverage_create_occluded: additive too; nor prv_debug_live_bytes; nor prv_mesh_set_colors and prv_mesh_render: additive) */
 
 /* error codes (0 = ok, < 0 = error; message via prv_last_error) */
 #define PRV_OK 0
@@ -760,6 +760,51 @@ int prv_coverage_create_occluded(prv_ctx* ctx, const float* xyz_dev, uint64_t n_
                                  const int* view_ids, int n_views, int width, int height, const prv_coverage_opts* opts,
                                  float* depth_out_dev, prv_coverage** out);
 
+/* ---- mesh colour images: a vertex-coloured surface seen from a camera ----------- */
+/* replaces: Perception_3D::render (main.cpp:68-96) for an object held as a SURFACE -- prv_splat_points is the same screenshot
+ * for a cloud: square splats have holes at close range and need a point size; a mesh has neither.  With convertToAlpha and the
+ * flip, these are the rgbaClip_<i>.png images of a mesh (`gt_surface: mesh` in the planner's mode 3).
+ * prv_mesh_set_colors: one RGB byte triple per vertex from the host; the mesh then HAS colours (prv_mesh_get, _save and _filter
+ * see them).  A marching-cubes mesh extracted with colours has them already.  Errors, PRV_E_INVALID: a count that is not the
+ * mesh's, a NULL array with a non-zero count.
+ * ARITHMETIC CONTRACT of prv_mesh_render.  A visibility buffer in two stages; every float64 operation below is one IEEE
+ * operation in the order written, the integers are exact.
+ *   stage A: the vertices, the snap, the edge functions, the inside test and z are those of the depth contract above, bit for
+ *     bit.  The pixel takes min(pixel, key) on a uint64 buffer, key = ((uint64)bits of z << 32) | triangle id, all ones at the
+ *     start.  A pixel is empty iff the high word of its key is 0xFFFFFFFF.
+ *     TIE RULE: the nearest depth wins; among triangles with equal depth bits at a pixel, the lowest triangle id.
+ *   stage B, per pixel of a view: empty -> the background.  Otherwise the triangle named by the low word is set up again for the
+ *     view (a, b, c: its ORIENTED vertices -- where the depth contract exchanges b and c, their colours go with them), w_a, w_b,
+ *     w_c are formed at the pixel's centre, and
+ *         p_a = (double)w_a * i_a;  p_b = (double)w_b * i_b;  p_c = (double)w_c * i_c
+ *         iz  = (p_a + p_b) + p_c                              -- the depth contract's iz, bit for bit
+ *         c_k = ((p_a * (double)C_a[k] + p_b * (double)C_b[k]) + p_c * (double)C_c[k]) / iz      for channel k of r, g, b
+ *         byte_k = (uint8)min(255.0, floor(c_k + 0.5))
+ *     with C_v the colour bytes of vertex v: perspective-correct (hyperbolic) Gouraud interpolation.
+ *   output: RGBA8.  A covered pixel is (r, g, b, 255); the background is 255, 255, 255, 0; a covered pixel whose three bytes
+ *     come out exactly 255, 255, 255 gets alpha 0 as well (convertToAlpha's rule, as prv_splat_points applies it).  flip180 puts
+ *     pixel (x, y) at (width - 1 - x, height - 1 - y), as prv_splat_points does.
+ *   planes (optional, written by the same lane, NEVER flipped, like prv_mesh_depth's output): depth_out_dev = the high word of
+ *     the key as float32, 0 = empty; tri_out_dev = the low word, 0xFFFFFFFF = empty.
+ *   EQUALITY WITH prv_mesh_depth: the depth plane equals prv_mesh_depth of the same mesh, views and size bit for bit (the high
+ *     word of a minimum over keys is the minimum over high words).
+ * HOW IT RUNS (no byte depends on it): stage A is the two raster kernels of prv_mesh_depth on the 64-bit key, with the same
+ * small_max, list and chunks (PRV_RASTER_SMALL_PIXELS, PRV_RASTER_LIST_ENTRIES); stage B is one lane per pixel, no atomics.  The
+ * views are batched on the z-buffer budget of prv_coverage_create at 8 bytes per pixel (PRV_COVERAGE_ZBUF_BYTES).  Two calls
+ * return identical bytes.  Synchronises.  An empty mesh (with colours set) gives all background.  prv_debug_raster_stats reports
+ * the call as it does prv_mesh_depth.
+ * Errors: what prv_mesh_depth refuses, with its messages (a NULL mesh, a mesh of another context, a lens camera, a bad size or
+ * view list, a NULL or host pointer where a device pointer is required; a mesh that outlives its context: PRV_E_STATE), and a
+ * mesh without colours: PRV_E_INVALID, "call prv_mesh_set_colors".
+ * LIMITS: PINHOLE ONLY; NO NEAR-PLANE CLIPPING (a triangle with a vertex behind or at the camera is dropped whole for that view);
+ * GOURAUD VERTEX COLOURS ONLY -- no textures, NO LIGHTING, no anti-aliasing: a pixel shows the surface at its centre;
+ * SINGLE-RANK. */
+/* rgb_host: n_vertices*3 bytes; n_vertices must equal the mesh's; the mesh then has colours (prv_mesh_get, _save, _filter see them) */
+int prv_mesh_set_colors(prv_mesh* m, const uint8_t* rgb_host, uint64_t n_vertices);
+/* out_rgba8_dev: n_views*h*w*4 bytes; depth_out_dev / tri_out_dev optional (NULL), n_views*h*w each */
+int prv_mesh_render(prv_ctx* ctx, const prv_mesh* m, const prv_camset* cs, const int* view_ids, int n_views, int width, int height,
+                    int flip180, uint8_t* out_rgba8_dev, float* depth_out_dev, uint32_t* tri_out_dev);
+
 /* ---- several GPUs: view sharding + one all-gather ----------------------------- */
 /* replaces: nothing in the reference -- its loops over the candidates are serial (main.cpp:2045-2094, 2105-2158;
  * run.py:293) and it has no multi-GPU path.  One process per GPU (RANK / WORLD_SIZE / LOCAL_RANK as torchrun exports
@@ -908,7 +953,7 @@ int prv_debug_raygen(prv_ctx* ctx, const prv_camset* cs, int view, int width, in
 int prv_debug_mesh_stages(prv_ctx* ctx, float ms[4]);
 /* hook + compress rounds the mesh's labelling took (0: no triangles); PRV_E_STATE before prv_mesh_components has run */
 int prv_debug_mesh_component_rounds(const prv_mesh* m, int* rounds);
-/* the last prv_mesh_depth / prv_coverage_create_occluded call: out[0] = (view, triangle) pairs rasterised, out[1] = those whose
+/* the last prv_mesh_depth / prv_mesh_render / prv_coverage_create_occluded call: out[0] = (view, triangle) pairs rasterised, out[1] = those whose
  * clipped pixel box held more than small_max pixels (the large path took them) */
 int prv_debug_raster_stats(prv_ctx* ctx, uint64_t out[2]);
 /* bytes of device memory the library holds in this process: every context's workspaces and models, every handle's arrays,

@@ -214,6 +214,8 @@ SIGNATURES = {
     "prv_coverage_destroy": (None, [_vp]),
     "prv_mesh_from_arrays": (_i, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _P(_vp)]),
     "prv_mesh_depth": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "prv_mesh_set_colors": (_i, [_vp, _vp, C.c_uint64]),
+    "prv_mesh_render": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "prv_coverage_create_occluded": (_i, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, _i, _i, _i, _P(CoverageOpts), _vp, _P(_vp)]),
     "prv_debug_raster_stats": (_i, [_vp, _vp]),
     "prv_debug_live_bytes": (C.c_uint64, []),

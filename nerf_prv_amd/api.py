@@ -638,14 +638,22 @@ class Context:
         return Coverage(self, h, depth)
 
     # -- a rasterised surface (include/prv.h, mesh depth and the mesh occluder)
-    def mesh_from_arrays(self, vertices, triangles):
-        """a Mesh from host arrays in the ENGINE frame: vertices (n, 3) float32, triangles (m, 3) uint32 (prv_mesh_from_arrays)"""
+    def mesh_from_arrays(self, vertices, triangles, colors=None):
+        """a Mesh from host arrays in the ENGINE frame: vertices (n, 3) float32, triangles (m, 3) uint32 (prv_mesh_from_arrays);
+        colors (n, 3) uint8, if given, become its vertex colours (Mesh.set_colors)"""
         v = np.ascontiguousarray(np.asarray(vertices, np.float32).reshape(-1, 3))
         tr = np.ascontiguousarray(np.asarray(triangles, np.uint32).reshape(-1, 3))
         h = C.c_void_p()
         self._chk(self.lib.prv_mesh_from_arrays(self.handle, _ptr(v) if len(v) else None, len(v), _ptr(tr) if len(tr) else None, len(tr),
                                                 C.byref(h)))
-        return Mesh(self, h)
+        m = Mesh(self, h)
+        if colors is not None:
+            try:
+                m.set_colors(colors)
+            except Exception:
+                m.close()
+                raise
+        return m
 
     def mesh_depth(self, mesh, camset, view_ids, width, height):
         """the nearest surface depth of `mesh` per pixel and view (prv_mesh_depth) -> float32 [n_views, h, w] on the device, 0 =
@@ -656,8 +664,25 @@ class Context:
         self._chk(self.lib.prv_mesh_depth(self.handle, mesh.handle, camset.handle, _ptr(ids), len(ids), int(width), int(height), _ptr(depth)))
         return depth
 
+    def mesh_render(self, mesh, camset, view_ids, width, height, flip180=False, want_depth=False, want_triangles=False):
+        """colour images of a vertex-coloured `mesh` (prv_mesh_render) -> uint8 [n_views, h, w, 4] on the device: the nearest
+        triangle's colours interpolated perspective-correctly, alpha 255; background and exactly-white pixels 255, 255, 255, 0;
+        flip180 turns each image by 180 degrees as splat_points does.  With want_depth / want_triangles a tuple that also holds
+        the float32 depth (0 = empty) and / or the int32 triangle-id plane (-1, i.e. 0xFFFFFFFF, = empty), both [n_views, h, w]
+        and never flipped.  Pinhole cameras only"""
+        t = self.torch
+        ids = self._ids(camset, view_ids)
+        shape = (len(ids), int(height), int(width))
+        rgba = t.empty(shape + (4,), dtype=t.uint8, device=self.device)
+        depth = t.empty(shape, dtype=t.float32, device=self.device) if want_depth else None
+        tri = t.empty(shape, dtype=t.int32, device=self.device) if want_triangles else None
+        self._chk(self.lib.prv_mesh_render(self.handle, mesh.handle, camset.handle, _ptr(ids), len(ids), int(width), int(height),
+                                           int(bool(flip180)), _ptr(rgba), _ptr(depth), _ptr(tri)))
+        out = (rgba,) + ((depth,) if want_depth else ()) + ((tri,) if want_triangles else ())
+        return out if len(out) > 1 else rgba
+
     def raster_stats(self):
-        """the last mesh_depth / mesh-occluded coverage call: (view, triangle) pairs rasterised, and those the large path took"""
+        """the last mesh_depth / mesh_render / mesh-occluded coverage call: (view, triangle) pairs rasterised, and those the large path took"""
         out = (C.c_uint64 * 2)()
         self._chk(self.lib.prv_debug_raster_stats(self.handle, out))
         return dict(pairs=int(out[0]), large=int(out[1]))
@@ -729,6 +754,12 @@ class Mesh(_Handle):
         if rc != 0:
             _mesh_file_error(rc)
         return nv.value, nt.value
+
+    def set_colors(self, rgb):
+        """the mesh's vertex colours from a host array (n_vertices, 3) uint8 (prv_mesh_set_colors); refreshes self.colors"""
+        rgb = np.ascontiguousarray(np.asarray(rgb, np.uint8).reshape(-1, 3))
+        self._chk(self.ctx.lib.prv_mesh_set_colors(self.handle, _ptr(rgb) if len(rgb) else None, len(rgb)))
+        self.colors = rgb.copy()
 
     def save(self, path, scale=0.33, offset=(0.5, 0.5, 0.5)):
         """.ply / .obj in the dataset frame: (cycle(e) - offset) / scale (prv_mesh_save)"""

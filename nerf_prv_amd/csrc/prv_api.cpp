@@ -2250,4 +2250,5 @@ int prv_debug_field(prv_ctx* c, int slot, const float* pos, const float* dir, in
 #include "prv_geom_api.inc"
 #include "prv_select_api.inc"
 #include "prv_raster_api.inc"
+#include "prv_raster_color_api.inc"
 #include "prv_coverage_api.inc"

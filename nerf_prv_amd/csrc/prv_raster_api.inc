@@ -6,10 +6,10 @@ namespace {
 constexpr uint64_t kMeshFromArraysMost = 1ull << 31;
 
 // the views of a call in batches that fit the coverage stage's z-buffer budget (PRV_COVERAGE_ZBUF_BYTES: tests)
-int zbuf_views_per_batch(int n_views, size_t npix) {
+int zbuf_views_per_batch(int n_views, size_t npix, size_t key_bytes = 4) {
   size_t budget = kCoverageZBufBudget;
   if (const char* e = getenv("PRV_COVERAGE_ZBUF_BYTES")) budget = (size_t)strtoull(e, nullptr, 10);
-  return (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)n_views, (size_t)kCoverageMaxBatch), budget / (npix * 4)));
+  return (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)n_views, (size_t)kCoverageMaxBatch), budget / (npix * key_bytes)));
 }
 
 int raster_refuse_lenses(prv_ctx* c, const std::vector<CamDev>& cams) {
@@ -46,10 +46,12 @@ int raster_begin(prv_ctx* c, RasterWork& w, const prv_mesh* m, int views_per_bat
   return PRV_OK;
 }
 
-// zbuf = the depth buffers of the nb views of cams_dev: cleared, then every triangle of the mesh, chunk by chunk
-int raster_fill(prv_ctx* c, RasterWork& w, const prv_mesh* m, const CamDev* cams_dev, int nb, int W, int H, uint32_t* zbuf) {
+// zbuf = the depth buffers (Key = uint32_t) or the visibility buffers (Key = unsigned long long) of the nb views of cams_dev:
+// cleared to all ones, then every triangle of the mesh, chunk by chunk
+template <typename Key>
+int raster_fill(prv_ctx* c, RasterWork& w, const prv_mesh* m, const CamDev* cams_dev, int nb, int W, int H, Key* zbuf) {
   const size_t npix = (size_t)W * (size_t)H;
-  HIPCHK(c, hipMemsetAsync(zbuf, 0xff, (size_t)nb * npix * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(zbuf, 0xff, (size_t)nb * npix * sizeof(Key), c->stream));
   if (m->nt == 0) return PRV_OK;
   const int vsub = (int)std::min<size_t>((size_t)nb, w.capacity); // a capacity below the batch: fewer views per launch
   for (int v0 = 0; v0 < nb; v0 += vsub) {

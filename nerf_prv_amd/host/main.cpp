@@ -30,6 +30,7 @@ extern "C" {
 #include "fit_curve.hpp"
 #include "geometry_eval.hpp"
 #include "extras/pcd_io.hpp" // mode 3 only: the coloured cloud the splat rasteriser turns into rgbaClip images (not exported)
+#include "extras/ply_io.hpp" // mode 3 with `gt_surface: mesh`: the vertex-coloured mesh prv_mesh_render turns into them (not exported)
 #include "png_io.hpp"
 #include "engine.hpp" // PlannerEngine, EngineConfig and, through it, the handles of prv_handles.hpp
 
@@ -445,9 +446,18 @@ int instant_ngp_curves(prv_ctx* ctx, const std::string& cfg, const std::string& 
 // 17/16 (:827-833), bring it to the object size (the reference draws a random size in [0.075, 0.115] m and keeps it
 // in <gt_path>/size.txt, :851-867; here: that file if it exists, else `object_size`), place the N views, write
 // <gt_path>/<N>.json and the <N>/rgbaClip_<i>.png images (PCL screenshot + convertToAlpha + flip = prv_splat_points).
+// `gt_surface: mesh` (default `points`): the object is the vertex-coloured mesh <model_path>/<name>.ply instead (the layout
+// prv_mesh_write_file writes); its vertices are centred and scaled as the cloud's points are, and the images are
+// prv_mesh_render's -- a surface without holes and without a point size.  A bad key or file is refused before anything is written.
 int get_coverage_from_cloud(prv_ctx* ctx, const std::string& cfg, const std::string& name) {
   FileStorage fs;
   fs.open(cfg);
+  const std::string surface = fs.has("gt_surface") ? fs.str("gt_surface") : "points";
+  if (surface != "points" && surface != "mesh") {
+    std::cerr << "gt_surface must be points or mesh, got \"" << surface << "\": nothing was written" << std::endl;
+    return -73;
+  }
+  const bool mesh = surface == "mesh";
   auto sd = std::make_shared<Share_Data>(cfg, name, -1, -1, 0);
   if (!sd->ok) {
     std::cerr << sd->error << std::endl;
@@ -455,11 +465,21 @@ int get_coverage_from_cloud(prv_ctx* ctx, const std::string& cfg, const std::str
   }
   std::vector<float> xyz;
   std::vector<uint8_t> rgb;
-  const std::string cloud = sd->model_path + name + ".pcd";
-  const int prc = pcd_read(cloud, xyz, rgb);
-  if (prc != 0) {
-    std::cerr << "cannot read " << cloud << " (" << prc << ")" << std::endl;
-    return -70;
+  std::vector<uint32_t> tri; // (gt_surface: mesh)
+  if (mesh) {
+    std::string why = ply_read(sd->model_path + name + ".ply", xyz, rgb, tri);
+    if (why.empty() && xyz.empty()) why = sd->model_path + name + ".ply: a mesh without vertices";
+    if (!why.empty()) {
+      std::cerr << "gt_surface: mesh: " << why << ": nothing was written" << std::endl;
+      return -74;
+    }
+  } else {
+    const std::string cloud = sd->model_path + name + ".pcd";
+    const int prc = pcd_read(cloud, xyz, rgb);
+    if (prc != 0) {
+      std::cerr << "cannot read " << cloud << " (" << prc << ")" << std::endl;
+      return -70;
+    }
   }
   const size_t n = xyz.size() / 3;
   double c[3] = {0, 0, 0};
@@ -512,23 +532,32 @@ int get_coverage_from_cloud(prv_ctx* ctx, const std::string& cfg, const std::str
   const int point_size = fs.has("points_size_cloud") ? (int)fs.num("points_size_cloud") : 5; // yaml:18
   DeviceArray<float> xyz_dev;
   DeviceArray<uint8_t> rgb_dev, img_dev;
-  int rc = xyz_dev.alloc(ctx, xyz.size() * 4);
-  if (rc == PRV_OK) rc = rgb_dev.alloc(ctx, rgb.size());
-  if (rc == PRV_OK) rc = img_dev.alloc(ctx, (size_t)w * h * 4);
-  if (rc == PRV_OK) rc = prv_memcpy_h2d(ctx, xyz_dev.get(), xyz.data(), xyz.size() * 4);
-  if (rc == PRV_OK) rc = prv_memcpy_h2d(ctx, rgb_dev.get(), rgb.data(), rgb.size());
+  MeshPtr surface_mesh;
   const Vec3 oc = labeler.view_space->object_center_world;
   const double scale = 0.5 / labeler.view_space->predicted_size; // the json's (main.cpp:1599-1602)
   const double offset[3] = {0.5 + oc.z, 0.5 + oc.x, 0.5 + oc.y};
+  int rc = img_dev.alloc(ctx, (size_t)w * h * 4);
+  if (mesh) { // the vertices go where prv_splat_points puts the cloud's points (geometry_eval.hpp)
+    geometry_to_engine(xyz, scale, offset);
+    if (rc == PRV_OK) rc = prv_mesh_from_arrays(ctx, xyz.data(), n, tri.data(), tri.size() / 3, out_arg(surface_mesh));
+    if (rc == PRV_OK) rc = prv_mesh_set_colors(surface_mesh.get(), rgb.data(), n);
+  } else {
+    if (rc == PRV_OK) rc = xyz_dev.alloc(ctx, xyz.size() * 4);
+    if (rc == PRV_OK) rc = rgb_dev.alloc(ctx, rgb.size());
+    if (rc == PRV_OK) rc = prv_memcpy_h2d(ctx, xyz_dev.get(), xyz.data(), xyz.size() * 4);
+    if (rc == PRV_OK) rc = prv_memcpy_h2d(ctx, rgb_dev.get(), rgb.data(), rgb.size());
+  }
   sd->access_directory(sd->gt_path + "/" + N);
   std::vector<uint8_t> px((size_t)w * h * 4);
   for (int i = 0; rc == PRV_OK && i < count; i++) {
-    rc = prv_splat_points(ctx, xyz_dev.get(), rgb_dev.get(), n, scale, offset, ds.get(), &i, 1, w, h, point_size, 1, img_dev.get());
+    rc = mesh ? prv_mesh_render(ctx, surface_mesh.get(), ds.get(), &i, 1, w, h, 1, img_dev.get(), nullptr, nullptr)
+              : prv_splat_points(ctx, xyz_dev.get(), rgb_dev.get(), n, scale, offset, ds.get(), &i, 1, w, h, point_size, 1, img_dev.get());
     if (rc == PRV_OK) rc = prv_memcpy_d2h(ctx, px.data(), img_dev.get(), px.size());
     if (rc == PRV_OK && png_write_rgba8(sd->gt_path + "/" + N + "/rgbaClip_" + std::to_string(i) + ".png", w, h, px.data()) != 0) rc = PRV_E_IO;
   }
   if (rc != PRV_OK) std::cerr << "prv: " << prv_last_error(ctx) << std::endl;
-  std::cout << "object " << name << ": " << n << " points, size " << size << " m, " << count << " views" << std::endl;
+  std::cout << "object " << name << ": " << n << (mesh ? " vertices, " + std::to_string(tri.size() / 3) + " triangles" : std::string(" points")) << ", size " << size
+            << " m, " << count << " views" << std::endl;
   return rc;
 }
 

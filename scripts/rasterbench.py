@@ -3,8 +3,11 @@ scripts/coveragebench.py's two sizes (540 views of 80 x 45, 144 views of 800 x 8
 model's res-256 mesh, that mesh as the occluder), the share of (view, triangle) pairs the large path took, a sweep of
 PRV_RASTER_SMALL_PIXELS on both, and prv_mesh_depth of one 12-triangle box at 144 x 800 x 800 (the large path alone).  Host clock
 around calls that end in a device synchronise (every entry point here synchronises).
+--color: prv_mesh_render (64-bit keys, then the shading pass) beside prv_mesh_depth on the same two sizes and nothing else; the
+mesh then carries the field's colours.
 
     python scripts/rasterbench.py [--reps 5] [--log2n 20] [--sweep 1,4,16,64,256,1024] [--json out.json]
+    python scripts/rasterbench.py --color --reps 3
 """
 import argparse
 import json
@@ -21,6 +24,7 @@ ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--log2n", type=int, default=20)
 ap.add_argument("--sweep", default="1,4,16,64,256,1024")
 ap.add_argument("--json", default="")
+ap.add_argument("--color", action="store_true")
 args = ap.parse_args()
 
 import torch
@@ -65,8 +69,8 @@ def cameras(k):
 
 ctx.synthetic_model(0, api.field_desc(**api.FIELD_256), 0x5EED0001)
 thr = float(np.median(ctx.density_grid(0, 64).cpu().numpy()))
-mesh = ctx.marching_cubes(0, 256, threshold=thr, colors=False)
-pts = mesh.sample(n, 1)
+mesh = ctx.marching_cubes(0, 256, threshold=thr, colors=args.color)
+pts = None if args.color else mesh.sample(n, 1)
 lo, hi = np.array([0.2, 0.2, 0.2]), np.array([0.8, 0.8, 0.8])
 bv = np.array([[(hi if (k >> a) & 1 else lo)[a] for a in range(3)] for k in range(8)], np.float32)
 quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
@@ -76,6 +80,17 @@ for n_views, (w, h) in ((540, (80, 45)), (144, (800, 800))):
     cs = cameras(n_views)
     row = dict(case=f"{n_views}x{w}x{h}", n=n, triangles=int(mesh.counts()[1]))
     os.environ.pop("PRV_RASTER_SMALL_PIXELS", None)
+    if args.color:
+        row["mesh_depth_ms"] = timed(lambda: ctx.mesh_depth(mesh, cs, None, w, h))
+        row["mesh_render_ms"] = timed(lambda: ctx.mesh_render(mesh, cs, None, w, h))
+        row["mesh_render_planes_ms"] = timed(lambda: ctx.mesh_render(mesh, cs, None, w, h, want_depth=True, want_triangles=True))
+        stats = ctx.raster_stats()
+        row["pairs"], row["large_pairs"] = stats["pairs"], stats["large"]
+        row["render_over_depth"] = row["mesh_render_ms"]["median"] / row["mesh_depth_ms"]["median"]
+        cs.close()
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        continue
     row["points_create_ms"] = timed(lambda: ctx.coverage(pts, cs, None, w, h, point_size=1))
     row["mesh_create_ms"] = timed(lambda: ctx.coverage(pts, cs, None, w, h, occluder=mesh))
     stats = ctx.raster_stats()
