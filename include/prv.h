@@ -940,6 +940,17 @@ typedef struct prv_model_layout {
   int32_t n_dense_levels;         /* leading physically dense levels */
 } prv_model_layout;
 int prv_debug_model_layout(prv_ctx* ctx, int model_slot, prv_model_layout* out);
+/* Dense replicas of a loaded field's leading hashed levels (a buffer beside the physical table, built when the model is
+ * installed): how many levels the model holds them for -- which is the render_queue64 replica variant
+ * prv_render launches for it under PRV_STEP_FIXED_S (under PRV_STEP_NGP the launch reads at most two of them); 0: none, the
+ * plain instance -- and the bytes of that buffer.  Only F = 4 fields that run the
+ * <4, 5> instance get any; PRV_REPLICA_LEVELS (0..3) caps the count, PRV_REPLICA_MB sets the byte budget, both read when a
+ * model is installed.  prv_model_layout does not change with them. */
+int prv_debug_replica_layout(prv_ctx* ctx, int model_slot, int32_t* n_levels, uint64_t* bytes);
+/* The layout arithmetic of one replica, no context needed: a level of `res` vertices per axis with entries of n_features halfs
+ * -> entries per row (= rows per plane: res + 1 rounded up to 8), the z stride in bytes (must stay below 2^24) and the bytes
+ * of the replica (res + 1 planes, rounded up to 4 KiB; 0: such a level is not replicated). */
+int prv_debug_replica_level(uint32_t res, uint32_t n_features, uint32_t* row_entries, uint64_t* z_stride_bytes, uint64_t* bytes);
 /* Shader clock the render launches actually ran at (roofline accounting: the VALU issue peak is per clock and the
  * clock under this load is well below the 2.4 GHz maximum).  One wave of every render_queue launch stamps the shader
  * cycle counter and the constant-rate reference counter at its start and end; this returns the two sums since the

@@ -251,6 +251,8 @@ SIGNATURES = {
     "prv_model_exchange": (_i, [_vp, _vp, _i, C.POINTER(FieldDesc)]),
     "prv_model_exchange_slots": (_i, [_vp, _vp, _i, _P(_i), _P(_i), C.POINTER(FieldDesc)]),
     "prv_debug_model_layout": (_i, [_vp, _i, C.POINTER(ModelLayout)]),
+    "prv_debug_replica_layout": (_i, [_vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
+    "prv_debug_replica_level": (_i, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "prv_debug_render_clock": (_i, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "prv_debug_raygen": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "prv_debug_mesh_stages": (_i, [_vp, _P(C.c_float)]),

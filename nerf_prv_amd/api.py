@@ -33,6 +33,24 @@ FIELD_HBM = dict(n_levels=16, n_features=2, log2_hashmap=24, base_res=16, finest
                  density_bias=3.0, table_amp=4.0)
 
 
+def replica_level(res, n_features=4):
+    """(entries per row, z stride in bytes, bytes) of the dense replica of a hashed level of `res` vertices per axis
+    (prv_debug_replica_level; needs no GPU)"""
+    row, mz, b = C.c_uint32(), C.c_uint64(), C.c_uint64()
+    if L.load().prv_debug_replica_level(int(res), int(n_features), C.byref(row), C.byref(mz), C.byref(b)) != 0:
+        raise PrvError(L.PRV_E_INVALID, "prv_debug_replica_level failed")
+    return row.value, mz.value, b.value
+
+
+def replica_layout(ctx, model_slot):
+    """(levels, bytes) of the dense replicas the field in a slot of Context `ctx` holds of its leading hashed levels: the replica
+    variant its render launches, 0 = the plain instance (prv_debug_replica_layout; the tests' hook, like Context.model_layout,
+    whose answer does not change with replicas)"""
+    n, b = C.c_int32(), C.c_uint64()
+    ctx._chk(ctx.lib.prv_debug_replica_layout(ctx.handle, int(model_slot), C.byref(n), C.byref(b)))
+    return n.value, b.value
+
+
 class RenderMode(enum.IntEnum):
     """testbed.render_mode (run.py:287: `testbed.render_mode = ngp.Depth` for --screenshot_depth)"""
 

@@ -51,6 +51,11 @@ struct Model {
   uint64_t phys_bytes = 0; // the kernel layout of THIS field (phys may be a larger allocation left by an earlier one)
   float occ_lo[3] = {0, 0, 0}, occ_hi[3] = {1, 1, 1};
   Buffer table, phys, occ, occ_coarse, frags, frags64, mlp; // table/mlp = canonical (ABI) copies kept for export; phys = kernel layout
+  // dense replicas of the leading hashed levels, for the render launch and the field hook (build_replicas); a buffer of their
+  // own: phys, phys_bytes and dev describe the field as they did without
+  Buffer repl;
+  ReplicaDev rdev{};
+  uint64_t repl_bytes = 0;
 };
 
 } // namespace
@@ -229,6 +234,50 @@ float rng_sym(uint64_t seed, uint64_t stream, uint64_t i, float amp) {
 }
 const float kSynthSpheres[4][4] = {
     {0.50f, 0.50f, 0.50f, 0.35f}, {0.80f, 0.50f, 0.62f, 0.13f}, {0.36f, 0.80f, 0.45f, 0.11f}, {0.40f, 0.24f, 0.78f, 0.10f}};
+
+// Dense replicas of the leading hashed levels of a model whose render runs the <4, 5> instance (prv_device.hpp: ReplicaDev): the
+// hash is there to save memory while TRAINING; an installed model's table is constant until the next install, so the hash is
+// undone here, once, and the render's gather of those levels is the dense one.  As many levels, from the coarsest, as fit the
+// budget -- PRV_REPLICA_MB, default kReplicaBudgetDefault -- and at most PRV_REPLICA_LEVELS (0..3; 0: none), both read here
+// like PRV_NO_PAIR.  Every other field (F = 2, the generic instances, wide offsets, levels finer than their table: whatever
+// render_instance_dense_levels does not answer 5 for) gets none and gives the buffer back.  Called at the end of every
+// install, a trainer's publish included (republish_model), once m.dev and the physical table are complete.
+constexpr uint64_t kReplicaBudgetDefault = (uint64_t)256 << 20; // api.FIELD_256: 13.5 + 43.1 + 143.3 MB for its three hashed levels
+
+int build_replicas(prv_ctx* c, Model& m) {
+  const FieldDev& f = m.dev;
+  m.rdev = ReplicaDev{};
+  m.repl_bytes = 0;
+  int cap = kMaxReplicas;
+  uint64_t budget = kReplicaBudgetDefault;
+  if (const char* e = getenv("PRV_REPLICA_LEVELS")) cap = std::max(0, std::min(kMaxReplicas, atoi(e)));
+  if (const char* e = getenv("PRV_REPLICA_MB")) budget = (uint64_t)std::max(0ll, std::min(strtoll(e, nullptr, 10), 1ll << 20)) << 20;
+  int n = 0;
+  uint64_t total = 0;
+  uint32_t pack[kMaxReplicas] = {0, 0, 0};
+  if (f.n_features == 4 && render_instance_dense_levels(f) == 5) {
+    for (int l = f.n_dense_levels; l < f.n_levels && n < cap; l++, n++) {
+      const uint32_t res = f.levels[l].res_m1 + 1u;
+      const ReplicaLevelLayout lay = replica_level_layout(res, 8u);
+      if (res > 1024u || lay.bytes == 0 || total + lay.bytes > budget || total + lay.bytes >= (1ull << 32)) break;
+      pack[n] = (uint32_t)total | (lay.row / 8u); // total is a multiple of 4 KiB, row / 8 < 4096
+      total += lay.bytes;
+    }
+  }
+  if (n == 0) {
+    m.repl.reset(); // (the stream is idle: install_model has just waited for it)
+    return PRV_OK;
+  }
+  int rc;
+  if ((rc = ensure(c, m.repl, total)) != PRV_OK) return rc;
+  m.rdev.table = (const uint16_t*)m.repl.p;
+  m.rdev.n_levels = n;
+  memcpy(m.rdev.pack, pack, sizeof(pack));
+  m.repl_bytes = total;
+  for (int k = 0; k < n; k++) HIPCHK(c, launch_fill_replica(f, m.rdev, k, c->stream)); // (padding rows and columns are never read)
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return PRV_OK;
+}
 
 int install_model(prv_ctx* c, int slot, const prv_field_desc& d, const uint16_t* mlp, const uint32_t* occ_host,
                   const uint16_t* table_host /* may be null: table already on device */) {
@@ -429,6 +478,7 @@ int install_model(prv_ctx* c, int slot, const prv_field_desc& d, const uint16_t*
       L.pack = (L.off_b & ~31u) | (sx[l] & 31u);
     }
   }
+  if ((rc = build_replicas(c, m)) != PRV_OK) return rc;
   m.loaded = true;
   m.dirty = false;
   return PRV_OK;
@@ -938,7 +988,7 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
       pp.bin_mul = (uint32_t)(n_bins * 65536u / (size_t)(ngp ? kNgpMaxSteps : o->samples_per_ray));
     }
     if ((rc = timed(c, c->ev_render, [&] {
-           HIPCHK(c, n_planes ? launch_render_planes(pp, t.mode, n_blocks, c->stream) : launch_render(pp.r, n_blocks, c->stream));
+           HIPCHK(c, n_planes ? launch_render_planes(pp, t.mode, n_blocks, c->stream) : launch_render(pp.r, m.rdev, n_blocks, c->stream));
            return PRV_OK;
          })) != PRV_OK)
       return rc;
@@ -1053,7 +1103,7 @@ int render_ensemble_ngp(prv_ctx* c, const int* slots, int E, const prv_camset* c
     const int n_blocks = render_blocks(c, m, npix);
     uint32_t* q_head = (uint32_t*)((char*)c->counters_multi.p + (size_t)e * kStatOffset);
     const RenderParams rp = render_params(c, m, o, L, mp.seg_cap, mp.mem[e], q_head, stat, kRenderColour);
-    if ((rc = timed(c, c->ev_render, [&] { HIPCHK(c, launch_render(rp, n_blocks, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
+    if ((rc = timed(c, c->ev_render, [&] { HIPCHK(c, launch_render(rp, m.rdev, n_blocks, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
     if (spp > 1)
       HIPCHK(c, launch_spp_reduce((const float*)mp.mem[e].out_f32, (size_t)n_views * npix, spp, o->background, scratch_f32, (uint32_t*)out_u8[e], c->stream));
   }
@@ -2188,6 +2238,26 @@ int prv_debug_model_layout(prv_ctx* c, int slot, prv_model_layout* out) try {
   return PRV_OK;
 } catch (...) { return caught(c); }
 
+int prv_debug_replica_layout(prv_ctx* c, int slot, int32_t* n_levels, uint64_t* bytes) try {
+  if (!c) return PRV_E_INVALID;
+  int rc = check_model(c, slot);
+  if (rc != PRV_OK) return rc;
+  if (!n_levels || !bytes) return fail(c, PRV_E_INVALID, "out is NULL");
+  const Model& m = c->models[slot];
+  *n_levels = replica_instance_levels(m.dev, m.rdev);
+  *bytes = m.repl_bytes;
+  return PRV_OK;
+} catch (...) { return caught(c); }
+
+int prv_debug_replica_level(uint32_t res, uint32_t n_features, uint32_t* row_entries, uint64_t* z_stride_bytes, uint64_t* bytes) {
+  if (!row_entries || !z_stride_bytes || !bytes || res < 1 || res > 4096 || (n_features != 2 && n_features != 4)) return PRV_E_INVALID;
+  const ReplicaLevelLayout lay = replica_level_layout(res, n_features * 2u);
+  *row_entries = lay.row;
+  *z_stride_bytes = (uint64_t)lay.row * lay.row * n_features * 2u;
+  *bytes = lay.bytes;
+  return PRV_OK;
+}
+
 int prv_debug_raygen(prv_ctx* c, const prv_camset* cs, int view, int W, int H, int spp_k, float* o, float* d, float* t) try {
   if (!c) return PRV_E_INVALID;
   if (!cs || view < 0 || view >= (int)cs->cams.size() || W < 1 || H < 1 || !o || !d || !t)
@@ -2221,7 +2291,7 @@ static int debug_field_common(prv_ctx* c, int slot, const float* pos, const floa
     return rc;
   HIPCHK(c, hipMemcpyAsync(c->dbg[0].p, pos, N * 12, hipMemcpyHostToDevice, c->stream));
   if (dir) HIPCHK(c, hipMemcpyAsync(c->dbg[1].p, dir, N * 12, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, launch_debug_field(c->models[slot].dev, (const float*)c->dbg[0].p, dir ? (const float*)c->dbg[1].p : nullptr,
+  HIPCHK(c, launch_debug_field(c->models[slot].dev, c->models[slot].rdev, (const float*)c->dbg[0].p, dir ? (const float*)c->dbg[1].p : nullptr,
                                n, (uint16_t*)c->dbg[3].p, (float*)c->dbg[4].p, (int32_t*)c->dbg[5].p, c->stream));
   if (feat) HIPCHK(c, hipMemcpyAsync(feat, c->dbg[3].p, N * 64, hipMemcpyDeviceToHost, c->stream));
   if (out36) HIPCHK(c, hipMemcpyAsync(out36, c->dbg[4].p, N * 144, hipMemcpyDeviceToHost, c->stream));

@@ -70,6 +70,21 @@ struct FieldDev {
   float occ_lo[3], occ_hi[3]; // bounding box of the occupied cells, grown by one cell (march pass clips to it)
 };
 
+// Dense REPLICAS of the leading hashed levels of a field that runs the <4, 5> render instance (built where the model is
+// installed, prv_api.cpp: build_replicas; a buffer of their own beside the physical table).  A model that is rendered has a
+// constant table, so the hash can be undone once: replica[x, y, z] = the entry the hashed gather fetches for vertex
+// (min(x, res-1), min(y, res-1), min(z, res-1)), x, y, z in [0, res] -- the dense levels' duplicated border.  The level then
+// goes through the dense gather (4 paired loads, no clamps, no hash) and yields the same entries: features are bit-identical.
+// Strides are tight, not powers of two: a row of res + 1 entries rounded up to 8 entries (one 64-byte line at F = 4), as
+// many rows per plane, res + 1 planes; level offsets are multiples of 4 KiB, so one word holds a level:
+//   pack = off_b | row entries / 8        y stride = row entries * ebytes, z stride = y stride * row entries  (< 2^24)
+constexpr int kMaxReplicas = 3;
+struct ReplicaDev {
+  const uint16_t* table;       // the replica buffer (null: the model has none)
+  uint32_t pack[kMaxReplicas]; // replica k = level n_dense_levels + k
+  int n_levels;                // how many of the field's hashed levels are replicated, from the coarsest
+};
+
 struct CamDev {  // engine-frame camera
   float c2w[12]; // row-major 3x4
   float fx, fy, cx, cy;
@@ -351,7 +366,7 @@ struct HashConsts { // the field's shared hash constants, wave-uniform (FieldDev
   uint32_t my_b, mz_b, m_b;
   uint32_t wide; // FieldDev::wide_offsets (the generic gather's 32-bit multiplies)
 };
-enum { kLevelDense = 0, kLevelHashedShared = 1, kLevelGeneric = 2 };
+enum { kLevelDense = 0, kLevelHashedShared = 1, kLevelGeneric = 2, kLevelReplica = 3 };
 
 // The last cell a LANE gathered on one hashed level and its eight corner entries.  Under the engine's stepping rule
 // (dt = sqrt(3)/1024 = 0.43 of the finest cell of a 256^3 field) a ray's consecutive samples stay in the cell about
@@ -385,12 +400,14 @@ __device__ __forceinline__ void encode_level2(const uint16_t* __restrict__ table
   // out of the loop into registers the kernel does not have (it was spilling 40..117 SGPRs, one v_readlane per use).
   uint32_t pk = L.pack;
   if (KIND != kLevelGeneric) asm volatile("" : "+s"(pk));
-  if (DENSE) {
+  if (DENSE || KIND == kLevelReplica) {
     // the level constants are wave-uniform here (scalar registers): the level offset and the +y neighbour go into two
     // SCALAR base pointers (SALU adds), so the four paired loads need one vector add between them -- (b, base),
     // (b, base + my), (b + mz, base), (b + mz, base + my)
-    const uint32_t sxl = pk & 31u, off = pk & ~31u;
-    const uint32_t my = (uint32_t)(F * 2) << sxl, mz = (uint32_t)(F * 2) << (2u * sxl);
+    // (a replica -- `table` is the replica buffer, pk its ReplicaDev::pack word -- differs in its strides alone)
+    const uint32_t sxl = pk & 31u, row8 = pk & 4095u, off = pk & (DENSE ? ~31u : ~4095u);
+    const uint32_t my = DENSE ? (uint32_t)(F * 2) << sxl : row8 * (uint32_t)(F * 16);
+    const uint32_t mz = DENSE ? (uint32_t)(F * 2) << (2u * sxl) : my * (row8 << 3);
     const char* base0 = reinterpret_cast<const char*>(table) + off;
     const char* base1 = base0 + my;
     const uint32_t b = (c0[0] << ESH) + __umul24(c0[1], my) + __umul24(c0[2], mz);
@@ -575,23 +592,40 @@ __device__ __forceinline__ void encode_all_levels_cached(const uint16_t* __restr
 
 // NDENSE > 0: the field has EXACTLY NDENSE leading dense levels and its hashed levels share their constants
 // (FieldDev::hash_shared; the host picks the instance).  NDENSE = 0: every level through the generic path.
-template <int F, int NDENSE, int... J>
+// NREPL > 0: the hashed levels NDENSE .. NDENSE + NREPL - 1 are read from their dense replicas (R; the host picks the instance
+// by what the model holds), the rest through the shared hash as before.  NREPL = all of them: no hash code, no clamps.
+template <int F, int NDENSE, int NREPL, int J>
+__device__ __forceinline__ void encode_level_at(const uint16_t* __restrict__ table, const LevelDev* __restrict__ lv, const HashConsts& H,
+                                                const ReplicaDev* __restrict__ R, float px, float py, float pz, half2v* out) {
+  if constexpr (J >= NDENSE && J < NDENSE + NREPL) {
+    LevelDev L = {};
+    L.scale = lv[J].scale;
+    L.pack = R->pack[J - NDENSE];
+    encode_level2<F, kLevelReplica>(R->table, L, H, px, py, pz, out + J * (F / 2));
+  } else {
+    encode_level2<F, (J < NDENSE ? kLevelDense : NDENSE > 0 ? kLevelHashedShared : kLevelGeneric)>(table, lv[J], H, px, py, pz, out + J * (F / 2));
+  }
+}
+template <int F, int NDENSE, int NREPL, int... J>
 __device__ __forceinline__ void encode_all_levels(const uint16_t* __restrict__ table, const LevelDev* __restrict__ lv, const HashConsts& H,
-                                                  float px, float py, float pz, half2v* out, std::integer_sequence<int, J...>) {
-  (encode_level2<F, (J < NDENSE ? kLevelDense : NDENSE > 0 ? kLevelHashedShared : kLevelGeneric)>(table, lv[J], H, px, py, pz, out + J * (F / 2)), ...);
+                                                  const ReplicaDev* __restrict__ R, float px, float py, float pz, half2v* out,
+                                                  std::integer_sequence<int, J...>) {
+  (encode_level_at<F, NDENSE, NREPL, J>(table, lv, H, R, px, py, pz, out), ...);
 }
 
 // all 32 features of one sample in canonical order (feature F*l + f), as four half8 = the k rows [8s, 8s+8) of the first
 // layer; render_queue64 turns them into MFMA B fragments with v_permlane32_swap
-template <int F, int NDENSE, bool CACHE = false>
+template <int F, int NDENSE, bool CACHE = false, int NREPL = 0>
 __device__ __forceinline__ void encode_sample(const uint16_t* __restrict__ table, const LevelDev* __restrict__ lv, const HashConsts& H,
-                                              float px, float py, float pz, half8 f[4], CornerCache<F>* cc = nullptr) {
+                                              float px, float py, float pz, half8 f[4], CornerCache<F>* cc = nullptr,
+                                              const ReplicaDev* __restrict__ R = nullptr) {
+  static_assert(NREPL == 0 || (!CACHE && NDENSE > 0 && NDENSE + NREPL <= 32 / F && NREPL <= kMaxReplicas), "replicas: plain instances with dense levels only");
   px = clamp01(px);
   py = clamp01(py);
   pz = clamp01(pz);
   half2v out[16];
   if constexpr (CACHE && NDENSE > 0) encode_all_levels_cached<F, NDENSE>(table, lv, H, px, py, pz, out, cc, std::make_integer_sequence<int, 32 / F>{});
-  else encode_all_levels<F, NDENSE>(table, lv, H, px, py, pz, out, std::make_integer_sequence<int, 32 / F>{});
+  else encode_all_levels<F, NDENSE, NREPL>(table, lv, H, R, px, py, pz, out, std::make_integer_sequence<int, 32 / F>{});
 #pragma unroll
   for (int s = 0; s < 4; s++)
 #pragma unroll

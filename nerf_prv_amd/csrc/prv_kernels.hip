@@ -750,8 +750,9 @@ __device__ __forceinline__ float entropy_add(float p, float H) { return p >= 1.1
 // when the bin changes the sum goes to X->out_bins[bin * X->plane_stride + pix] with one store and restarts at 0, the open bin is
 // flushed at ray end beside 1 - T to X->out_alpha[pix] (the entropy mode's bits).  A bin address is written at most once per
 // ray, by whichever lane holds the ray then: no atomics, nothing read back.  The sum lives in the entropy mode's H.
-template <int F, int NDENSE, bool NGP, bool CACHE, int MODE>
-__device__ __forceinline__ void render_queue64_body(RenderParams P, const RenderPlanesParams* X) {
+// NREPL > 0 (render_queue64_replica_kernel): the first NREPL hashed levels are gathered from their dense replicas (R; prv_device.hpp: ReplicaDev)
+template <int F, int NDENSE, bool NGP, bool CACHE, int MODE, int NREPL = 0>
+__device__ __forceinline__ void render_queue64_body(RenderParams P, const RenderPlanesParams* X, const ReplicaDev* R = nullptr) {
   using M = RenderMode<MODE>; // what the mode sums and which words move with a ray (prv_kernels.hpp)
   constexpr int kDWord = M::kDWord, kMoveWords = M::kMoveWords, kFrags = M::kFrags;
   __shared__ half8 wl[kFrags * 64];
@@ -1078,7 +1079,7 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
       const float t = fmaf((float)i + 0.5f, dt, t0);
       if constexpr (M::DSTATE) ts = t;
       if constexpr (M::TERM) sbin = min((i * X->bin_mul) >> 16, X->n_bins - 1u); // (the min changes no bin of a ray within n_max steps: it keeps any other inside the planes)
-      encode_sample<F, NDENSE, CACHE>(P.field.table, lvl, hc, fmaf(t, d[0], o[0]), fmaf(t, d[1], o[1]), fmaf(t, d[2], o[2]), f, cc);
+      encode_sample<F, NDENSE, CACHE, NREPL>(P.field.table, lvl, hc, fmaf(t, d[0], o[0]), fmaf(t, d[1], o[1]), fmaf(t, d[2], o[2]), f, cc, R);
     }
     // f[2s] | f[2s+1] = k rows [16s, 16s+8) | [16s+8, 16s+16) of the lane's own sample -> B operands of the two groups
     swap_halves(f[0], f[1]); // f[0] = group A k-step 0, f[1] = group B k-step 0
@@ -1161,6 +1162,15 @@ __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(CACHE ? 2 : NDENSE == 0 ? 1 : 3)))
 void render_queue64_kernel(RenderParams P) {
   render_queue64_body<F, NDENSE, NGP, CACHE, kRenderColour>(P, nullptr);
+}
+
+// render_queue64_kernel<4, 5, NGP, false> for a model that holds dense replicas of its first NREPL hashed levels (prv_api.cpp:
+// build_replicas): those levels cost 4 address instructions and 4 paired loads each instead of 26 and 8.  Same pixels.
+template <bool NGP, int NREPL>
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(3)))
+void render_queue64_replica_kernel(RenderParams P, ReplicaDev R) {
+  render_queue64_body<4, 5, NGP, false, kRenderColour, NREPL>(P, nullptr, &R);
 }
 
 // prv_render_depth / prv_render_entropy / prv_render_footprint / prv_render_surface / prv_render_termination: the render that writes scalar planes (render_queue64_body,
@@ -1718,6 +1728,31 @@ __global__ __launch_bounds__(256) void repack_level_kernel(const uint16_t* __res
   }
 }
 
+// physical table -> the dense replica of one hashed level (prv_device.hpp: ReplicaDev).  One lane per replica vertex
+// (x, y, z) in [0, res]^3, the duplicated border included: it reads the entry of vertex (min(x, res-1), ..) where
+// encode_level2's kLevelHashedShared path reads it -- the level's base from its pack word, the byte offset from the field's
+// shared hash constants, term for term -- and stores it at the address the kLevelReplica path forms from the replica's word.
+template <int F>
+__global__ __launch_bounds__(256) void fill_replica_kernel(const uint16_t* __restrict__ phys, uint16_t* __restrict__ repl, uint32_t level_pack,
+                                                           HashConsts H, uint32_t replica_pack, uint32_t res) {
+  typedef typename EntryWord<F>::type word_t;
+  constexpr int ESH = F == 4 ? 3 : 2;
+  const uint32_t res_m1 = level_pack & 4095u, n1 = res + 1u;
+  const char* src = reinterpret_cast<const char*>(phys) + (level_pack & ~4095u);
+  const uint32_t row8 = replica_pack & 4095u;
+  const uint32_t my = row8 * (uint32_t)(F * 16), mz = my * (row8 << 3);
+  char* dst = reinterpret_cast<char*>(repl) + (replica_pack & ~4095u);
+  const uint32_t nv = n1 * n1 * n1; // res <= 1024 (host-checked)
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < nv; i += gridDim.x * 256) {
+    const uint32_t x = i % n1, y = (i / n1) % n1, z = i / (n1 * n1);
+    const uint32_t tx = min(x, res_m1) << ESH;
+    const uint32_t ty = __umul24(min(y, res_m1), H.my_b) & H.m_b;
+    const uint32_t tz = __umul24(min(z, res_m1), H.mz_b) & H.m_b;
+    const word_t v = *reinterpret_cast<const word_t*>(src + (tx ^ ty ^ tz));
+    *reinterpret_cast<word_t*>(dst + ((x << ESH) + __umul24(y, my) + __umul24(z, mz))) = v;
+  }
+}
+
 // ------------------------------------------------------------------ stage hooks (parity tests)
 
 __global__ __launch_bounds__(256) void debug_raygen_kernel(CamDev cam, int W, int H, int spp_k,
@@ -1740,11 +1775,11 @@ __global__ __launch_bounds__(256) void debug_raygen_kernel(CamDev cam, int W, in
 }
 
 // the same hook through the 64-slot kernel's machinery: one wave = 64 points, one lane = one point (encode_sample,
-// permlane swaps, mlp_forward2 on the frags64 set)
-template <int F, int NDENSE>
+// permlane swaps, mlp_forward2 on the frags64 set); NREPL > 0: through the model's replicas, as its render launch goes
+template <int F, int NDENSE, int NREPL = 0>
 __global__ __launch_bounds__(256) void debug_field64_kernel(FieldDev fd, const float* __restrict__ pos, const float* __restrict__ dir,
                                                             int n, uint16_t* __restrict__ feat, float* __restrict__ out36,
-                                                            int32_t* __restrict__ occ_out) {
+                                                            int32_t* __restrict__ occ_out, ReplicaDev R) {
   __shared__ half8 wl[kNumFrags * 64];
   const LevelDev* __restrict__ lvl = fd.levels; // wave-uniform kernel arguments, as in the render kernel
   for (int i = threadIdx.x; i < kNumFrags * 64; i += 256) wl[i] = fd.frags64[i];
@@ -1766,7 +1801,7 @@ __global__ __launch_bounds__(256) void debug_field64_kernel(FieldDev fd, const f
   dir_of(idxB, dB);
   half8 f[4];
   const HashConsts hc = {fd.hash_my_b, fd.hash_mz_b, fd.hash_m_b, (uint32_t)fd.wide_offsets};
-  encode_sample<F, NDENSE>(fd.table, lvl, hc, p[0], p[1], p[2], f);
+  encode_sample<F, NDENSE, false, NREPL>(fd.table, lvl, hc, p[0], p[1], p[2], f, nullptr, NREPL > 0 ? &R : nullptr);
   if (ok && feat) {
     typedef uint16_t ushort8 __attribute__((ext_vector_type(8)));
     uint16_t* dst = feat + (size_t)idx * 32;
@@ -1913,11 +1948,24 @@ hipError_t launch_march_multi(const MarchMultiParams& P, int n_views, int n_spp,
 }
 
 template <bool NGP>
-static void launch_render_mode(const RenderParams& P, int n_blocks, hipStream_t s) {
+static void launch_render_mode(const RenderParams& P, const ReplicaDev& R, int n_blocks, hipStream_t s) {
   // the caller asked for the per-lane corner cache (prv_api.cpp: render_policy says when).  Only <4, 5> has the instance
   // (the F = 2 fields have six hashed levels: their cache does not fit 256 registers -- 128 spilled -- so they run without)
   if (P.cell_cache && P.field.n_features == 4 && render_instance_dense_levels(P.field) == 5) {
     hipLaunchKernelGGL((render_queue64_kernel<4, 5, NGP, true>), dim3(n_blocks), dim3(256), 0, s, P);
+    return;
+  }
+  // the model holds dense replicas of its leading hashed levels (only a field that runs <4, 5> ever does): the instance without their hash
+  // (under the engine's rule at most kReplicaLevelsNgp of them, prv_kernels.hpp: <true, 3> lost to <true, 2> and is not compiled)
+  if (const int nr = NGP ? std::min(replica_instance_levels(P.field, R), kReplicaLevelsNgp) : replica_instance_levels(P.field, R)) {
+    if constexpr (!NGP) {
+      if (nr == 3) {
+        hipLaunchKernelGGL((render_queue64_replica_kernel<false, 3>), dim3(n_blocks), dim3(256), 0, s, P, R);
+        return;
+      }
+    }
+    if (nr >= 2) hipLaunchKernelGGL((render_queue64_replica_kernel<NGP, 2>), dim3(n_blocks), dim3(256), 0, s, P, R);
+    else hipLaunchKernelGGL((render_queue64_replica_kernel<NGP, 1>), dim3(n_blocks), dim3(256), 0, s, P, R);
     return;
   }
   with_field_instance(P.field, [&](auto f, auto nd) {
@@ -1925,9 +1973,9 @@ static void launch_render_mode(const RenderParams& P, int n_blocks, hipStream_t 
   });
 }
 
-hipError_t launch_render(const RenderParams& P, int n_blocks, hipStream_t s) {
-  if (P.step_mode == PRV_STEP_NGP) launch_render_mode<true>(P, n_blocks, s);
-  else launch_render_mode<false>(P, n_blocks, s);
+hipError_t launch_render(const RenderParams& P, const ReplicaDev& R, int n_blocks, hipStream_t s) {
+  if (P.step_mode == PRV_STEP_NGP) launch_render_mode<true>(P, R, n_blocks, s);
+  else launch_render_mode<false>(P, R, n_blocks, s);
   return hipGetLastError();
 }
 
@@ -2026,6 +2074,16 @@ hipError_t launch_synth_table(uint16_t* table, size_t n, uint64_t seed, float am
   return hipGetLastError();
 }
 
+hipError_t launch_fill_replica(const FieldDev& fd, const ReplicaDev& R, int k, hipStream_t s) {
+  const LevelDev& L = fd.levels[fd.n_dense_levels + k];
+  const uint32_t res = L.res_m1 + 1u, nv = (res + 1u) * (res + 1u) * (res + 1u);
+  if (fd.n_features != 4 || k < 0 || k >= R.n_levels || res > 1024u) return hipErrorInvalidValue;
+  const HashConsts hc = {fd.hash_my_b, fd.hash_mz_b, fd.hash_m_b, 0u};
+  hipLaunchKernelGGL(fill_replica_kernel<4>, dim3(std::min(8192u, (nv + 255u) / 256u)), dim3(256), 0, s, fd.table,
+                     const_cast<uint16_t*>(R.table), L.pack, hc, R.pack[k], res);
+  return hipGetLastError();
+}
+
 hipError_t launch_repack_level(const uint16_t* canon, uint16_t* phys, const RepackLevel& L, int F, hipStream_t s) {
   unsigned blocks = ((L.hashed ? L.n : L.res * L.res * L.res) + 255) / 256;
   if (blocks > 8192) blocks = 8192;
@@ -2044,11 +2102,17 @@ hipError_t launch_debug_raygen(const CamDev& cam, int W, int H, int spp_k, float
   return hipGetLastError();
 }
 
-hipError_t launch_debug_field(const FieldDev& fd, const float* pos, const float* dir, int n, uint16_t* feat,
+hipError_t launch_debug_field(const FieldDev& fd, const ReplicaDev& R, const float* pos, const float* dir, int n, uint16_t* feat,
                               float* out36, int32_t* occ, hipStream_t s) {
   const unsigned blocks64 = (unsigned)((n + 255) / 256);
+  if (const int nr = replica_instance_levels(fd, R)) {
+    if (nr == 3) hipLaunchKernelGGL((debug_field64_kernel<4, 5, 3>), dim3(blocks64), dim3(256), 0, s, fd, pos, dir, n, feat, out36, occ, R);
+    else if (nr == 2) hipLaunchKernelGGL((debug_field64_kernel<4, 5, 2>), dim3(blocks64), dim3(256), 0, s, fd, pos, dir, n, feat, out36, occ, R);
+    else hipLaunchKernelGGL((debug_field64_kernel<4, 5, 1>), dim3(blocks64), dim3(256), 0, s, fd, pos, dir, n, feat, out36, occ, R);
+    return hipGetLastError();
+  }
   with_field_instance(fd, [&](auto f, auto nd) {
-    hipLaunchKernelGGL((debug_field64_kernel<decltype(f)::value, decltype(nd)::value>), dim3(blocks64), dim3(256), 0, s, fd, pos, dir, n, feat, out36, occ);
+    hipLaunchKernelGGL((debug_field64_kernel<decltype(f)::value, decltype(nd)::value>), dim3(blocks64), dim3(256), 0, s, fd, pos, dir, n, feat, out36, occ, R);
   });
   return hipGetLastError();
 }

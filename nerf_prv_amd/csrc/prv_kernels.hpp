@@ -181,7 +181,7 @@ hipError_t launch_repack_level(const uint16_t* canon, uint16_t* phys, const Repa
 hipError_t launch_march(const MarchParams& P, int n_views, int n_spp, hipStream_t s);
 hipError_t launch_spp_reduce(const float* stage, size_t n_pixels, int spp, const float bg[4], float* out, uint32_t* out_u8,
                              hipStream_t s);
-hipError_t launch_render(const RenderParams& P, int n_blocks, hipStream_t s);
+hipError_t launch_render(const RenderParams& P, const ReplicaDev& R, int n_blocks, hipStream_t s); // R: the model's replicas (n_levels 0: none)
 hipError_t launch_render_planes(const RenderPlanesParams& P, int mode, int n_blocks, hipStream_t s); // mode: kRenderDepth / Entropy / Footprint / Surface / Termination
 hipError_t launch_spp_reduce_depth(const float* stage, size_t n_pixels, int spp, float* out, hipStream_t s);
 hipError_t launch_score_entropy(const float* entropy, const float* alpha, size_t npix, int n_views, int n_blocks, double* partial,
@@ -221,6 +221,30 @@ void with_field_instance(const FieldDev& fd, Fn&& fn) {
     else fn(integral_constant<int, 2>{}, integral_constant<int, 0>{});
   }
 }
+// Dense replicas of hashed levels (prv_device.hpp: ReplicaDev).  Only the <4, 5> instance has replica variants: a model holds
+// replicas only if it runs that instance, and the launch goes by what the model holds (0: the plain instance).
+// The engine's stepping rule (dt = 0.43 finest cells: it walks the occupied volume densely) gathers from the replicas of at most
+// two levels, whatever the model holds.  64 views 800x800 of api.FIELD_256 under that rule, render launch: 40.35 ms without
+// replicas, 38.97 / 38.31 / 40.81 ms with 1 / 2 / 3 -- the finest level's 143 MB replica costs more in L2 misses than its hash
+// did in instructions.  Under the fixed-S rule all three win (8.07 -> 7.77 / 7.59 / 7.51 ms).  profiles/NOTES.md
+constexpr int kReplicaLevelsNgp = 2;
+inline int replica_instance_levels(const FieldDev& fd, const ReplicaDev& R) {
+  return R.table && fd.n_features == 4 && render_instance_dense_levels(fd) == 5 ? R.n_levels : 0;
+}
+// one replica of a level of `res` vertices per axis: rows of res + 1 entries rounded up to 8, as many rows per plane, res + 1
+// planes; levels start at multiples of 4 KiB.  0 bytes: the level cannot be replicated (its z stride must stay below 2^24 for
+// the gather's 24-bit multiplies, its row count / 8 inside the 12 low bits of the pack word)
+struct ReplicaLevelLayout {
+  uint32_t row;   // entries per row = rows per plane
+  uint64_t bytes; // row * row * (res + 1) * ebytes, rounded up to 4 KiB
+};
+inline ReplicaLevelLayout replica_level_layout(uint32_t res, uint32_t ebytes) {
+  const uint32_t row = (res + 1u + 7u) & ~7u;
+  const uint64_t mz = (uint64_t)row * row * ebytes;
+  if (mz >= (1ull << 24) || row / 8u > 4095u) return {row, 0};
+  return {row, (mz * (res + 1u) + 4095ull) & ~4095ull};
+}
+hipError_t launch_fill_replica(const FieldDev& fd, const ReplicaDev& R, int k, hipStream_t s); // replica k from fd.table (the physical table)
 struct PreceptPose {
   double w2c[16], c2w[16];
 };
@@ -242,7 +266,7 @@ hipError_t launch_score_finalize(const double* partial, int n_views, int n_block
 hipError_t launch_synth_table(uint16_t* table, size_t n, uint64_t seed, float amp, hipStream_t s);
 hipError_t launch_debug_raygen(const CamDev& cam, int W, int H, int spp_k, float* o, float* d, float* t,
                                hipStream_t s);
-hipError_t launch_debug_field(const FieldDev& fd, const float* pos, const float* dir, int n, uint16_t* feat,
+hipError_t launch_debug_field(const FieldDev& fd, const ReplicaDev& R, const float* pos, const float* dir, int n, uint16_t* feat,
                               float* out36, int32_t* occ, hipStream_t s);
 
 } // namespace prv

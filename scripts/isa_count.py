@@ -2,7 +2,9 @@
 """Static instruction counts of a render kernel instance's hot loop (dev tool): compiles prv_kernels.hip to assembly and
 prints, per basic block with more than a few VALU instructions, the VALU / MFMA / VMEM / LDS / SALU counts, plus the opcode
 histogram of the two hot blocks (gather, MLP + compositing).
-  python scripts/isa_count.py [F] [NDENSE] [ngp: 0|1] [--json]
+  python scripts/isa_count.py [F] [NDENSE] [ngp: 0|1] [--json] [--cache | --repl=N]
+--repl=N: the <4, 5> instance that reads its first N hashed levels from dense replicas (render_queue64_replica_kernel<NGP, N>:
+what a model holding replicas launches -- api.FIELD_256 by default, N = 3); recorded under the key of <4, 5>, as bench.py looks it up.
 --json: also record the issue-class histogram of the two hot blocks (c2 / c4 / c8 / mfma: the classes
 scripts/valu_rate.hip measured, profiles/r04_valu_issue_rate.txt) in profiles/r06_isa_classes.json, keyed by the kernel
 instance and stamped with the digest of the device code -- what bench.py prices the ISSUED instructions with."""
@@ -16,13 +18,17 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from nerf_prv_amd import build as b  # noqa: E402
 
 WANT_JSON = "--json" in sys.argv
-F, ND, NGP = ([a for a in sys.argv if a not in ("--json", "--cache")] + ["4", "5", "0"])[1:4]
+REPL = next((int(a.split("=")[1]) for a in sys.argv if a.startswith("--repl=")), 0)
+F, ND, NGP = ([a for a in sys.argv if a not in ("--json", "--cache") and not a.startswith("--repl=")] + ["4", "5", "0"])[1:4]
 asm = "/tmp/prv_kernels.s"
 flags = [f for f in b.HIP_FLAGS if f not in ("-shared", "-fPIC")]
 subprocess.run([b.hipcc()] + flags + ["-S", "--cuda-device-only", "-o", asm, os.path.join(b.CSRC, "prv_kernels.hip")], check=True,
                stderr=subprocess.DEVNULL)
 CACHE = "1" if "--cache" in sys.argv else "0"  # the CornerCache instance (small images under the engine's rule)
 name = f"_ZN3prv21render_queue64_kernelILi{F}ELi{ND}ELb{NGP}ELb{CACHE}EEEvNS_12RenderParamsE"
+if REPL:
+    assert (F, ND, CACHE) == ("4", "5", "0"), "replica variants exist for <4, 5> only"
+    name = f"_ZN3prv29render_queue64_replica_kernelILb{NGP}ELi{REPL}EEEvNS_12RenderParamsENS_10ReplicaDevE"
 text = open(asm).read().split("\n")
 start = next(i for i, l in enumerate(text) if l.startswith(name + ":"))
 end = next(i for i in range(start, len(text)) if "s_endpgm" in text[i])
@@ -48,7 +54,7 @@ def ops(a, z):
 
 
 labels = [i for i, l in enumerate(lines) if re.match(r"^\.LBB\d+_\d+:", l)] + [len(lines)]
-print(f"render_queue64_kernel<{F}, {ND}, {NGP}, {CACHE}>: blocks with > 12 VALU instructions")
+print(f"render_queue64_kernel<{F}, {ND}, {NGP}, {CACHE}>" + (f", replicas of {REPL} levels" if REPL else "") + ": blocks with > 12 VALU instructions")
 hot = []
 for a, z in zip(labels, labels[1:]):
     c = collections.Counter(cls(o) for o in ops(a, z))
@@ -88,6 +94,6 @@ if WANT_JSON and len(hot) >= 2:
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "r06_isa_classes.json")
     data = json.load(open(path)) if os.path.exists(path) else {}
     data[f"64<{F}, {ND}>" + (" ngp" if NGP == "1" else "") + (" cache" if CACHE == "1" else "")] = dict(hist, device_code_sha256=_lib.device_code_digest(),
-                                                                    source="scripts/isa_count.py: static histogram of the gather block and the MLP + compositing block")
+                                                                    source="scripts/isa_count.py: static histogram of the gather block and the MLP + compositing block" + (f" of render_queue64_replica_kernel<{NGP}, {REPL}>" if REPL else ""))
     json.dump(data, open(path, "w"), indent=1)
     print("  issue classes of the hot loop:", dict(hist))
