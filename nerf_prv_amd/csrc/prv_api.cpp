@@ -26,6 +26,7 @@
 #include "prv_coverage.hpp"
 #include "prv_raster.hpp"
 #include "prv_levels.hpp"
+#include "prv_field_plan.hpp"
 #include "prv_ingp.hpp"
 #include "prv_train.hpp"
 #include "prv_train_switches.hpp"
@@ -49,6 +50,7 @@ struct Model {
   FieldDev dev{};
   uint64_t table_halfs = 0, occ_words = 0;
   uint64_t phys_bytes = 0; // the kernel layout of THIS field (phys may be a larger allocation left by an earlier one)
+  int n_hashed_levels = 0;
   float occ_lo[3] = {0, 0, 0}, occ_hi[3] = {1, 1, 1};
   Buffer table, phys, occ, occ_coarse, frags, frags64, mlp; // table/mlp = canonical (ABI) copies kept for export; phys = kernel layout
   // dense replicas of the leading hashed levels, for the render launch and the field hook (build_replicas); a buffer of their
@@ -168,317 +170,124 @@ int handle_alive(const prv_handle* h, const char* name, const char* the_name) {
   return PRV_OK;
 }
 
-static_assert(kMaxFieldLevels == kMaxLevels, "level tables of the host and the kernels must agree");
+static_assert(kMaxFieldLevels == kMaxLevels && kPlanNumFrags == kNumFrags && kPlanFragHalfs == kFragHalfs && kPlanMaxReplicas == kMaxReplicas,
+              "the host's plan (prv_field_plan.hpp) and the kernels (prv_device.hpp) must agree");
+static_assert(sizeof(LevelPlan) == sizeof(LevelDev), "LevelPlan mirrors LevelDev: a new member goes into both and into fill_field_dev");
 
-// ---- MFMA A-fragment prepack.  Canonical weights W[layer][in][out] (fp16 bits).
-// Fragment (layer, mt, s): lane (r,h), element j = W[kmap(s,h,j)][32*mt + r], zero past n_out.
-const int kIn[5] = {32, 64, 32, 64, 64};
-const int kOut[5] = {64, 16, 64, 64, 16};
-const int kOff[5] = {0, 2048, 3072, 5120, 9216};
-
-// hidden unit held by element j of lane half h in k-step s of a 64-wide activation
-inline int hidden_k(int s, int h, int j) { return 32 * (s >> 1) + 16 * (s & 1) + 8 * (j >> 2) + 4 * h + (j & 3); }
-
-// v64 = the fragment set of render_queue64: first-layer k rows in canonical feature order (the lane gathers every
-// level of its own sample), and the units the compositing needs repeated in padding rows that land in lane half 1:
-// density layer 2's unit 0 at row 20 (register 8), colour layer 3's units 0..2 at rows 20..22 (registers 8..10).
-void prepack_fragments(const uint16_t* mlp, int n_features, std::vector<uint16_t>& frags, bool v64 = false) {
-  frags.assign((size_t)kNumFrags * kFragHalfs, 0);
-  int f = 0;
-  auto emit = [&](int layer, int mt, int s, int (*kmap)(int, int, int)) {
-    uint16_t* dst = frags.data() + (size_t)f * kFragHalfs;
-    for (int lane = 0; lane < 64; lane++) {
-      const int r = lane & 31, h = lane >> 5;
-      int out = 32 * mt + r;
-      if (v64 && (layer == 1 || layer == 4) && out >= 20 && out < 20 + (layer == 1 ? 1 : 3)) out -= 20;
-      for (int j = 0; j < 8; j++) {
-        const int k = kmap(s, h, j);
-        dst[lane * 8 + j] = out < kOut[layer] ? mlp[kOff[layer] + k * kOut[layer] + out] : (uint16_t)0;
-      }
-    }
-    f++;
-  };
-  // grid features: fragment s, element j of lane half h = feature (j % F) of level 2*(s*LH/2 + j/F) + h
-  auto k_feat4 = [](int s, int h, int j) { return 4 * (2 * (s * 2 + j / 4) + h) + j % 4; };
-  auto k_feat2 = [](int s, int h, int j) { return 2 * (2 * (s * 4 + j / 2) + h) + j % 2; };
-  auto k_rgb_in = [](int s, int h, int j) { return s == 0 ? hidden_k(0, h, j) : 16 + 8 * h + j; }; // [dens | SH]
-  auto k_canon = [](int s, int h, int j) { return 16 * s + 8 * h + j; };
-  for (int mt = 0; mt < 2; mt++)
-    for (int s = 0; s < 2; s++)
-      emit(0, mt, s, v64 ? (int (*)(int, int, int))k_canon : n_features == 4 ? (int (*)(int, int, int))k_feat4 : (int (*)(int, int, int))k_feat2);
-  for (int s = 0; s < 4; s++) emit(1, 0, s, hidden_k);
-  for (int mt = 0; mt < 2; mt++)
-    for (int s = 0; s < 2; s++) emit(2, mt, s, k_rgb_in);
-  for (int mt = 0; mt < 2; mt++)
-    for (int s = 0; s < 4; s++) emit(3, mt, s, hidden_k);
-  for (int s = 0; s < 4; s++) emit(4, 0, s, hidden_k);
-}
-
-// ---- host fp16 + counter RNG for the (tiny) synthetic MLP weights and occupancy
-uint16_t f2h(float f) {
-  _Float16 h = (_Float16)f; // host clang: IEEE RNE conversion
-  uint16_t u;
-  memcpy(&u, &h, 2);
-  return u;
-}
-uint64_t mix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-float rng_sym(uint64_t seed, uint64_t stream, uint64_t i, float amp) {
-  const uint64_t hsh = mix64(seed + (stream + 1) * 0xD1B54A32D192ED03ull + i * 0x9E3779B97F4A7C15ull);
-  const uint32_t u = (uint32_t)(hsh >> 40);
-  const float v = (float)u * (1.0f / 8388608.0f) - 1.0f;
-  return v * amp;
-}
-const float kSynthSpheres[4][4] = {
-    {0.50f, 0.50f, 0.50f, 0.35f}, {0.80f, 0.50f, 0.62f, 0.13f}, {0.36f, 0.80f, 0.45f, 0.11f}, {0.40f, 0.24f, 0.78f, 0.10f}};
-
-// Dense replicas of the leading hashed levels of a model whose render runs the <4, 5> instance (prv_device.hpp: ReplicaDev): the
-// hash is there to save memory while TRAINING; an installed model's table is constant until the next install, so the hash is
-// undone here, once, and the render's gather of those levels is the dense one.  As many levels, from the coarsest, as fit the
-// budget -- PRV_REPLICA_MB, default kReplicaBudgetDefault -- and at most PRV_REPLICA_LEVELS (0..3; 0: none), both read here
-// like PRV_NO_PAIR.  Every other field (F = 2, the generic instances, wide offsets, levels finer than their table: whatever
-// render_instance_dense_levels does not answer 5 for) gets none and gives the buffer back.  Called at the end of every
-// install, a trainer's publish included (republish_model), once m.dev and the physical table are complete.
-constexpr uint64_t kReplicaBudgetDefault = (uint64_t)256 << 20; // api.FIELD_256: 13.5 + 43.1 + 143.3 MB for its three hashed levels
-
-int build_replicas(prv_ctx* c, Model& m) {
-  const FieldDev& f = m.dev;
-  m.rdev = ReplicaDev{};
-  m.repl_bytes = 0;
+// What an install of `d` into `slot` will do, decided before anything is allocated or copied (prv_field_plan.hpp).  A descriptor
+// that is no field at all changes nothing; a field the kernels cannot lay out leaves an empty slot, like every failed install.
+// The only place that reads the install-time switches, at every install: PRV_NO_PAIR (the generic gather for every level),
+// PRV_REPLICA_LEVELS (0..3; 0: no replicas) and PRV_REPLICA_MB (their budget, default kReplicaBudgetDefault).
+struct ModelPlan {
+  FieldPlan field;
+  ReplicaPlan repl;
+};
+int plan_model(prv_ctx* c, int slot, const prv_field_desc& d, ModelPlan& P) {
   int cap = kMaxReplicas;
   uint64_t budget = kReplicaBudgetDefault;
   if (const char* e = getenv("PRV_REPLICA_LEVELS")) cap = std::max(0, std::min(kMaxReplicas, atoi(e)));
   if (const char* e = getenv("PRV_REPLICA_MB")) budget = (uint64_t)std::max(0ll, std::min(strtoll(e, nullptr, 10), 1ll << 20)) << 20;
-  int n = 0;
-  uint64_t total = 0;
-  uint32_t pack[kMaxReplicas] = {0, 0, 0};
-  if (f.n_features == 4 && render_instance_dense_levels(f) == 5) {
-    for (int l = f.n_dense_levels; l < f.n_levels && n < cap; l++, n++) {
-      const uint32_t res = f.levels[l].res_m1 + 1u;
-      const ReplicaLevelLayout lay = replica_level_layout(res, 8u);
-      if (res > 1024u || lay.bytes == 0 || total + lay.bytes > budget || total + lay.bytes >= (1ull << 32)) break;
-      pack[n] = (uint32_t)total | (lay.row / 8u); // total is a multiple of 4 KiB, row / 8 < 4096
-      total += lay.bytes;
-    }
+  std::string why;
+  const int rc = plan_field(d, getenv("PRV_NO_PAIR") != nullptr, P.field, why);
+  if (rc != PRV_OK) {
+    if (P.field.n_levels) c->models[slot].loaded = false;
+    return fail(c, rc, "%s", why.c_str());
   }
-  if (n == 0) {
+  P.repl = plan_replicas(P.field, cap, budget);
+  return PRV_OK;
+}
+
+void fill_field_dev(FieldDev& f, const Model& m, const FieldPlan& P) {
+  memset(&f, 0, sizeof(f));
+  f.table = (const uint16_t*)m.phys.p;
+  f.occ = (const uint32_t*)m.occ.p;
+  f.occ_coarse = P.has_coarse_occupancy() ? (const uint32_t*)m.occ_coarse.p : nullptr;
+  f.frags = (const half8*)m.frags.p;
+  f.frags64 = (const half8*)m.frags64.p;
+  f.n_levels = P.n_levels;
+  f.n_features = P.desc.n_features;
+  f.occ_res = P.desc.occ_res;
+  f.density_bias = P.desc.density_bias;
+  for (int a = 0; a < 3; a++) {
+    f.occ_lo[a] = m.occ_lo[a];
+    f.occ_hi[a] = m.occ_hi[a];
+  }
+  f.n_dense_levels = P.n_dense_levels;
+  f.hash_my_b = P.hash_my_b;
+  f.hash_mz_b = P.hash_mz_b;
+  f.hash_m_b = P.hash_m_b;
+  f.hash_shared = P.hash_shared;
+  f.wide_offsets = P.wide_offsets;
+  for (int l = 0; l < P.n_levels; l++) {
+    const LevelPlan& s = P.levels[l];
+    f.levels[l] = LevelDev{s.scale, s.res_m1, s.my_b, s.mz_b, s.m_b, s.off_b, s.myz_b, s.pack};
+  }
+}
+
+// Dense replicas of the leading hashed levels of a model whose render runs the <4, 5> instance (prv_device.hpp: ReplicaDev): the
+// hash is there to save memory while TRAINING; an installed model's table is constant until the next install, so the hash is
+// undone here, once, and the render's gather of those levels is the dense one.  Which levels, and where: plan_replicas
+// (prv_field_plan.hpp); a field that gets none gives the buffer back.  Called at the end of every install, a trainer's publish
+// included (republish_model), once m.dev and the physical table are complete.
+int build_replicas(prv_ctx* c, Model& m, const ReplicaPlan& R) {
+  m.rdev = ReplicaDev{};
+  m.repl_bytes = 0;
+  if (R.n == 0) {
     m.repl.reset(); // (the stream is idle: install_model has just waited for it)
     return PRV_OK;
   }
   int rc;
-  if ((rc = ensure(c, m.repl, total)) != PRV_OK) return rc;
+  if ((rc = ensure(c, m.repl, R.total_bytes)) != PRV_OK) return rc;
   m.rdev.table = (const uint16_t*)m.repl.p;
-  m.rdev.n_levels = n;
-  memcpy(m.rdev.pack, pack, sizeof(pack));
-  m.repl_bytes = total;
-  for (int k = 0; k < n; k++) HIPCHK(c, launch_fill_replica(f, m.rdev, k, c->stream)); // (padding rows and columns are never read)
+  m.rdev.n_levels = R.n;
+  memcpy(m.rdev.pack, R.pack, sizeof(R.pack));
+  m.repl_bytes = R.total_bytes;
+  for (int k = 0; k < R.n; k++) HIPCHK(c, launch_fill_replica(m.dev, m.rdev, k, c->stream)); // (padding rows and columns are never read)
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return PRV_OK;
 }
 
-int install_model(prv_ctx* c, int slot, const prv_field_desc& d, const uint16_t* mlp, const uint32_t* occ_host,
+int install_model(prv_ctx* c, int slot, const ModelPlan& plan, const uint16_t* mlp, const uint32_t* occ_host,
                   const uint16_t* table_host /* may be null: table already on device */) {
   Model& m = c->models[slot];
-  HostLevel lv[kMaxLevels];
-  uint64_t total = 0;
-  if (compute_levels(d, lv, &total) != 0) return fail(c, PRV_E_INVALID, "invalid field descriptor");
+  const FieldPlan& P = plan.field;
   m.loaded = false; // until everything below has succeeded: a failed install leaves an empty slot, not half a model
-  m.desc = d;
-  m.table_halfs = total * (uint64_t)d.n_features;
-  const uint64_t R = (uint64_t)d.occ_res;
-  m.occ_words = (R * R * R + 31) / 32;
+  m.desc = P.desc;
+  m.table_halfs = P.table_halfs();
+  m.occ_words = P.occ_words();
+  m.phys_bytes = P.phys_bytes();
+  m.n_hashed_levels = P.n_hashed_levels;
   int rc;
   if ((rc = ensure(c, m.table, m.table_halfs * 2)) != PRV_OK) return rc;
   if ((rc = ensure(c, m.occ, m.occ_words * 4)) != PRV_OK) return rc;
   if ((rc = ensure(c, m.frags, (size_t)kNumFrags * kFragHalfs * 2)) != PRV_OK) return rc;
   if ((rc = ensure(c, m.frags64, (size_t)kNumFrags * kFragHalfs * 2)) != PRV_OK) return rc;
   if ((rc = ensure(c, m.mlp, PRV_MLP_HALFS * 2)) != PRV_OK) return rc;
+  if ((rc = ensure(c, m.phys, m.phys_bytes)) != PRV_OK) return rc;
   if (table_host) HIPCHK(c, hipMemcpyAsync(m.table.p, table_host, m.table_halfs * 2, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(m.occ.p, occ_host, m.occ_words * 4, hipMemcpyHostToDevice, c->stream));
-  // bounding box of the occupied cells (grown by one cell) for the march pass
-  {
-    const int R = d.occ_res;
-    int lo[3] = {R, R, R}, hi[3] = {-1, -1, -1};
-    const bool words = R % 32 == 0; // a row is whole words: 65 K words instead of 2 M bits (the planner loop installs five fields per round)
-    for (int z = 0; words && z < R; z++)
-      for (int y = 0; y < R; y++)
-        for (int w = 0; w < R / 32; w++) {
-          const uint32_t v = occ_host[((size_t)R * ((size_t)y + (size_t)R * (size_t)z)) / 32 + (size_t)w];
-          if (!v) continue;
-          lo[0] = std::min(lo[0], 32 * w + __builtin_ctz(v));
-          hi[0] = std::max(hi[0], 32 * w + 31 - __builtin_clz(v));
-          lo[1] = std::min(lo[1], y);
-          hi[1] = std::max(hi[1], y);
-          lo[2] = std::min(lo[2], z);
-          hi[2] = std::max(hi[2], z);
-        }
-    for (int z = 0; !words && z < R; z++)
-      for (int y = 0; y < R; y++)
-        for (int x = 0; x < R; x++) {
-          const size_t b = (size_t)x + (size_t)R * ((size_t)y + (size_t)R * (size_t)z);
-          if (!((occ_host[b >> 5] >> (b & 31)) & 1u)) continue;
-          const int cxyz[3] = {x, y, z};
-          for (int a = 0; a < 3; a++) {
-            lo[a] = std::min(lo[a], cxyz[a]);
-            hi[a] = std::max(hi[a], cxyz[a]);
-          }
-        }
-    for (int a = 0; a < 3; a++) {
-      m.occ_lo[a] = hi[a] < 0 ? 2.0f : (float)(lo[a] - 1) / (float)R; // empty grid: an empty box
-      m.occ_hi[a] = hi[a] < 0 ? -1.0f : (float)(hi[a] + 2) / (float)R;
-    }
+  HIPCHK(c, hipMemcpyAsync(m.mlp.p, mlp, PRV_MLP_HALFS * 2, hipMemcpyHostToDevice, c->stream));
+  // canonical -> physical (the gaps of the power-of-two layout stay zero), while the host walks the occupancy grid and packs the fragments
+  HIPCHK(c, hipMemsetAsync(m.phys.p, 0, m.phys_bytes, c->stream));
+  for (int l = 0; l < P.n_levels; l++) {
+    RepackLevel R{P.lv[l].offset, P.poff[l], P.lv[l].size, P.lv[l].res, P.sx[l], P.lv[l].hashed};
+    HIPCHK(c, launch_repack_level((const uint16_t*)m.table.p, (uint16_t*)m.phys.p, R, P.desc.n_features, c->stream));
   }
-  // dilated coarse occupancy for the march pass: coarse cell = 4^3 fine cells; bit set when any fine
-  // cell of the block or of its 26 neighbour blocks is occupied
-  std::vector<uint32_t> coarse;
-  if (d.occ_res % 4 == 0 && d.occ_res >= 8) {
-    const int R = d.occ_res, Rc = R / 4;
-    std::vector<uint8_t> blk((size_t)Rc * Rc * Rc, 0);
-    const bool words = R % 32 == 0; // as above: a word is eight blocks' worth of one row
-    for (int z = 0; words && z < R; z++)
-      for (int y = 0; y < R; y++)
-        for (int w = 0; w < R / 32; w++) {
-          const uint32_t v = occ_host[((size_t)R * ((size_t)y + (size_t)R * (size_t)z)) / 32 + (size_t)w];
-          if (!v) continue;
-          uint8_t* row = &blk[(size_t)(8 * w) + (size_t)Rc * ((size_t)(y / 4) + (size_t)Rc * (size_t)(z / 4))];
-          for (int k = 0; k < 8; k++)
-            if ((v >> (4 * k)) & 0xfu) row[k] = 1;
-        }
-    for (int z = 0; !words && z < R; z++)
-      for (int y = 0; y < R; y++)
-        for (int x = 0; x < R; x += 32) { // 32 fine cells of a row = one word (R is a multiple of 4; handle R < 32 too)
-          const size_t bit0 = (size_t)x + (size_t)R * ((size_t)y + (size_t)R * (size_t)z);
-          for (int k = 0; k < 32 && x + k < R; k++) {
-            const size_t b = bit0 + k;
-            if ((occ_host[b >> 5] >> (b & 31)) & 1u) blk[(size_t)((x + k) / 4) + (size_t)Rc * ((size_t)(y / 4) + (size_t)Rc * (size_t)(z / 4))] = 1;
-          }
-        }
-    coarse.assign(((size_t)Rc * Rc * Rc + 31) / 32, 0u);
-    for (int z = 0; z < Rc; z++)
-      for (int y = 0; y < Rc; y++)
-        for (int x = 0; x < Rc; x++) {
-          bool any = false;
-          for (int dz = -1; dz <= 1 && !any; dz++)
-            for (int dy = -1; dy <= 1 && !any; dy++)
-              for (int dx = -1; dx <= 1 && !any; dx++) {
-                const int xx = x + dx, yy = y + dy, zz = z + dz;
-                if (xx < 0 || yy < 0 || zz < 0 || xx >= Rc || yy >= Rc || zz >= Rc) continue;
-                any = blk[(size_t)xx + (size_t)Rc * ((size_t)yy + (size_t)Rc * (size_t)zz)] != 0;
-              }
-          if (any) {
-            const size_t b = (size_t)x + (size_t)Rc * ((size_t)y + (size_t)Rc * (size_t)z);
-            coarse[b >> 5] |= 1u << (b & 31);
-          }
-        }
-    if ((rc = ensure(c, m.occ_coarse, coarse.size() * 4)) != PRV_OK) return rc;
-    HIPCHK(c, hipMemcpyAsync(m.occ_coarse.p, coarse.data(), coarse.size() * 4, hipMemcpyHostToDevice, c->stream));
+  const OccupancySummary occ = summarize_occupancy(occ_host, P.desc.occ_res);
+  const std::vector<uint16_t> frags = prepack_fragments(mlp, P.desc.n_features, false), frags64 = prepack_fragments(mlp, P.desc.n_features, true);
+  for (int a = 0; a < 3; a++) {
+    m.occ_lo[a] = occ.lo[a];
+    m.occ_hi[a] = occ.hi[a];
   }
-  std::vector<uint16_t> frags, frags64;
-  prepack_fragments(mlp, d.n_features, frags);
-  prepack_fragments(mlp, d.n_features, frags64, true);
+  if (!occ.coarse.empty()) {
+    if ((rc = ensure(c, m.occ_coarse, occ.coarse.size() * 4)) != PRV_OK) return rc;
+    HIPCHK(c, hipMemcpyAsync(m.occ_coarse.p, occ.coarse.data(), occ.coarse.size() * 4, hipMemcpyHostToDevice, c->stream));
+  }
   HIPCHK(c, hipMemcpyAsync(m.frags.p, frags.data(), frags.size() * 2, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(m.frags64.p, frags64.data(), frags64.size() * 2, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(m.mlp.p, mlp, PRV_MLP_HALFS * 2, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream)); // host staging vectors go out of scope
-  // ---- physical layout: power-of-two strides for dense levels, size-aligned level offsets
-  const uint32_t ebytes = (uint32_t)d.n_features * 2u;
-  uint32_t psize[kMaxLevels], sx[kMaxLevels], poff[kMaxLevels];
-  int order[kMaxLevels];
-  auto ceil_log2 = [](uint32_t v) { uint32_t s = 0; while ((1u << s) < v) s++; return s; };
-  for (int l = 0; l < d.n_levels; l++) {
-    order[l] = l;
-    if (lv[l].hashed) {
-      sx[l] = 0;
-      psize[l] = lv[l].size;
-    } else {
-      sx[l] = ceil_log2(lv[l].res + 1); // +1: room for the duplicated border vertex / row / plane
-      psize[l] = 1u << ceil_log2((lv[l].res + 1u) << (2 * sx[l])); // res + 1 planes: the last one is duplicated
-    }
-  }
-  std::stable_sort(order, order + d.n_levels, [&](int a, int b) { return psize[a] > psize[b]; });
-  uint64_t ptotal = 0;
-  for (int k = 0; k < d.n_levels; k++) {
-    poff[order[k]] = (uint32_t)ptotal; // multiple of every later (smaller or equal) power of two
-    ptotal += psize[order[k]];
-  }
-  if (ptotal * ebytes >= (1ull << 32)) return fail(c, PRV_E_INVALID, "field too large for 32-bit gather offsets");
-  if ((rc = ensure(c, m.phys, ptotal * ebytes)) != PRV_OK) return rc;
-  m.phys_bytes = ptotal * ebytes;
-  HIPCHK(c, hipMemsetAsync(m.phys.p, 0, ptotal * ebytes, c->stream));
-  for (int l = 0; l < d.n_levels; l++) {
-    RepackLevel R{lv[l].offset, poff[l], lv[l].size, lv[l].res, sx[l], lv[l].hashed};
-    HIPCHK(c, launch_repack_level((const uint16_t*)m.table.p, (uint16_t*)m.phys.p, R, d.n_features, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  FieldDev& f = m.dev;
-  memset(&f, 0, sizeof(f));
-  f.table = (const uint16_t*)m.phys.p;
-  f.occ = (const uint32_t*)m.occ.p;
-  f.occ_coarse = (d.occ_res % 4 == 0 && d.occ_res >= 8) ? (const uint32_t*)m.occ_coarse.p : nullptr;
-  f.frags = (const half8*)m.frags.p;
-  f.frags64 = (const half8*)m.frags64.p;
-  f.n_levels = d.n_levels;
-  f.n_features = d.n_features;
-  f.occ_res = d.occ_res;
-  f.density_bias = d.density_bias;
-  for (int a = 0; a < 3; a++) {
-    f.occ_lo[a] = m.occ_lo[a];
-    f.occ_hi[a] = m.occ_hi[a];
-  }
-  f.n_dense_levels = 0;
-  while (f.n_dense_levels < d.n_levels && !lv[f.n_dense_levels].hashed) f.n_dense_levels++;
-  if (getenv("PRV_NO_PAIR")) f.n_dense_levels = 0; // tests: every level through the generic (clamped, 8-load) gather
-  // the hashed levels' shared constants (every hashed level has T entries of ebytes): valid for the kernel's shared path
-  // when no hashed level is finer than its table, so that (x << esh) needs no mask
-  f.hash_my_b = (2654435761u * ebytes) & 0xffffffu;
-  f.hash_mz_b = (805459861u * ebytes) & 0xffffffu;
-  f.hash_m_b = (uint32_t)(((1ull << d.log2_hashmap) - 1ull) * ebytes);
-  f.hash_shared = 1;
-  f.wide_offsets = 0;
-  for (int l = 0; l < d.n_levels; l++)
-    if (lv[l].hashed && (lv[l].res > lv[l].size || l < f.n_dense_levels)) f.hash_shared = 0;
-  if (getenv("PRV_NO_PAIR")) f.hash_shared = 0;
-  for (int l = 0; l < d.n_levels; l++) {
-    LevelDev& L = f.levels[l];
-    L.scale = lv[l].scale;
-    L.res_m1 = lv[l].res - 1;
-    if (lv[l].res > 4096) return fail(c, PRV_E_INVALID, "level %d has %u vertices per axis (limit 4096)", l, lv[l].res);
-    if (lv[l].hashed) {
-      // the kernels multiply with v_mul_u32_u24 (the low 24 bits of the constants are all a level of <= 16 MiB needs).  A hashed
-      // level LARGER than 16 MiB (round 6: tables that really leave the 256 MiB Infinity Cache, e.g. log2_hashmap 24 at F = 2)
-      // keeps the full 32-bit constants and runs the generic instance, whose gather then multiplies in 32 bits (wide_offsets)
-      if ((uint64_t)(lv[l].size - 1u) * ebytes >= (1ull << 32)) return fail(c, PRV_E_INVALID, "hashed level of 4 GiB or more");
-      L.m_b = (lv[l].size - 1u) * ebytes;
-      const bool wide = L.m_b >= (1u << 24);
-      L.my_b = wide ? 2654435761u * ebytes : (2654435761u * ebytes) & 0xffffffu;
-      L.mz_b = wide ? 805459861u * ebytes : (805459861u * ebytes) & 0xffffffu;
-      if (wide) {
-        f.wide_offsets = 1;
-        f.hash_shared = 0;
-      }
-    } else {
-      L.my_b = ebytes << sx[l];
-      L.mz_b = ebytes << (2 * sx[l]);
-      L.m_b = 0xffffffffu;
-      if (L.mz_b >= (1u << 24) || lv[l].res > 4096) return fail(c, PRV_E_INVALID, "dense level too large");
-    }
-    L.off_b = poff[l] * ebytes;
-    L.myz_b = L.my_b + L.mz_b;
-    // the render kernel's packed word (prv_device.hpp: LevelDev::pack); the alignment the packing relies on is checked
-    // (a field whose offsets leave no room for it -- hashed tables below 4 KiB -- runs the generic instance, which reads the
-    // unpacked constants)
-    if (lv[l].hashed) {
-      if ((L.off_b & 4095u) != 0u || L.res_m1 > 4095u) f.hash_shared = 0;
-      L.pack = (L.off_b & ~4095u) | (L.res_m1 & 4095u);
-    } else {
-      if ((L.off_b & 31u) != 0u || sx[l] > 31u) f.hash_shared = 0;
-      L.pack = (L.off_b & ~31u) | (sx[l] & 31u);
-    }
-  }
-  if ((rc = build_replicas(c, m)) != PRV_OK) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream)); // the host staging vectors go out of scope
+  fill_field_dev(m.dev, m, P);
+  if ((rc = build_replicas(c, m, plan.repl)) != PRV_OK) return rc;
   m.loaded = true;
   m.dirty = false;
   return PRV_OK;
@@ -493,8 +302,10 @@ int republish_model(prv_ctx* c, int slot) {
   HIPCHK(c, hipMemcpyAsync(mlp.data(), m.mlp.p, PRV_MLP_HALFS * 2, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(occ.data(), m.occ.p, m.occ_words * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const prv_field_desc d = m.desc;
-  return install_model(c, slot, d, mlp.data(), occ.data(), nullptr);
+  ModelPlan plan;
+  int rc;
+  if ((rc = plan_model(c, slot, m.desc, plan)) != PRV_OK) return rc;
+  return install_model(c, slot, plan, mlp.data(), occ.data(), nullptr);
 }
 
 int model_present(prv_ctx* c, int slot) {
@@ -1348,13 +1159,13 @@ int prv_memcpy_d2h(prv_ctx* c, void* d, const void* s, size_t bytes) try {
 
 int prv_model_sizes(const prv_field_desc* d, uint64_t* table_halfs, uint64_t* mlp_halfs, uint64_t* occ_words) try {
   if (!d) return PRV_E_INVALID;
-  HostLevel lv[kMaxLevels];
-  uint64_t total = 0;
-  if (compute_levels(*d, lv, &total) != 0) return PRV_E_INVALID;
-  if (table_halfs) *table_halfs = total * (uint64_t)d->n_features;
+  FieldPlan P;
+  std::string why;
+  plan_field(*d, false, P, why); // the sizes of every field compute_levels accepts, also of one the kernels could not lay out
+  if (!P.n_levels) return PRV_E_INVALID;
+  if (table_halfs) *table_halfs = P.table_halfs();
   if (mlp_halfs) *mlp_halfs = PRV_MLP_HALFS;
-  const uint64_t R = (uint64_t)d->occ_res;
-  if (occ_words) *occ_words = (R * R * R + 31) / 32;
+  if (occ_words) *occ_words = P.occ_words();
   return PRV_OK;
 } catch (...) { return caught(nullptr); }
 
@@ -1365,7 +1176,10 @@ int prv_model_load(prv_ctx* c, int slot, const prv_field_desc* d, const uint16_t
   if (!d || !table || !mlp || !occ) return fail(c, PRV_E_INVALID, "NULL argument");
   HIPCHK(c, hipSetDevice(c->device));
   c->models[slot].generation++; // a live trainer of this slot holds stale masters from now on (train_check)
-  return install_model(c, slot, *d, mlp, occ, table);
+  ModelPlan plan;
+  int rc;
+  if ((rc = plan_model(c, slot, *d, plan)) != PRV_OK) return rc;
+  return install_model(c, slot, plan, mlp, occ, table);
 } catch (...) { return caught(c); }
 
 static int model_synthetic(prv_ctx* c, int slot, const prv_field_desc* d, uint64_t seed, bool all_occupied);
@@ -1380,46 +1194,16 @@ static int model_synthetic(prv_ctx* c, int slot, const prv_field_desc* d, uint64
   if (slot < 0 || slot >= PRV_MAX_SLOTS) return fail(c, PRV_E_INVALID, "model slot %d out of range", slot);
   if (!d) return fail(c, PRV_E_INVALID, "NULL descriptor");
   HIPCHK(c, hipSetDevice(c->device));
-  HostLevel lv[kMaxLevels];
-  uint64_t total = 0;
-  if (compute_levels(*d, lv, &total) != 0) return fail(c, PRV_E_INVALID, "invalid field descriptor");
-  std::vector<uint16_t> mlp(PRV_MLP_HALFS);
-  size_t o = 0;
-  for (int l = 0; l < 5; l++) {
-    const float amp = sqrtf(6.0f / (float)(kIn[l] + kOut[l]));
-    const size_t cnt = (size_t)kIn[l] * kOut[l];
-    for (size_t i = 0; i < cnt; i++) mlp[o + i] = f2h(rng_sym(seed, (uint64_t)(l + 1), i, amp));
-    o += cnt;
-  }
-  const int R = d->occ_res;
-  std::vector<uint32_t> occ(((size_t)R * R * R + 31) / 32, 0u);
-  const float invR = 1.0f / (float)R;
-  if (all_occupied) { // a fresh field (the planner loop makes five per round): every cell, without the walk over 2 M of them
-    const size_t n_cells = (size_t)R * R * R;
-    std::fill(occ.begin(), occ.end(), 0xffffffffu);
-    if (n_cells & 31) occ.back() = (1u << (n_cells & 31)) - 1u;
-  }
-  for (int z = 0; z < (all_occupied ? 0 : R); z++)
-    for (int y = 0; y < R; y++)
-      for (int x = 0; x < R; x++) {
-        const float cx = ((float)x + 0.5f) * invR, cy = ((float)y + 0.5f) * invR, cz = ((float)z + 0.5f) * invR;
-        bool in = false;
-        for (int b = 0; b < 4 && !in; b++) {
-          const float dx = cx - kSynthSpheres[b][0], dy = cy - kSynthSpheres[b][1], dz = cz - kSynthSpheres[b][2];
-          const float d2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
-          in = d2 <= kSynthSpheres[b][3] * kSynthSpheres[b][3];
-        }
-        if (in) {
-          const size_t bit = (size_t)x + (size_t)R * ((size_t)y + (size_t)R * (size_t)z);
-          occ[bit >> 5] |= 1u << (bit & 31);
-        }
-      }
+  ModelPlan plan;
+  int rc;
+  if ((rc = plan_model(c, slot, *d, plan)) != PRV_OK) return rc;
+  const std::vector<uint16_t> mlp = synthetic_mlp(seed);
+  const std::vector<uint32_t> occ = synthetic_occupancy(d->occ_res, all_occupied);
   Model& m = c->models[slot];
-  int rc = ensure(c, m.table, total * (uint64_t)d->n_features * 2);
-  if (rc != PRV_OK) return rc;
-  HIPCHK(c, launch_synth_table((uint16_t*)m.table.p, total * (uint64_t)d->n_features, seed, d->table_amp, c->stream));
+  if ((rc = ensure(c, m.table, plan.field.table_halfs() * 2)) != PRV_OK) return rc;
+  HIPCHK(c, launch_synth_table((uint16_t*)m.table.p, plan.field.table_halfs(), seed, d->table_amp, c->stream));
   m.generation++;
-  return install_model(c, slot, *d, mlp.data(), occ.data(), nullptr);
+  return install_model(c, slot, plan, mlp.data(), occ.data(), nullptr);
 }
 
 int prv_model_export(prv_ctx* c, int slot, uint16_t* table, uint16_t* mlp, uint32_t* occ) try {
@@ -2224,17 +2008,13 @@ int prv_debug_model_layout(prv_ctx* c, int slot, prv_model_layout* out) try {
   if (rc != PRV_OK) return rc;
   if (!out) return fail(c, PRV_E_INVALID, "out is NULL");
   const Model& m = c->models[slot];
-  HostLevel lv[kMaxLevels];
-  uint64_t total = 0;
-  compute_levels(m.desc, lv, &total);
   out->table_bytes_canonical = m.table_halfs * 2;
   out->table_bytes_physical = m.phys_bytes;
   out->kernel_features = m.dev.n_features;
   out->kernel_dense_levels = render_instance_dense_levels(m.dev);
   out->kernel_slots = 64;
   out->n_dense_levels = m.dev.n_dense_levels;
-  out->n_hashed_levels = 0;
-  for (int l = 0; l < m.desc.n_levels; l++) out->n_hashed_levels += lv[l].hashed ? 1 : 0;
+  out->n_hashed_levels = m.n_hashed_levels;
   return PRV_OK;
 } catch (...) { return caught(c); }
 

@@ -71,7 +71,7 @@ struct FieldDev {
 };
 
 // Dense REPLICAS of the leading hashed levels of a field that runs the <4, 5> render instance (built where the model is
-// installed, prv_api.cpp: build_replicas; a buffer of their own beside the physical table).  A model that is rendered has a
+// installed: prv_field_plan.hpp: plan_replicas, prv_api.cpp: build_replicas; a buffer of their own beside the physical table).  A model that is rendered has a
 // constant table, so the hash can be undone once: replica[x, y, z] = the entry the hashed gather fetches for vertex
 // (min(x, res-1), min(y, res-1), min(z, res-1)), x, y, z in [0, res] -- the dense levels' duplicated border.  The level then
 // goes through the dense gather (4 paired loads, no clamps, no hash) and yields the same entries: features are bit-identical.
@@ -764,7 +764,7 @@ __device__ __forceinline__ MlpOut mlp_forward(const half8* __restrict__ wl, int 
 
 // Both MLPs for TWO column groups of 32 samples (render_queue64: the wave's lanes 0..31 and 32..63 each own a sample):
 // every weight fragment is read from LDS once and used for both groups; the groups' chains are independent, so one
-// group's MFMAs run while the other group's accumulators are being packed.  Fragments: the `frags64` set (prv_api.cpp:
+// group's MFMAs run while the other group's accumulators are being packed.  Fragments: the `frags64` set (prepack_fragments:
 // first-layer k rows in canonical feature order; the density layer's unit 0 and the colour layer's units 0..2 repeated in
 // the padding rows 20 / 20..22, which land in lane half 1: register 8 / registers 8..10).
 struct MlpOut2 {

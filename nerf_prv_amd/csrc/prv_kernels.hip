@@ -1164,7 +1164,7 @@ void render_queue64_kernel(RenderParams P) {
   render_queue64_body<F, NDENSE, NGP, CACHE, kRenderColour>(P, nullptr);
 }
 
-// render_queue64_kernel<4, 5, NGP, false> for a model that holds dense replicas of its first NREPL hashed levels (prv_api.cpp:
+// render_queue64_kernel<4, 5, NGP, false> for a model that holds dense replicas of its first NREPL hashed levels (plan_replicas,
 // build_replicas): those levels cost 4 address instructions and 4 paired loads each instead of 26 and 8.  Same pixels.
 template <bool NGP, int NREPL>
 __global__ __launch_bounds__(256)

@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/prv.h"
 #include "prv_device.hpp"
+#include "prv_field_plan.hpp"
 #include <type_traits>
 
 namespace prv {
@@ -196,15 +197,8 @@ struct TerminationJsdParams {
   double* partial; // [view][block][2]: the block's sums of J and of the members' mean opacity
 };
 hipError_t launch_score_termination_jsd(const TerminationJsdParams& P, int n_views, int n_blocks, hipStream_t s);
-// compiled instances of the field-evaluating kernels (render, planes, mesh, field hook): NDENSE = the field's count of leading dense levels when an
-// instance for exactly that count exists (5 / 3 for F = 4, 10 / 6 for F = 2: api.FIELD_256 / FIELD_512 run <4,5> / <2,10>) and its hashed levels share their hash
-// constants; any other field -- util.SMALL (4 dense), SMALL_F2 (9), instant-ngp's base.json (F = 2, 5 dense), levels > 16 MiB -- runs <F, 0> (tests/instances.py)
-inline int render_instance_dense_levels(const FieldDev& fd) {
-  const int n = fd.n_dense_levels;
-  if (!fd.hash_shared) return 0;
-  if (fd.n_features == 4) return n == 5 ? 5 : n == 3 ? 3 : 0;
-  return n == 10 ? 10 : n == 6 ? 6 : 0;
-}
+// the compiled instance of the field-evaluating kernels (render, planes, mesh, field hook) a field runs on: prv_field_plan.hpp has the rule
+inline int render_instance_dense_levels(const FieldDev& fd) { return instance_dense_levels(fd.n_features, fd.n_dense_levels, fd.hash_shared); }
 // calls fn(std::integral_constant<int, F>{}, std::integral_constant<int, NDENSE>{}) for the one compiled instance fd runs on:
 // the only list of the six (F, NDENSE) pairs a kernel template is instantiated for
 template <class Fn>
@@ -231,19 +225,7 @@ constexpr int kReplicaLevelsNgp = 2;
 inline int replica_instance_levels(const FieldDev& fd, const ReplicaDev& R) {
   return R.table && fd.n_features == 4 && render_instance_dense_levels(fd) == 5 ? R.n_levels : 0;
 }
-// one replica of a level of `res` vertices per axis: rows of res + 1 entries rounded up to 8, as many rows per plane, res + 1
-// planes; levels start at multiples of 4 KiB.  0 bytes: the level cannot be replicated (its z stride must stay below 2^24 for
-// the gather's 24-bit multiplies, its row count / 8 inside the 12 low bits of the pack word)
-struct ReplicaLevelLayout {
-  uint32_t row;   // entries per row = rows per plane
-  uint64_t bytes; // row * row * (res + 1) * ebytes, rounded up to 4 KiB
-};
-inline ReplicaLevelLayout replica_level_layout(uint32_t res, uint32_t ebytes) {
-  const uint32_t row = (res + 1u + 7u) & ~7u;
-  const uint64_t mz = (uint64_t)row * row * ebytes;
-  if (mz >= (1ull << 24) || row / 8u > 4095u) return {row, 0};
-  return {row, (mz * (res + 1u) + 4095ull) & ~4095ull};
-}
+// (replica_level_layout, one replica's strides and size: prv_field_plan.hpp)
 hipError_t launch_fill_replica(const FieldDev& fd, const ReplicaDev& R, int k, hipStream_t s); // replica k from fd.table (the physical table)
 struct PreceptPose {
   double w2c[16], c2w[16];

@@ -1359,7 +1359,7 @@ __global__ __launch_bounds__(256) void train_reduce_dw2_kernel(const float* __re
 
 __device__ __forceinline__ void end_step(const AdamParams& P, uint32_t* sample_count, float lr, float beta1, float beta2);
 
-// the 24 MFMA A-fragments of the current fp16 weights (the layout prv_api.cpp: prepack_fragments gives the
+// the 24 MFMA A-fragments of the current fp16 weights (the layout prv_field_plan.hpp: prepack_fragments gives the
 // render kernel), rebuilt on the device after every optimiser step: one thread per fragment element
 __device__ __forceinline__ int frag_hidden_k(int s, int h, int j) { return 32 * (s >> 1) + 16 * (s & 1) + 8 * (j >> 2) + 4 * h + (j & 3); }
 

@@ -3,9 +3,10 @@ field-evaluating kernels and one per reason for falling back to the generic inst
 produce (prv_model_layout: kernel_dense_levels, n_dense_levels, n_hashed_levels).
 
 The expectations are written down, not computed: `restated_layout` below restates compute_levels (prv_levels.hpp) and the
-physical-layout rules of install_model (prv_api.cpp) in Python so that the table can be checked without a GPU
-(tests/test_instances_host.py); on the GPU every test asserts the context's own answer against the table first, so a shape
-that does not select its instance fails loudly instead of running on <F, 0> unnoticed.
+physical-layout rules of plan_field (prv_field_plan.hpp) in Python so that the table can be checked without a GPU
+(tests/test_instances_host.py), and the C++ rules against the restatement (tests/test_field_plan_host.py); on the GPU every test
+asserts the context's own answer against the table first, so a shape that does not select its instance fails loudly instead
+of running on <F, 0> unnoticed.
 
     id                    dense / hashed   instance   why
     F4_5, F4_3            5 / 3, 3 / 5     5, 3       SMALL with a larger / smaller table
@@ -56,7 +57,7 @@ ALL_INSTANCES = {(4, 5), (4, 3), (4, 0), (2, 10), (2, 6), (2, 0)}
 
 
 def is_wide(kw):
-    """prv_api.cpp's rule: a hashed level whose last byte offset does not fit 24 bits takes the 32-bit multiply path"""
+    """plan_field's rule (prv_field_plan.hpp): a hashed level whose last byte offset does not fit 24 bits takes the 32-bit multiply path"""
     return restated_layout(kw)["n_hashed_levels"] >= 1 and ((1 << kw["log2_hashmap"]) - 1) * 2 * kw["n_features"] >= 1 << 24
 
 
@@ -71,6 +72,7 @@ def assert_layout(layout, entry, no_pair=False):
         assert layout["kernel_dense_levels"] == entry.instance, layout
         assert layout["n_dense_levels"] == entry.n_dense, layout
     assert is_wide(entry.kw) == entry.wide
+    assert layout["table_bytes_physical"] == restated_layout(entry.kw)["table_bytes_physical"]  # (the same with and without PRV_NO_PAIR)
 
 
 def restated_levels(kw):
@@ -94,7 +96,7 @@ def restated_levels(kw):
 
 
 def restated_layout(kw):
-    """the instance install_model + render_instance_dense_levels pick for a descriptor, restated: power-of-two strides and
+    """the instance plan_field + instance_dense_levels (prv_field_plan.hpp) pick for a descriptor, restated: power-of-two strides and
     sizes for the dense levels, levels placed largest first, the shared-hash conditions, the instance table"""
     lv = restated_levels(kw)
     F = kw["n_features"]

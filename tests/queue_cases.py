@@ -12,7 +12,7 @@ Restated here, in Python:
   * the region rule of march_emit (prv_kernels.hip): the wave's first live lane picks the region; the octant is that of the
     ray's position at the middle of its live span, (first + last live step) >> 1, t = fmaf(i + 0.5, dt, t0) and
     fmaf(t, d, o) > 0.5f * (occ_lo + occ_hi) in float32, occ_lo / occ_hi the one-cell-grown box of the occupied cells
-    (install_model); the sub-region is `linear block id % n_sub`; the region is (octant * n_sub + sub) % n_seg.
+    (summarize_occupancy); the sub-region is `linear block id % n_sub`; the region is (octant * n_sub + sub) % n_seg.
 The masks are the oracle's: rays and box intersection through its exported primitives (oracle.raygen), the steps
 t_i = fmaf(i + 0.5, dt, t0), p = fmaf(t, d, o) and orc_occupied's cell rule vectorised with tests/march_ref.py's fmaf (float64
 product and sum, rounded once to float32); `population` asserts their sum against OracleField.march_count.
@@ -141,7 +141,7 @@ class Case:
         return api.render_opts(self.w, self.h, S_FIXED if mode == FIXED else 0, self.spp, self.min_T if min_T is None else min_T, step_mode=mode, **kw)
 
     def occ_box(self):
-        """install_model's occ_lo / occ_hi (float32)"""
+        """summarize_occupancy's occ_lo / occ_hi (prv_field_plan.hpp; float32)"""
         z, y, x = np.nonzero(self.occ)
         if x.size == 0:
             return np.full(3, 2.0, f32), np.full(3, -1.0, f32)

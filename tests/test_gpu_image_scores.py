@@ -295,7 +295,7 @@ def test_ensemble_chunk_boundaries(ctx, oracle, method, E):
 # ------------------------------------------------------------------ the cull rectangle of the fused PSNR round
 
 def occupied_box(occ, R):
-    """the box the library culls against: the occupied cells' bounding box, one cell of margin (prv_api.cpp, model install)"""
+    """the box the library culls against: the occupied cells' bounding box, one cell of margin (prv_field_plan.hpp: summarize_occupancy)"""
     bits = np.unpackbits(occ.view(np.uint8), bitorder="little")[: R ** 3].reshape(R, R, R)  # z, y, x
     lo, hi = np.zeros(3), np.zeros(3)
     for a, axis in enumerate((2, 1, 0)):

@@ -125,6 +125,32 @@ def test_layout_of_an_imported_snapshot_shape(ctx):
     ctx.synthetic_model(SLOT + 7, api.field_desc(**util.SMALL), util.SEED_A)
 
 
+def test_a_rejected_install_empties_its_slot_and_no_other(ctx, cams):
+    """a descriptor the plan rejects (tests/test_field_plan_host.py: PAST_LIMIT, a level of 4097 vertices per axis), loaded over a
+    valid model: the call fails with the plan's text, the slot is empty afterwards, and the context's other slots render what they
+    rendered before"""
+    from tests.test_field_plan_host import PAST_LIMIT
+
+    victim, bystander = SLOT + 3, SLOT + 6
+    small = api.field_desc(**util.SMALL)
+    ctx.synthetic_model(victim, small, util.SEED_A)
+    ctx.synthetic_model(bystander, small, util.SEED_B)
+    opts = _opts(W, H, 128, 1, 0)
+    before = ctx.render(bystander, cams[0], None, opts)[0].cpu().numpy().copy()
+    assert (ctx.render(victim, cams[0], None, opts)[0].cpu().numpy()[..., 3] > 0).any()
+    bad = api.field_desc(**PAST_LIMIT)
+    t, m, o = api.model_sizes(bad)
+    with pytest.raises(api.PrvError, match=r"level 1 has 4097 vertices per axis \(limit 4096\)") as e:
+        ctx.load_model(victim, bad, np.zeros(t, np.uint16), np.zeros(m, np.uint16), np.zeros(o, np.uint32))
+    assert e.value.code == api.L.PRV_E_INVALID
+    with pytest.raises(api.PrvError, match=f"model slot {victim} is empty") as e:
+        ctx.render(victim, cams[0], None, opts)
+    assert e.value.code == api.L.PRV_E_STATE
+    assert np.array_equal(ctx.render(bystander, cams[0], None, opts)[0].cpu().numpy(), before)
+    ctx.synthetic_model(victim, small, util.SEED_A)  # the slot takes a model again
+    instances.assert_layout(ctx.model_layout(victim), instances.MATRIX["F4_0"])
+
+
 # ---- features, field
 def test_features_bit_exact(ctx, inst):
     instances.assert_layout(ctx.model_layout(SLOT), inst.entry)

@@ -1,5 +1,5 @@
-"""Dense replicas of the hashed levels of an F = 4 field that runs the <4, 5> instance (prv_device.hpp: ReplicaDev; prv_api.cpp:
-build_replicas): a replica holds exactly the entries the hashed gather fetches, so everything a model computes with replicas
+"""Dense replicas of the hashed levels of an F = 4 field that runs the <4, 5> instance (prv_device.hpp: ReplicaDev; prv_field_plan.hpp:
+plan_replicas): a replica holds exactly the entries the hashed gather fetches, so everything a model computes with replicas
 equals, BYTE FOR BYTE, what it computes without -- features, field outputs, pixels (float and RGBA8), evaluated-sample counts.
 No comparison in this file has a tolerance.
 
@@ -19,7 +19,7 @@ gpu = pytest.mark.gpu
 # the replica counts a model can hold = the variants the library ships (render_queue64_replica_kernel<NGP, NREPL>; under the
 # engine's rule the launch reads at most two of the levels a model holds: kReplicaLevelsNgp, prv_kernels.hpp)
 VARIANTS = (1, 2, 3)
-DEFAULT_LEVELS = 3    # what a model gets with nothing set, budget permitting (prv_api.cpp: kReplicaBudgetDefault = 256 MiB)
+DEFAULT_LEVELS = 3    # what a model gets with nothing set, budget permitting (prv_field_plan.hpp: kReplicaBudgetDefault = 256 MiB)
 F4_5 = instances.MATRIX["F4_5"]
 BASELINE_256 = dict(api.FIELD_256, table_amp=0.1, density_bias=0.0)  # bench.py's field_kw("256", "baseline")
 W, H = 48, 32

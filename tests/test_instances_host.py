@@ -1,6 +1,7 @@
 """The field matrix of tests/instances.py without a GPU: the layout each entry is expected to produce equals what a Python
-restatement of compute_levels (prv_levels.hpp) and of install_model's physical-layout rules (prv_api.cpp) gives, and the
-restated level geometry is the oracle's.  (On the GPU, tests/test_gpu_instances.py asserts the context's own answer.)"""
+restatement of compute_levels (prv_levels.hpp) and of plan_field's physical-layout rules (prv_field_plan.hpp) gives, and the
+restated level geometry is the oracle's.  (tests/test_field_plan_host.py holds the C++ rules against the restatement; on the GPU,
+tests/test_gpu_instances.py asserts the context's own answer.)"""
 import numpy as np
 import pytest
 
