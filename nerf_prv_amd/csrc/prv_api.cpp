@@ -107,6 +107,9 @@ struct prv_ctx {
   float mesh_ms[4] = {0, 0, 0, 0};           // stages of the last mesh extraction (prv_mesh_api.inc: prv_debug_mesh_stages)
   int queue_segments = 8; // ray-queue segments = XCDs (PRV_QUEUE_SEGMENTS: 1 = single shared head)
   int spatial_regions = 1; // a wave's records go to the region of its first live ray's octant (PRV_SPATIAL_REGIONS=0: block id % regions, rounds 1-5)
+  int region_cells = 4;   // PRV_REGION_CELLS = 1, 2, 4, 8: the render drains an octant region in cells^3 spatial cells, in Morton order (1: in
+                          // the order of arrival, no descriptors and no ordering launch; needs spatial_regions).  Pixels do not depend on it
+  Buffer desc, desc_sorted; // ... the march waves' block descriptors and their sorted lists, 8 bytes per queue slot each (prv_queue_order.hpp)
   int pool_on = -1;       // render_queue64 block-level tail pool (PRV_POOL=0/1; -1 = by table and image size, see render_policy)
   int merge_max = -1;     // render_queue64 tail merge threshold (PRV_MERGE_MAX; 0 = off; -1 = by table size, see render_policy)
   size_t stage_budget = (size_t)4 << 30; // staging bytes for multi-sample renders (spp x batch x image)
@@ -529,10 +532,12 @@ constexpr size_t kCountersBytes = kStatOffset + 72 * 8; // {evaluated, wave roun
 // the image, i.e. in ONE octant, and one returning-atomic word serves ~90 of them per microsecond.
 struct MarchLayout {
   int spp, n_sub, n_seg;
+  int n_cells; // cells per axis an octant region is drained in (prv_ctx::region_cells; 1 without spatial regions)
   int spp_inner_log2 = 0, tile_w_log2, tile_h_log2;
   uint32_t tiles_x, tiles_y;
   MarchLayout(const prv_ctx* c, int W, int H, int spp_) : spp(spp_) {
     n_sub = c->spatial_regions ? kSubRegions : 1;
+    n_cells = c->spatial_regions ? c->region_cells : 1;
     n_seg = c->queue_segments * n_sub;
     if (spp > 1 && spp <= 64 && (spp & (spp - 1)) == 0)
       while ((1 << spp_inner_log2) < spp) spp_inner_log2++;
@@ -545,6 +550,10 @@ struct MarchLayout {
   size_t blocks(size_t n_views) const { return (size_t)tiles_x * tiles_y * n_views * (size_t)(spp_inner_log2 > 0 ? 1 : spp); }
   size_t seg_cap(size_t n_views) const { return ((blocks(n_views) + n_seg - 1) / n_seg) * 256 + 64; }
 };
+
+// bytes per queue slot beyond the record (and its extension): with region cells, a descriptor and its sorted copy.  One per SLOT,
+// not per 64 slots: a march wave's block may hold a single record (one live ray per wave), and then every record has a descriptor
+size_t desc_slot_bytes(const prv_ctx* c) { return c->spatial_regions && c->region_cells > 1 ? 2 * sizeof(QueueDesc) : 0; }
 
 // the fields MarchParams and MarchMultiParams share (same names), for views [v0, v0 + n_views) of the upload
 template <class PT>
@@ -563,6 +572,7 @@ void march_common(PT& mp, const prv_ctx* c, const MarchLayout& L, const prv_rend
   mp.stat = stat;
   mp.n_seg = L.n_seg;
   mp.n_sub = L.n_sub;
+  mp.n_cells = L.n_cells;
   mp.seg_cap = (uint32_t)L.seg_cap(n_views);
   mp.spatial_regions = c->spatial_regions;
   mp.last_pass = o->spp == 1; // staged sub-samples are written raw; scaling / bytes happen in the reduce
@@ -625,9 +635,28 @@ void render_policy(prv_ctx* c, const Model& m, size_t npix, bool ngp, RenderPara
   rp.pool_on = (c->pool_on >= 0 ? c->pool_on != 0 : (coherent || cached)) && rp.merge_max > 0;
 }
 
+// n_cells > 1, between a queue's march and its render: the ordering launch (descriptors `desc` of the queue with counters
+// queue_count -> sorted lists, their lengths behind the heads)
+int order_queue(prv_ctx* c, const MarchLayout& L, uint32_t seg_cap, const QueueDesc* desc, QueueDesc* sorted, const uint32_t* queue_count,
+                uint32_t* queue_head) {
+  OrderParams op;
+  memset(&op, 0, sizeof(op));
+  op.desc = desc;
+  op.sorted = sorted;
+  op.queue_count = queue_count;
+  op.queue_head = queue_head;
+  op.n_seg = L.n_seg;
+  op.n_sub = L.n_sub;
+  op.seg_cap = seg_cap;
+  op.n_keys = L.n_cells * L.n_cells * L.n_cells;
+  HIPCHK(c, launch_order_descriptors(op, c->stream));
+  return PRV_OK;
+}
+
 // the render launch over one queue the march filled (q: its records, counts and images; queue_head: its heads), in mode kRender*
+// (sorted: the queue's sorted descriptor lists, L.n_cells > 1)
 RenderParams render_params(prv_ctx* c, const Model& m, const prv_render_opts* o, const MarchLayout& L, uint32_t seg_cap,
-                           const MarchMember& q, uint32_t* queue_head, unsigned long long* stat, int mode) {
+                           const MarchMember& q, uint32_t* queue_head, unsigned long long* stat, int mode, const QueueDesc* sorted = nullptr) {
   RenderParams rp;
   memset(&rp, 0, sizeof(rp));
   rp.field = m.dev;
@@ -638,6 +667,8 @@ RenderParams render_params(prv_ctx* c, const Model& m, const prv_render_opts* o,
   rp.queue_head = queue_head;
   rp.n_segments = L.n_seg;
   rp.n_sub = L.n_sub;
+  rp.n_cells = sorted ? L.n_cells : 1;
+  rp.desc_sorted = sorted;
   rp.seg_cap = seg_cap;
   rp.stat_evaluated = stat;
   rp.out_f32 = q.out_f32;
@@ -697,7 +728,7 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
   // view v is image (k*nb + v) of a staging buffer, reduced over k in order afterwards (spp = 1 renders
   // straight into the output).  Batches keep queue and staging within their budgets.
   const bool ngp = o->step_mode == PRV_STEP_NGP;
-  const size_t slot_bytes = kRecordBytes + (ngp ? kExtBytes : 0); // NGP: every queue slot has its mask-extension slot
+  const size_t slot_bytes = kRecordBytes + (ngp ? kExtBytes : 0) + desc_slot_bytes(c); // NGP: every queue slot has its mask-extension slot
   size_t batch = std::max<size_t>(1, c->queue_budget / (npix * slot_bytes * (size_t)spp));
   batch = std::min<size_t>(batch, (size_t)n_views);
   // the launch's scalar planes, in the order they are reduced: where the plane goes, where its sub-samples are staged, and the
@@ -725,6 +756,8 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
   if (seg_cap_max * (size_t)L.n_seg >= (1ull << 32)) return fail(c, PRV_E_INVALID, "image x spp too large");
   if ((rc = ensure(c, c->queue, seg_cap_max * (size_t)L.n_seg * kRecordBytes)) != PRV_OK) return rc;
   if (ngp && (rc = ensure(c, c->queue_ext, seg_cap_max * (size_t)L.n_seg * kExtBytes)) != PRV_OK) return rc;
+  const size_t desc_bytes = L.n_cells > 1 ? seg_cap_max * (size_t)L.n_seg * sizeof(QueueDesc) : 0;
+  if (desc_bytes && ((rc = ensure(c, c->desc, desc_bytes)) != PRV_OK || (rc = ensure(c, c->desc_sorted, desc_bytes)) != PRV_OK)) return rc;
   if (spp > 1 && colour && (rc = ensure(c, c->stage, batch * npix * (size_t)spp * 16)) != PRV_OK) return rc;
   for (int i = 0; i < n_planes && spp > 1; i++)
     if ((rc = ensure(c, *planes[i].stage, batch * npix * (size_t)spp * 4)) != PRV_OK) return rc;
@@ -759,6 +792,7 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
     mp.queue = c->queue.p;
     mp.queue_ext = (uint4*)c->queue_ext.p;
     mp.queue_count = q_count;
+    mp.desc = desc_bytes ? (QueueDesc*)c->desc.p : nullptr;
     mp.out_f32 = !colour ? nullptr : spp > 1 ? (float*)c->stage.p : dst_f32;
     mp.out_u8 = spp > 1 ? nullptr : dst_u8;
     // A caller that consumes the image through the views' cull rectangles (prv_score_views, method 5: the image is a private
@@ -782,10 +816,16 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
       mp.live_grid = 1;
       mp.live_tiles_max = (uint32_t)live_max;
     }
-    if ((rc = timed(c, c->ev_march, [&] { HIPCHK(c, launch_march(mp, nb, spp, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
+    // (the ordering launch is timed with the march: "march" in a profiling window is everything between the views and a drainable queue)
+    if ((rc = timed(c, c->ev_march, [&] {
+           HIPCHK(c, launch_march(mp, nb, spp, c->stream));
+           return desc_bytes ? order_queue(c, L, mp.seg_cap, mp.desc, (QueueDesc*)c->desc_sorted.p, q_count, q_head) : PRV_OK;
+         })) != PRV_OK)
+      return rc;
     RenderPlanesParams pp;
     memset(&pp, 0, sizeof(pp));
-    pp.r = render_params(c, m, o, L, mp.seg_cap, {mp.queue, mp.queue_ext, mp.queue_count, mp.out_f32, mp.out_u8}, q_head, stat, t.mode);
+    pp.r = render_params(c, m, o, L, mp.seg_cap, {mp.queue, mp.queue_ext, mp.queue_count, mp.desc, mp.out_f32, mp.out_u8}, q_head, stat, t.mode,
+                         desc_bytes ? (const QueueDesc*)c->desc_sorted.p : nullptr);
     for (int i = 0; i < n_planes; i++) pp.*planes[i].slot = target[i];
     pp.cams = mp.cams;
     pp.view_ids = mp.view_ids;
@@ -833,7 +873,7 @@ int render_ensemble_ngp(prv_ctx* c, const int* slots, int E, const prv_camset* c
   }
   const int W = o->width, H = o->height, spp = o->spp;
   const size_t npix = (size_t)W * H;
-  const size_t slot_bytes = kRecordBytes + kExtBytes;
+  const size_t slot_bytes = kRecordBytes + kExtBytes + desc_slot_bytes(c);
   // all views in ONE batch, every member with a queue and a staging image of its own: refuse (-> member by member, batched)
   // when that does not fit the budgets
   if ((size_t)n_views * npix * (size_t)spp >= (1ull << 32)) return PRV_OK;
@@ -849,12 +889,15 @@ int render_ensemble_ngp(prv_ctx* c, const int* slots, int E, const prv_camset* c
   const size_t R = (size_t)m0.desc.occ_res, n_fine = R * R * R, Rc = R / 4, n_coarse = Rc * Rc * Rc;
   if ((rc = ensure(c, c->occ_multi, n_fine + n_coarse + 64)) != PRV_OK) return rc;
   const size_t q_stride = seg_cap * (size_t)L.n_seg * kRecordBytes, x_stride = seg_cap * (size_t)L.n_seg * kExtBytes,
-               s_stride = spp > 1 ? (size_t)n_views * npix * (size_t)spp * 16 : 0;
+               s_stride = spp > 1 ? (size_t)n_views * npix * (size_t)spp * 16 : 0,
+               d_stride = L.n_cells > 1 ? seg_cap * (size_t)L.n_seg * sizeof(QueueDesc) : 0; // descriptors and their sorted lists, per member as the queues
   { // E queues, E extension buffers, E staging images at once: only where the device has the room (else member by member,
     // whose buffers are a fifth of these)
     const size_t grow = (q_stride * (size_t)E > c->queue.bytes ? q_stride * (size_t)E - c->queue.bytes : 0) +
                         (x_stride * (size_t)E > c->queue_ext.bytes ? x_stride * (size_t)E - c->queue_ext.bytes : 0) +
-                        (s_stride * (size_t)E > c->stage.bytes ? s_stride * (size_t)E - c->stage.bytes : 0);
+                        (s_stride * (size_t)E > c->stage.bytes ? s_stride * (size_t)E - c->stage.bytes : 0) +
+                        (d_stride * (size_t)E > c->desc.bytes ? d_stride * (size_t)E - c->desc.bytes : 0) +
+                        (d_stride * (size_t)E > c->desc_sorted.bytes ? d_stride * (size_t)E - c->desc_sorted.bytes : 0);
     size_t free_b = 0, total_b = 0;
     // (the context's parked trainer buffers count as free: ensure() releases them before an allocation fails)
     if (grow && (hipMemGetInfo(&free_b, &total_b) != hipSuccess || grow + ((size_t)2 << 30) > free_b + c->parked.bytes)) return PRV_OK;
@@ -885,6 +928,7 @@ int render_ensemble_ngp(prv_ctx* c, const int* slots, int E, const prv_camset* c
   if ((rc = ensure(c, c->queue, q_stride * (size_t)E)) != PRV_OK) return rc;
   if ((rc = ensure(c, c->queue_ext, x_stride * (size_t)E)) != PRV_OK) return rc;
   if (spp > 1 && (rc = ensure(c, c->stage, s_stride * (size_t)E)) != PRV_OK) return rc;
+  if (d_stride && ((rc = ensure(c, c->desc, d_stride * (size_t)E)) != PRV_OK || (rc = ensure(c, c->desc_sorted, d_stride * (size_t)E)) != PRV_OK)) return rc;
   HIPCHK(c, hipMemsetAsync(c->counters.p, 0, kCountersBytes, c->stream)); // a new statistics window (this call renders every member)
   HIPCHK(c, hipMemsetAsync(c->counters_multi.p, 0, (size_t)E * kStatOffset, c->stream));
 
@@ -903,17 +947,28 @@ int render_ensemble_ngp(prv_ctx* c, const int* slots, int E, const prv_camset* c
     mm.queue = (char*)c->queue.p + q_stride * (size_t)e;
     mm.queue_ext = (uint4*)((char*)c->queue_ext.p + x_stride * (size_t)e);
     mm.queue_count = (uint32_t*)((char*)c->counters_multi.p + (size_t)e * kStatOffset) + kMaxSegments * 16;
+    mm.desc = d_stride ? (QueueDesc*)((char*)c->desc.p + d_stride * (size_t)e) : nullptr;
     // spp > 1: the member's own staging image; spp == 1: the caller's scratch image is shared (nobody reads it), the bytes are the member's
     mm.out_f32 = spp > 1 ? (float*)((char*)c->stage.p + s_stride * (size_t)e) : scratch_f32;
     mm.out_u8 = spp > 1 ? nullptr : (uint32_t*)out_u8[e];
   }
-  if ((rc = timed(c, c->ev_march, [&] { HIPCHK(c, launch_march_multi(mp, n_views, spp, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
+  if ((rc = timed(c, c->ev_march, [&] { // (with the members' ordering launches, as in render_views)
+         HIPCHK(c, launch_march_multi(mp, n_views, spp, c->stream));
+         for (int e = 0; e < E && d_stride; e++) {
+           const int orc = order_queue(c, L, mp.seg_cap, mp.mem[e].desc, (QueueDesc*)((char*)c->desc_sorted.p + d_stride * (size_t)e), mp.mem[e].queue_count,
+                                       (uint32_t*)((char*)c->counters_multi.p + (size_t)e * kStatOffset));
+           if (orc != PRV_OK) return orc;
+         }
+         return PRV_OK;
+       })) != PRV_OK)
+    return rc;
 
   for (int e = 0; e < E; e++) {
     const Model& m = c->models[slots[e]];
     const int n_blocks = render_blocks(c, m, npix);
     uint32_t* q_head = (uint32_t*)((char*)c->counters_multi.p + (size_t)e * kStatOffset);
-    const RenderParams rp = render_params(c, m, o, L, mp.seg_cap, mp.mem[e], q_head, stat, kRenderColour);
+    const QueueDesc* sorted = d_stride ? (const QueueDesc*)((char*)c->desc_sorted.p + d_stride * (size_t)e) : nullptr;
+    const RenderParams rp = render_params(c, m, o, L, mp.seg_cap, mp.mem[e], q_head, stat, kRenderColour, sorted);
     if ((rc = timed(c, c->ev_render, [&] { HIPCHK(c, launch_render(rp, m.rdev, n_blocks, c->stream)); return PRV_OK; })) != PRV_OK) return rc;
     if (spp > 1)
       HIPCHK(c, launch_spp_reduce((const float*)mp.mem[e].out_f32, (size_t)n_views * npix, spp, o->background, scratch_f32, (uint32_t*)out_u8[e], c->stream));
@@ -1004,6 +1059,7 @@ int prv_create(prv_ctx** out, int device_id) try {
   if (const char* s = getenv("PRV_BLOCKS_PER_CU")) c->blocks_per_cu = std::max(1, atoi(s));
   if (const char* s = getenv("PRV_QUEUE_SEGMENTS")) c->queue_segments = std::min(8, std::max(1, atoi(s)));
   if (const char* s = getenv("PRV_SPATIAL_REGIONS")) c->spatial_regions = std::max(0, std::min(2, atoi(s)));
+  if (const char* s = getenv("PRV_REGION_CELLS")) c->region_cells = region_cells_clamp(atoi(s));
   if (const char* s = getenv("PRV_MERGE_MAX")) c->merge_max = std::min(31, std::max(0, atoi(s)));
   if (const char* s = getenv("PRV_POOL")) c->pool_on = atoi(s) != 0 ? 1 : 0;
   if (const char* s = getenv("PRV_CELL_CACHE")) c->cell_cache = atoi(s) != 0 ? 1 : 0;

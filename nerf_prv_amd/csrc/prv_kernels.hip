@@ -183,6 +183,7 @@ struct MarchSink {
   uint32_t* queue_count;
   float* out_f32;
   uint32_t* out_u8;
+  QueueDesc* desc; // n_cells > 1: the descriptors of the waves' blocks, seg_cap per region (prv_queue_order.hpp)
 };
 
 // Wave-level compaction of the live rays into the queue + the record + the statistics + the dead ray's pixel.
@@ -257,16 +258,32 @@ __device__ __forceinline__ uint32_t ray_octant(const float o[3], const float d[3
 // called by ONE lane: n records in region `pref` or the first region after it with room; returns the first record's queue slot.
 // ONE returning add in the common case (a compare-and-swap loop here made the march pass five times as long: the waves running
 // at any one time are neighbours, i.e. all on the same few counters).  The one reservation that straddles a region's end keeps
-// its slots empty and says so in the word behind the counter (tail cut: the render kernel drains count - cut records); every
+// its slots empty and says so in word 2 of the counter's line (tail cut: the render kernel drains count - cut records); every
 // later add on that counter lands beyond the end and moves on as well.
-__device__ __forceinline__ uint32_t region_reserve(uint32_t* queue_count, uint32_t n_seg, uint32_t seg_cap, uint32_t pref, uint32_t n) {
+// desc_at != nullptr (PRV_REGION_CELLS > 1): the SAME add, 64 bits wide, also hands out the index of the block's descriptor in its
+// region (the counter's high word; *desc_at = where the descriptor goes).  Every reservation that succeeds comes before every one
+// that fails in the counter's order (a failed add leaves the count beyond seg_cap), so the descriptors of a region are dense; the
+// first reservation that fails leaves its index + 1 behind the cut (prv_queue_order.hpp: desc_valid_count).
+__device__ __forceinline__ uint32_t region_reserve(uint32_t* queue_count, uint32_t n_seg, uint32_t seg_cap, uint32_t pref, uint32_t n,
+                                                   uint32_t* desc_at = nullptr) {
   for (uint32_t k = 0; k < n_seg; k++) {
     const uint32_t shard = (pref + k) % n_seg;
     uint32_t* c = queue_count + 16u * shard;
     if (k != 0u && __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= seg_cap) continue; // (a full region: no add at all)
-    const uint32_t old = atomicAdd(c, n);
-    if (old + n <= seg_cap) return shard * seg_cap + old;
-    if (old < seg_cap) c[1] = seg_cap - old; // this reservation straddles the end: [old, seg_cap) stays unwritten
+    uint32_t old, idx = 0u;
+    if (desc_at) {
+      const unsigned long long o64 = atomicAdd(reinterpret_cast<unsigned long long*>(c), (1ull << 32) | (unsigned long long)n);
+      old = (uint32_t)o64;
+      idx = (uint32_t)(o64 >> 32);
+    } else {
+      old = atomicAdd(c, n);
+    }
+    if (old + n <= seg_cap) {
+      if (desc_at) *desc_at = shard * seg_cap + idx;
+      return shard * seg_cap + old;
+    }
+    if (old < seg_cap) c[2] = seg_cap - old; // this reservation straddles the end: [old, seg_cap) stays unwritten
+    if (desc_at && old <= seg_cap) c[3] = idx + 1u;
   }
   // unreachable: a reservation fails only in a CLOSED region (count >= seg_cap, which stays so), and a closed region holds at least
   // seg_cap - 63 records (the one straddling reservation, of <= 64, leaves at most 63 slots empty).  Had this wave found all n_seg
@@ -314,9 +331,17 @@ __device__ __forceinline__ void march_emit(const PT& P, const MarchSink& Q, uint
         }
       }
       const uint32_t lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-      const uint32_t pref = P.spatial_regions ? ray_octant(r.o, r.d, fmaf((float)i0 + 0.5f, dt, r.t0), P.field.occ_lo, P.field.occ_hi) * (uint32_t)P.n_sub + lin % (uint32_t)P.n_sub
+      const float tm = fmaf((float)i0 + 0.5f, dt, r.t0);
+      const uint32_t pref = P.spatial_regions ? ray_octant(r.o, r.d, tm, P.field.occ_lo, P.field.occ_hi) * (uint32_t)P.n_sub + lin % (uint32_t)P.n_sub
                                               : lin;
-      base = region_reserve(Q.queue_count, (uint32_t)P.n_seg, P.seg_cap, pref % (uint32_t)P.n_seg, (uint32_t)__popcll(b));
+      if (P.n_cells > 1) { // the block's descriptor: where it is, how many, and the cell of its octant the same point falls in
+        const float pm[3] = {fmaf(tm, r.d[0], r.o[0]), fmaf(tm, r.d[1], r.o[1]), fmaf(tm, r.d[2], r.o[2])};
+        uint32_t at = ~0u; // (stays so on region_reserve's unreachable path: then no descriptor is written over another's)
+        base = region_reserve(Q.queue_count, (uint32_t)P.n_seg, P.seg_cap, pref % (uint32_t)P.n_seg, (uint32_t)__popcll(b), &at);
+        if (at != ~0u) Q.desc[at] = make_desc(base, (uint32_t)__popcll(b), region_cell_key(pm, P.field.occ_lo, P.field.occ_hi, P.n_cells));
+      } else {
+        base = region_reserve(Q.queue_count, (uint32_t)P.n_seg, P.seg_cap, pref % (uint32_t)P.n_seg, (uint32_t)__popcll(b));
+      }
     }
     base = __shfl(base, (int)__builtin_ctzll(b));
   }
@@ -452,7 +477,7 @@ __device__ __forceinline__ void march_compact_body(MarchParams P) {
     }
 #endif
   }
-  const MarchSink Q{P.queue, P.queue_ext, (size_t)P.seg_cap * (size_t)P.n_seg, P.queue_count, P.out_f32, P.out_u8};
+  const MarchSink Q{P.queue, P.queue_ext, (size_t)P.seg_cap * (size_t)P.n_seg, P.queue_count, P.out_f32, P.out_u8, P.desc};
   march_emit<NGP, IMAGE>(P, Q, stage, r, live, n_live, dt, m, first_nz, last_nz,
                          [&](int k) { return (k >= k_lo && k < k_hi) ? mw[k][threadIdx.x] : 0u; });
 }
@@ -597,24 +622,42 @@ __global__ __launch_bounds__(256) void march_multi_kernel(MarchMultiParams P) {
     }
     const unsigned long long b_any = __ballot(first_any < 32);
     uint32_t pref = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+    uint32_t key = 0u;
     if (P.spatial_regions && b_any != 0ull) {
-      const uint32_t oct = ray_octant(o, d, fmaf((float)(16 * (min(first_any, 31) + last_any)) + 16.0f, dt, t0), P.occ_lo, P.occ_hi);
-      pref = (uint32_t)__shfl((int)oct, (int)__builtin_ctzll(b_any)) * (uint32_t)P.n_sub + pref % (uint32_t)P.n_sub;
+      const float tm = fmaf((float)(16 * (min(first_any, 31) + last_any)) + 16.0f, dt, t0);
+      uint32_t oct = ray_octant(o, d, tm, P.occ_lo, P.occ_hi);
+      if (P.n_cells > 1) { // the cell of that point inside its octant, for the members' descriptors (every member the same key)
+        const float pm[3] = {fmaf(tm, d[0], o[0]), fmaf(tm, d[1], o[1]), fmaf(tm, d[2], o[2])};
+        oct |= region_cell_key(pm, P.occ_lo, P.occ_hi, P.n_cells) << 3;
+      }
+      oct = (uint32_t)__shfl((int)oct, (int)__builtin_ctzll(b_any));
+      key = oct >> 3;
+      pref = (oct & 7u) * (uint32_t)P.n_sub + pref % (uint32_t)P.n_sub;
     }
     const uint32_t shard = pref % (uint32_t)P.n_seg;
     uint32_t* qc = nullptr;
+    QueueDesc* qd = nullptr;
     uint32_t mine = 0u, tot = 0u;
 #pragma unroll
     for (int e = 0; e < E; e++) {
       b[e] = __ballot(first_nz[e] < 32);
       if (lane == e) {
         qc = P.mem[e].queue_count;
+        qd = P.mem[e].desc;
         mine = (uint32_t)__popcll(b[e]);
       }
       tot += n_live[e];
     }
     uint32_t got = 0u;
-    if (mine) got = region_reserve(qc, (uint32_t)P.n_seg, P.seg_cap, shard, mine);
+    if (mine) {
+      if (P.n_cells > 1) {
+        uint32_t at = ~0u;
+        got = region_reserve(qc, (uint32_t)P.n_seg, P.seg_cap, shard, mine, &at);
+        if (at != ~0u) qd[at] = make_desc(got, mine, key);
+      } else {
+        got = region_reserve(qc, (uint32_t)P.n_seg, P.seg_cap, shard, mine);
+      }
+    }
 #pragma unroll
     for (int e = 0; e < E; e++) base[e] = __shfl(got, e);
     march_count(P, tot);
@@ -682,7 +725,7 @@ __global__ __launch_bounds__(256) void march_multi_kernel(MarchMultiParams P) {
   }
 #pragma unroll
   for (int e = 0; e < E; e++) {
-    const MarchSink Q{P.mem[e].queue, P.mem[e].queue_ext, ext_stride, P.mem[e].queue_count, P.mem[e].out_f32, P.mem[e].out_u8};
+    const MarchSink Q{P.mem[e].queue, P.mem[e].queue_ext, ext_stride, P.mem[e].queue_count, P.mem[e].out_f32, P.mem[e].out_u8, P.mem[e].desc};
     march_write<true, true>(P, Q, stage, r, first_nz[e] < 32, b[e], base[e], dt, m[e], first_nz[e], last_nz[e], [](int) { return 0u; });
   }
 }
@@ -694,6 +737,97 @@ __global__ __launch_bounds__(256) void occ_interleave_kernel(OccInterleaveParams
   uint32_t v = 0u;
   for (int e = 0; e < P.n_members; e++) v |= ((P.bits[e][c >> 5] >> (c & 31u)) & 1u) << e;
   P.out[c] = (uint8_t)v;
+}
+
+// ------------------------------------------------------------------ the order the render drains a region in (prv_queue_order.hpp)
+
+// One block per octant region: the descriptors of its n_sub sub-regions, interleaved by index (arrival), into ONE list sorted by
+// cell key -- a counting sort, stable.  The block's 16 waves each take one contiguous stretch of the arrival order: a wave counts
+// its stretch's keys, the counts are turned into every (wave, key)'s first output position (earlier keys, then earlier waves),
+// and the wave places its stretch 64 descriptors at a time, a lane's rank among the lanes with its key from ballots.  Integer
+// only, no block waits on another.  The list's length goes behind the region's cursor (queue_head[1] of its first sub-region).
+constexpr int kOrderWaves = 16;
+__global__ __launch_bounds__(64 * kOrderWaves) void order_descriptors_kernel(OrderParams P) {
+  __shared__ uint32_t cnt[kOrderWaves][kMaxCellKeys];
+  __shared__ uint32_t key_at[kMaxCellKeys];
+  __shared__ uint32_t nd[8];
+  const uint32_t oct = blockIdx.x, n_sub = (uint32_t)P.n_sub, n_keys = (uint32_t)P.n_keys;
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  for (uint32_t i = threadIdx.x; i < kOrderWaves * kMaxCellKeys; i += blockDim.x) (&cnt[0][0])[i] = 0u;
+  if (threadIdx.x < 8u) {
+    const uint32_t* c = P.queue_count + 16u * (oct * n_sub + threadIdx.x);
+    nd[threadIdx.x] = threadIdx.x < n_sub ? min(desc_valid_count(c[1], c[3]), P.seg_cap) : 0u;
+  }
+  __syncthreads();
+  uint32_t n_max = 0u;
+  for (uint32_t s = 0; s < n_sub; s++) n_max = max(n_max, nd[s]);
+  // position j of the arrival order is descriptor j / n_sub of sub-region j % n_sub (where that sub-region has one)
+  const uint32_t n_pos = n_max * n_sub;
+  const uint32_t per_wave = ((n_pos + 64u * kOrderWaves - 1u) / (64u * kOrderWaves)) * 64u;
+  const uint32_t j_lo = min(w * per_wave, n_pos), j_hi = min(j_lo + per_wave, n_pos);
+  const QueueDesc* in = P.desc + (size_t)oct * n_sub * P.seg_cap;
+  QueueDesc* out = P.sorted + (size_t)oct * n_sub * P.seg_cap;
+  for (uint32_t j0 = j_lo; j0 < j_hi; j0 += 64u) {
+    const uint32_t j = j0 + lane, s = j % n_sub, i = j / n_sub;
+    if (j < j_hi && i < nd[s]) atomicAdd(&cnt[w][min(desc_key(in[(size_t)s * P.seg_cap + i]), n_keys - 1u)], 1u);
+  }
+  __syncthreads();
+  // cnt[w][k] -> descriptors of key k in the waves before w; key_at[k] -> descriptors of the keys before k
+  uint32_t tot = 0u;
+  if (threadIdx.x < kMaxCellKeys) {
+    for (int v = 0; v < kOrderWaves; v++) {
+      const uint32_t t = cnt[v][threadIdx.x];
+      cnt[v][threadIdx.x] = tot;
+      tot += t;
+    }
+    key_at[threadIdx.x] = tot;
+  }
+  __syncthreads();
+  if (w == 0u) { // exclusive scan of the kMaxCellKeys totals: 8 per lane, the lanes' sums by shuffles
+    uint32_t v[kMaxCellKeys / 64], sum = 0u;
+#pragma unroll
+    for (int q = 0; q < kMaxCellKeys / 64; q++) {
+      v[q] = key_at[lane * (kMaxCellKeys / 64) + q];
+      sum += v[q];
+    }
+    uint32_t incl = sum;
+#pragma unroll
+    for (int sh = 1; sh < 64; sh <<= 1) {
+      const uint32_t up = (uint32_t)__shfl_up((int)incl, sh);
+      if (lane >= (uint32_t)sh) incl += up;
+    }
+    uint32_t run = incl - sum;
+#pragma unroll
+    for (int q = 0; q < kMaxCellKeys / 64; q++) {
+      key_at[lane * (kMaxCellKeys / 64) + q] = run;
+      run += v[q];
+    }
+    if (lane == 63u) P.queue_head[16u * (oct * n_sub) + 1u] = incl; // the list's length
+  }
+  __syncthreads();
+  for (uint32_t j0 = j_lo; j0 < j_hi; j0 += 64u) {
+    const uint32_t j = j0 + lane, s = j % n_sub, i = j / n_sub;
+    const bool have = j < j_hi && i < nd[s];
+    QueueDesc d = {0u, 0u};
+    if (have) d = in[(size_t)s * P.seg_cap + i];
+    const uint32_t key = min(desc_key(d), n_keys - 1u);
+    unsigned long long peers = __ballot(have); // the lanes that hold a descriptor of this lane's key
+    for (uint32_t bit = 1u; bit < n_keys; bit <<= 1) {
+      const unsigned long long set = __ballot((key & bit) != 0u);
+      peers &= (key & bit) ? set : ~set;
+    }
+    const uint32_t before = (uint32_t)__popcll(peers & ((1ull << lane) - 1ull));
+    uint32_t at = 0u;
+    if (have) at = key_at[key] + cnt[w][key];
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (have) {
+      out[at + before] = d;
+      if (before + 1u == (uint32_t)__popcll(peers)) cnt[w][key] += before + 1u; // the key's last lane: one writer per address
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
 }
 
 // ------------------------------------------------------------------ K_B render from the queue
@@ -808,7 +942,12 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
   const uint32_t n_seg = (uint32_t)P.n_segments;
   // (an XCD starts at the first sub-region of its own octant region and walks on from there)
   const uint32_t n_sub = (uint32_t)max(P.n_sub, 1);
-  uint32_t seg = n_seg > 1u ? (((uint32_t)__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u) % (n_seg / n_sub)) * n_sub + (blockIdx.x * 4u + (threadIdx.x >> 6)) % n_sub : 0u;
+  // (n_cells > 1: `seg` counts OCTANT regions -- all of an XCD's waves take the next descriptor of its octant's sorted list)
+  const bool by_desc = P.n_cells > 1;
+  const uint32_t n_reg = by_desc ? n_seg / n_sub : n_seg;
+  uint32_t seg = n_seg > 1u ? (((uint32_t)__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u) % (n_seg / n_sub)) * (by_desc ? 1u : n_sub) +
+                                  (by_desc ? 0u : (blockIdx.x * 4u + (threadIdx.x >> 6)) % n_sub)
+                            : 0u;
   uint32_t seg_tried = 0;
   const uint4* __restrict__ queue = reinterpret_cast<const uint4*>(P.queue);
 
@@ -1012,11 +1151,27 @@ __device__ __forceinline__ void render_queue64_body(RenderParams P, const Render
       for (int grp = 0; grp < 2; grp++) {
         if (!(grp == 0 ? needA : needB)) continue;
         while (q_cur == q_end && !drained) {
+          if (by_desc) { // the next block of records of octant region `seg`, in cell order: one descriptor per returning add
+            uint32_t* head = P.queue_head + 16u * (seg * n_sub);
+            uint32_t claim = 0;
+            if (lane == 0) claim = atomicAdd(head, 1u);
+            claim = __builtin_amdgcn_readfirstlane(claim);
+            if (claim < head[1]) {
+              const QueueDesc dd = P.desc_sorted[(size_t)seg * n_sub * P.seg_cap + claim];
+              q_cur = dd.first;
+              q_end = dd.first + desc_count(dd);
+            } else if (++seg_tried >= n_reg) {
+              drained = true;
+            } else {
+              seg = seg + 1u == n_reg ? 0u : seg + 1u;
+            }
+            continue;
+          }
           uint32_t claim = 0;
           if (lane == 0) claim = atomicAdd(P.queue_head + 16u * seg, kClaim);
           claim = __builtin_amdgcn_readfirstlane(claim);
           // region `seg` of the queue: the records added to it, less the slots a reservation left empty at its end (region_reserve)
-          const uint32_t s_lo = seg * P.seg_cap, s_cnt = min(P.queue_count[16u * seg], P.seg_cap) - P.queue_count[16u * seg + 1u];
+          const uint32_t s_lo = seg * P.seg_cap, s_cnt = min(P.queue_count[16u * seg], P.seg_cap) - P.queue_count[16u * seg + 2u];
           if (claim < s_cnt) {
             q_cur = s_lo + claim;
             q_end = min(q_cur + kClaim, s_lo + s_cnt);
@@ -1927,6 +2082,12 @@ hipError_t launch_march(const MarchParams& P, int n_views, int n_spp, hipStream_
   }
   if (P.step_mode == PRV_STEP_NGP) hipLaunchKernelGGL(march_compact_kernel<true>, grid, dim3(256), 0, s, P);
   else hipLaunchKernelGGL(march_compact_kernel<false>, grid, dim3(256), 0, s, P);
+  return hipGetLastError();
+}
+
+hipError_t launch_order_descriptors(const OrderParams& P, hipStream_t s) {
+  if (P.n_keys < 2 || P.n_keys > kMaxCellKeys || P.n_sub < 1 || P.n_sub > 8 || P.n_seg % P.n_sub != 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(order_descriptors_kernel, dim3((unsigned)(P.n_seg / P.n_sub)), dim3(64 * kOrderWaves), 0, s, P);
   return hipGetLastError();
 }
 

@@ -3,6 +3,7 @@
 #include "../../include/prv.h"
 #include "prv_device.hpp"
 #include "prv_field_plan.hpp"
+#include "prv_queue_order.hpp"
 #include <type_traits>
 
 namespace prv {
@@ -42,6 +43,8 @@ struct MarchParams {
   uint32_t seg_cap;      // (spatial_regions; 0: linear block id % n_seg, rounds 1-5), or to the next region that has room
   int spatial_regions;
   int n_sub;             // spatial_regions: the n_seg regions are n_seg / n_sub octant regions of n_sub sub-regions each (a counter per sub-region)
+  int n_cells;           // PRV_REGION_CELLS: > 1 = every wave also writes its block's descriptor, keyed by which of n_cells^3 cells of the octant
+  QueueDesc* desc;       //   its mid-span point falls in (prv_queue_order.hpp); seg_cap descriptors per region
   float* out_f32; // n_views*H*W*4
   uint32_t* out_u8; // optional, n_views*H*W
   int last_pass;
@@ -54,6 +57,7 @@ struct MarchMember {
   void* queue;
   uint4* queue_ext;
   uint32_t* queue_count; // this member's n_seg counters, 64 bytes apart
+  QueueDesc* desc;       // this member's descriptors (MarchParams::desc)
   float* out_f32;        // where this member's dead rays are written (its own staging / image)
   uint32_t* out_u8;
 };
@@ -71,6 +75,7 @@ struct MarchMultiParams {
   int n_seg;
   uint32_t seg_cap;
   int spatial_regions, n_sub; // MarchParams::spatial_regions, n_sub
+  int n_cells;                // MarchParams::n_cells
   int last_pass;
   float bg[4];
   int n_members;
@@ -84,6 +89,17 @@ struct OccInterleaveParams {
 };
 bool march_multi_supported(int n_members); // a compiled instance exists (2 and 5: the paper's ensembles)
 hipError_t launch_march_multi(const MarchMultiParams& P, int n_views, int n_spp, hipStream_t s);
+// the launch between march and render when n_cells > 1 (order_descriptors_kernel): every octant region's descriptors by cell key
+struct OrderParams {
+  const QueueDesc* desc;       // what the march wrote: seg_cap per region
+  QueueDesc* sorted;           // n_sub * seg_cap per octant region
+  const uint32_t* queue_count; // per region: [0] records, [1] descriptor indices handed out, [2] tail cut, [3] closed_at
+  uint32_t* queue_head;        // [1] of an octant region's first sub-region <- the length of its sorted list
+  int n_seg, n_sub;
+  uint32_t seg_cap;
+  int n_keys; // n_cells^3
+};
+hipError_t launch_order_descriptors(const OrderParams& P, hipStream_t s);
 hipError_t launch_occ_interleave(const OccInterleaveParams& P, hipStream_t s);
 
 struct RenderParams {
@@ -96,6 +112,8 @@ struct RenderParams {
   int n_segments;
   int n_sub; // an XCD starts at sub-region 0 of ITS octant region: segment (XCC id % (n_segments / n_sub)) * n_sub
   uint32_t seg_cap;     // records per region: region s = [s * seg_cap, s * seg_cap + queue_count[16 s])
+  int n_cells;          // > 1: a region is an OCTANT region, drained descriptor by descriptor from desc_sorted (one cursor: the head of its
+  const QueueDesc* desc_sorted; // first sub-region; the list's length behind it), n_sub * seg_cap descriptors apart
   unsigned long long* stat_evaluated;
   float* out_f32;
   uint32_t* out_u8;
