@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PRV_ABI_VERSION 5 /* 2: prv_field_desc.per_level_scale; 3: prv_render_opts.step_mode, prv_stats.samples_live; 4: prv_train_opts.patch_w / patch_h; 5: prv_train_opts.step_mode / deterministic (still 5: prv_train_create accepting lr = 0, which it refused, changes no layout and no call that worked; nor do the prv_coverage_* entry points: additive; nor prv_mesh_from_arrays, prv_mesh_depth and prv_coverage_create_occluded: additive too; nor prv_debug_live_bytes; nor prv_mesh_set_colors and prv_mesh_render: additive) */
+#define PRV_ABI_VERSION 5 /* 2: prv_field_desc.per_level_scale; 3: prv_render_opts.step_mode, prv_stats.samples_live; 4: prv_train_opts.patch_w / patch_h; 5: prv_train_opts.step_mode / deterministic (still 5: prv_train_create accepting lr = 0, which it refused, changes no layout and no call that worked; nor do the prv_coverage_* entry points: additive; nor prv_mesh_from_arrays, prv_mesh_depth and prv_coverage_create_occluded: additive too; nor prv_debug_live_bytes; nor prv_mesh_set_colors and prv_mesh_render: additive; nor the prv_tsdf_* entry points and prv_marching_cubes_grid_valid: additive) */
 
 /* error codes (0 = ok, < 0 = error; message via prv_last_error) */
 #define PRV_OK 0
@@ -511,6 +511,13 @@ int prv_density_grid(prv_ctx* ctx, int model_slot, const prv_mesh_opts* o, float
 int prv_marching_cubes(prv_ctx* ctx, int model_slot, const prv_mesh_opts* o, prv_mesh** out);
 /* marching cubes on a caller's sigma grid (device, layout of prv_density_grid); no colours (rgb reads as 0) */
 int prv_marching_cubes_grid(prv_ctx* ctx, const float* sigma_dev, const prv_mesh_opts* o, prv_mesh** out);
+/* the same on a grid of which only some points are known.  valid_dev: one byte per grid point (device, the grid's layout), 0 =
+ * not valid; NULL: every point is valid, the call IS prv_marching_cubes_grid, byte for byte.  A cell is KEPT iff all eight of
+ * its corners are valid.  Triangles come from kept cells only, in cell order; a grid edge gives a vertex iff it crosses and at
+ * least one of the (up to four) cells around it is kept, so no vertex is unused and vertices stay in edge-id order.  Positions
+ * and normals are computed as above (a normal whose gradient meets a NaN neighbour is (0, 0, 0) by the rule above).  The result
+ * is what prv_marching_cubes_grid gives with the triangles of the other cells dropped and the then-unused vertices removed. */
+int prv_marching_cubes_grid_valid(prv_ctx* ctx, const float* grid_dev, const uint8_t* valid_dev, const prv_mesh_opts* o, prv_mesh** out);
 int prv_mesh_counts(const prv_mesh* m, uint64_t* n_vertices, uint64_t* n_triangles);
 /* host arrays: xyz / normals n_vertices*3 floats, rgb n_vertices*3 bytes, tri n_triangles*3 vertex ids; any may be NULL */
 int prv_mesh_get(const prv_mesh* m, float* xyz, float* normals, uint8_t* rgb, uint32_t* tri);
@@ -804,6 +811,71 @@ int prv_mesh_set_colors(prv_mesh* m, const uint8_t* rgb_host, uint64_t n_vertice
 /* out_rgba8_dev: n_views*h*w*4 bytes; depth_out_dev / tri_out_dev optional (NULL), n_views*h*w each */
 int prv_mesh_render(prv_ctx* ctx, const prv_mesh* m, const prv_camset* cs, const int* view_ids, int n_views, int width, int height,
                     int flip180, uint8_t* out_rgba8_dev, float* depth_out_dev, uint32_t* tri_out_dev);
+
+/* ---- depth-map fusion: a truncated signed distance volume from depth images ------- */
+/* replaces: nothing in the reference.  This build's own: the surface that a set of views SAW -- depth (and colour) images of
+ * the views, from a field (prv_render_surface, prv_render_depth, prv_render_rgba8) or from a ground-truth surface (prv_mesh_depth,
+ * prv_mesh_render), fused into a volume whose zero level is extracted as a mesh.  Unlike prv_marching_cubes it needs no density
+ * iso-level, keeps no floater that no view's depth confirms, and leaves open what no view observed.
+ * The volume's grid points are prv_marching_cubes_grid's, bit for bit (p_a = lo[a] + (float)i * step[a], step[a] = (hi[a] - lo[a])
+ * / (float)(res[a] - 1), x fastest), so its mesh aligns with a density mesh of the same options.  State per point: D (the
+ * truncated distance in units of trunc), W (its weight), WC (the colour's weight) and C[3] (red, green, blue in byte units), all
+ * float32 and all 0 in a new volume.
+ * ARITHMETIC CONTRACT of prv_tsdf_integrate.  Every float operation below is one IEEE float32 operation in the order written
+ * (fmaf = one fused multiply-add); inv = 1.0f / trunc is formed once.  For each grid point e the views are taken IN LIST ORDER:
+ *   1. projection: the coverage section's, unchanged, lens cameras included (c_2 > 1e-6f, c_2 < +Inf; u, v, z = c_2).  fu =
+ *      floorf(u), fv = floorf(v); the view is skipped unless 0 <= fu < (float)width and 0 <= fv < (float)height (a NaN fails).
+ *   2. the pixel: d = depth[view][(int)fv][(int)fu], ws = weight ? weight[the same pixel] : 1.0f; the view is skipped unless
+ *      d > 0, d < +Inf, ws > 0 and ws < +Inf (a NaN fails).  Images are unflipped, as prv_mesh_depth writes them; depth is z along
+ *      the optical axis (the z of the projection), engine units.
+ *   3. sdf = d - z; the view is skipped if sdf < -trunc: the point lies behind what this view sees.
+ *   4. s = fminf(sdf * inv, 1.0f);  Wn = W + ws;  D = fmaf(D, W, s * ws) / Wn;  W = Wn.
+ *   5. only if the volume keeps colours, rgba8_dev is given and sdf <= trunc:  WCn = WC + ws;  for k = 0, 1, 2:
+ *      C[k] = fmaf(C[k], WC, (float)byte_k * ws) / WCn  (all three with the old WC);  then WC = WCn.  The alpha byte is not used.
+ *      The colour has a weight of its own because free space far in front of some other surface must not tint a voxel.
+ *   CONSEQUENCES: integrating the views [a, b] in one call equals integrating [a] and then [b], byte for byte (the state between
+ *   two views is the float32 state itself); two runs give identical bytes.  There are no atomics: one lane owns a point.
+ * prv_tsdf_grid: valid = W > 0 && W >= min_weight; grid = valid ? -D : NaN.  With threshold 0 "inside" is then D < 0, the
+ *   orientation of prv_marching_cubes: counter-clockwise seen from the lower value, i.e. from the observed free side.
+ * prv_tsdf_mesh: prv_tsdf_grid, then prv_marching_cubes_grid_valid at threshold 0 (cells that touch an unobserved point give
+ *   nothing: the back of the truncation band is no second surface), then, if the volume keeps colours, one colour per vertex:
+ *   the vertex takes the nearest grid point, i_a = clamp((int)rintf((p_a - lo[a]) / step[a]), 0, res[a] - 1) -- an end of its own
+ *   edge, and both ends are valid in a kept cell -- and byte_k = (uint8)fminf(255.0f, floorf(C[k] + 0.5f)) if that point has
+ *   WC > 0, else 0.  The result is an ordinary prv_mesh (prv_mesh_get, _save, _components, _filter, _sample, prv_mesh_render and
+ *   the occluder of prv_coverage_create_occluded take it).  A volume nothing was fused into gives 0 vertices, not an error.
+ * prv_tsdf_info: counts[0] = grid points, [1] = observed (W > 0), [2] = inside (observed and D < 0), [3] = band (observed and
+ *   |D| < 1); integer counts.
+ * HOW IT RUNS (no byte depends on it): one lane per grid point, x fastest, so a wave's 64 points project to neighbouring pixels;
+ * the loop over the views runs inside the kernel with the point's state in registers -- each state word is read once and written
+ * once per launch -- and the views' cameras travel as kernel arguments (scalar registers), 32 per launch (PRV_TSDF_CHUNK lowers
+ * it, read per call; a longer list takes several launches over consecutive views).  Synchronises.
+ * Errors, PRV_E_INVALID with a message: a NULL or host pointer where a device pointer is required, rgba8_dev not 4-byte aligned,
+ * a bad image size or view id, trunc not positive and finite, res or aabb that prv_mesh_opts would refuse (with its messages), a
+ * min_weight that is NaN or negative; a volume that outlives its context: PRV_E_STATE.  n_views = 0 is a no-op.
+ * LIMITS: NEAREST-PIXEL depth lookup, no sub-pixel interpolation of the depth image; colour by the NEAREST GRID POINT; the default
+ * trunc (three steps of the default grid) is an option value, NOT a measured one; 24 bytes per point with colours (8 without):
+ * about 400 MiB at 256^3; views that leave a side unobserved leave the mesh OPEN there, by design; SINGLE-RANK. */
+typedef struct prv_tsdf prv_tsdf; /* owns its device buffers; inert (PRV_E_STATE) if it outlives its context */
+typedef struct prv_tsdf_opts {
+  int32_t res[3];               /* grid points per axis, exactly prv_mesh_opts' meaning and limits */
+  float aabb_lo[3], aabb_hi[3]; /* engine frame, as prv_mesh_opts */
+  float trunc;                  /* truncation distance, engine units, > 0 and finite */
+  int32_t colors;               /* 1: keep a colour volume */
+} prv_tsdf_opts;
+int prv_tsdf_default_opts(prv_tsdf_opts* opts); /* 256^3, unit cube, trunc = 3 * the largest grid step, colours */
+int prv_tsdf_create(prv_ctx* ctx, const prv_tsdf_opts* opts, prv_tsdf** out);
+/* depth_dev: n_views*h*w float32; weight_dev (NULL: 1) the same shape; rgba8_dev (NULL: no colour) n_views*h*w*4 bytes; view_ids
+ * NULL: cameras 0..n_views-1 */
+int prv_tsdf_integrate(prv_tsdf* tsdf, const prv_camset* cs, const int* view_ids, int n_views, int width, int height,
+                       const float* depth_dev, const float* weight_dev, const uint8_t* rgba8_dev);
+int prv_tsdf_info(prv_tsdf* tsdf, uint64_t counts[4]);
+/* grid_dev: res[0]*res[1]*res[2] float32, the layout of prv_density_grid; valid_dev: as many bytes; either may be NULL */
+int prv_tsdf_grid(prv_tsdf* tsdf, float min_weight, float* grid_dev, uint8_t* valid_dev);
+int prv_tsdf_mesh(prv_tsdf* tsdf, float min_weight, prv_mesh** out);
+/* the state as host planes of one float per grid point: D, W, WC, and C as three planes (red, green, blue); any may be NULL; a
+ * volume without colours reads WC and C as 0 (a test hook) */
+int prv_debug_tsdf_state(prv_tsdf* tsdf, float* d_host, float* w_host, float* wc_host, float* c_host);
+void prv_tsdf_destroy(prv_tsdf* tsdf);
 
 /* ---- several GPUs: view sharding + one all-gather ----------------------------- */
 /* replaces: nothing in the reference -- its loops over the candidates are serial (main.cpp:2045-2094, 2105-2158;

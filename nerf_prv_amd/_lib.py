@@ -98,6 +98,10 @@ class CoverageOpts(C.Structure):
     _fields_ = [("point_size", C.c_int32), ("depth_tol", C.c_float)]
 
 
+class TsdfOpts(C.Structure):
+    _fields_ = [("res", C.c_int32 * 3), ("aabb_lo", C.c_float * 3), ("aabb_hi", C.c_float * 3), ("trunc", C.c_float), ("colors", C.c_int32)]
+
+
 class GeomMetrics(C.Structure):
     _fields_ = [("n_rec", C.c_uint64), ("n_ref", C.c_uint64)] + [(n, C.c_double) for n in (
         "accuracy", "completeness", "accuracy_sq", "completeness_sq", "chamfer", "precision", "recall", "fscore", "hausdorff_rec",
@@ -218,6 +222,15 @@ SIGNATURES = {
     "prv_mesh_render": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "prv_coverage_create_occluded": (_i, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, _i, _i, _i, _P(CoverageOpts), _vp, _P(_vp)]),
     "prv_debug_raster_stats": (_i, [_vp, _vp]),
+    "prv_marching_cubes_grid_valid": (_i, [_vp, _vp, _vp, _P(MeshOpts), _P(_vp)]),
+    "prv_tsdf_default_opts": (_i, [_P(TsdfOpts)]),
+    "prv_tsdf_create": (_i, [_vp, _P(TsdfOpts), _P(_vp)]),
+    "prv_tsdf_integrate": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "prv_tsdf_info": (_i, [_vp, _P(C.c_uint64)]),
+    "prv_tsdf_grid": (_i, [_vp, C.c_float, _vp, _vp]),
+    "prv_tsdf_mesh": (_i, [_vp, C.c_float, _P(_vp)]),
+    "prv_debug_tsdf_state": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "prv_tsdf_destroy": (None, [_vp]),
     "prv_debug_live_bytes": (C.c_uint64, []),
     "prv_score_ensemble_images": (_i, [_vp, _i, _vp, _i, _i, C.c_size_t, _vp]),
     "prv_score_psnr_images": (_i, [_vp, _vp, _vp, _i, C.c_size_t, _vp, _vp]),

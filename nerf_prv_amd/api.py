@@ -595,16 +595,34 @@ class Context:
         self._chk(self.lib.prv_marching_cubes(self.handle, slot, C.byref(o), C.byref(h)))
         return Mesh(self, h)
 
-    def marching_cubes_grid(self, sigma, aabb=None, threshold=2.5):
-        """marching cubes on a caller's sigma grid (torch float32 (rz, ry, rx) on the device) -> Mesh without colours"""
+    def marching_cubes_grid(self, sigma, aabb=None, threshold=2.5, valid=None):
+        """marching cubes on a caller's sigma grid (torch float32 (rz, ry, rx) on the device) -> Mesh without colours.  valid: a
+        uint8 or bool device tensor of the same shape -- only cells whose eight corners are valid give triangles, and no vertex is
+        left unused (prv_marching_cubes_grid_valid); None: every point is valid"""
         if sigma.dim() != 3 or sigma.dtype != self.torch.float32 or not sigma.is_cuda:
             raise ValueError("sigma must be a float32 (rz, ry, rx) device tensor")
         sigma = sigma.contiguous()
         rz, ry, rx = sigma.shape
         o = mesh_opts((rx, ry, rz), aabb, threshold, colors=False)
         h = C.c_void_p()
-        self._chk(self.lib.prv_marching_cubes_grid(self.handle, _ptr(sigma), C.byref(o), C.byref(h)))
+        if valid is None:
+            self._chk(self.lib.prv_marching_cubes_grid(self.handle, _ptr(sigma), C.byref(o), C.byref(h)))
+            return Mesh(self, h)
+        if tuple(valid.shape) != tuple(sigma.shape) or valid.dtype not in (self.torch.uint8, self.torch.bool) or not valid.is_cuda:
+            raise ValueError("valid must be a uint8 or bool device tensor of sigma's shape")
+        valid = valid.to(self.torch.uint8).contiguous()
+        self._chk(self.lib.prv_marching_cubes_grid_valid(self.handle, _ptr(sigma), _ptr(valid), C.byref(o), C.byref(h)))
         return Mesh(self, h)
+
+    # -- depth-map fusion (include/prv.h, depth-map fusion section)
+    def tsdf_volume(self, res=256, aabb=None, trunc=None, colors=True):
+        """a truncated signed distance volume on the grid of `marching_cubes_grid` (prv_tsdf_create) -> TSDFVolume.  res = N or
+        (rx, ry, rz); aabb = (lo, hi) in the engine frame (None: the unit cube); trunc: the truncation distance in engine units
+        (None: three times the largest grid step, an option value, not a measured one)"""
+        o = tsdf_opts(res, aabb, trunc, colors)
+        h = C.c_void_p()
+        self._chk(self.lib.prv_tsdf_create(self.handle, C.byref(o), C.byref(h)))
+        return TSDFVolume(self, h, o)
 
     # -- geometric evaluation (include/prv.h, geometric evaluation section)
     def _points(self, xyz):
@@ -830,6 +848,89 @@ class Mesh(_Handle):
         h = C.c_void_p()
         self._chk(self.ctx.lib.prv_mesh_filter(self.handle, C.byref(o), C.byref(h)))
         return Mesh(self.ctx, h)
+
+
+def tsdf_opts(res=256, aabb=None, trunc=None, colors=True):
+    """prv_tsdf_opts: res and aabb as `mesh_opts`; trunc None: 3 * the largest grid step of this grid, in float32"""
+    m = mesh_opts(res, aabb)
+    o = L.TsdfOpts()
+    L.load().prv_tsdf_default_opts(C.byref(o))
+    for a in range(3):
+        o.res[a], o.aabb_lo[a], o.aabb_hi[a] = m.res[a], m.aabb_lo[a], m.aabb_hi[a]
+    if trunc is None:
+        f = np.float32
+        with np.errstate(all="ignore"):  # (a bad res or box is the library's to refuse)
+            trunc = f(3) * max((f(m.aabb_hi[a]) - f(m.aabb_lo[a])) / f(max(m.res[a] - 1, 1)) for a in range(3))
+    o.trunc = float(trunc)
+    o.colors = int(bool(colors))
+    return o
+
+
+class TSDFVolume(_Handle):
+    """a truncated signed distance volume owned by the library (prv_tsdf): depth images of views are fused into it, and its
+    zero level comes out as a Mesh.  res = (rx, ry, rz), aabb = (lo, hi), trunc, colors: what it was made with"""
+    _destroy = "prv_tsdf_destroy"
+
+    def __init__(self, ctx, handle, opts):
+        super().__init__(ctx, handle)
+        self.res = tuple(int(x) for x in opts.res)
+        self.aabb = (tuple(float(x) for x in opts.aabb_lo), tuple(float(x) for x in opts.aabb_hi))
+        self.trunc, self.colors = float(opts.trunc), bool(opts.colors)
+
+    def _plane(self, t, name, dtype, shape):
+        torch = self.ctx.torch
+        if t is None:
+            return None
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be a {dtype} device tensor of shape {shape}")
+        return t.contiguous()
+
+    def integrate(self, camset, view_ids, depth, weight=None, rgba8=None):
+        """fuse the views' images (prv_tsdf_integrate), in list order: depth float32 [n, h, w] (z along the optical axis, engine
+        units, unflipped; <= 0, Inf and NaN pixels are skipped), weight float32 [n, h, w] or None (1), rgba8 uint8 [n, h, w, 4]
+        or None (no colour); device tensors, the size is the depth tensor's"""
+        torch = self.ctx.torch
+        ids = self.ctx._ids(camset, view_ids)
+        if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
+            raise ValueError("depth must be a float32 [n_views, h, w] device tensor")
+        n, h, w = (int(x) for x in depth.shape)
+        if n != len(ids):
+            raise ValueError(f"{len(ids)} views but {n} depth images")
+        depth = self._plane(depth, "depth", torch.float32, (n, h, w))
+        weight = self._plane(weight, "weight", torch.float32, (n, h, w))
+        rgba8 = self._plane(rgba8, "rgba8", torch.uint8, (n, h, w, 4))
+        self._chk(self.ctx.lib.prv_tsdf_integrate(self.handle, camset.handle, _ptr(ids), n, w, h, _ptr(depth), _ptr(weight), _ptr(rgba8)))
+
+    def info(self):
+        """-> dict(points, observed (W > 0), inside (observed, D < 0), band (observed, |D| < 1))"""
+        out = (C.c_uint64 * 4)()
+        self._chk(self.ctx.lib.prv_tsdf_info(self.handle, out))
+        return dict(points=int(out[0]), observed=int(out[1]), inside=int(out[2]), band=int(out[3]))
+
+    def grid(self, min_weight=0.0):
+        """-> (grid float32 (rz, ry, rx): -D, NaN where not valid; valid uint8 (rz, ry, rx): W > 0 and W >= min_weight), on the
+        device (prv_tsdf_grid): what `Context.marching_cubes_grid(grid, aabb, 0.0, valid=valid)` takes"""
+        torch = self.ctx.torch
+        rx, ry, rz = self.res
+        grid = torch.empty((rz, ry, rx), dtype=torch.float32, device=self.ctx.device)
+        valid = torch.empty((rz, ry, rx), dtype=torch.uint8, device=self.ctx.device)
+        self._chk(self.ctx.lib.prv_tsdf_grid(self.handle, float(min_weight), _ptr(grid), _ptr(valid)))
+        return grid, valid
+
+    def mesh(self, min_weight=0.0):
+        """the zero level as a Mesh (prv_tsdf_mesh): only cells whose corners are all observed with at least min_weight, vertex
+        colours from the nearest grid point if the volume keeps colours"""
+        h = C.c_void_p()
+        self._chk(self.ctx.lib.prv_tsdf_mesh(self.handle, float(min_weight), C.byref(h)))
+        return Mesh(self.ctx, h)
+
+    def state(self):
+        """host copies of the state (prv_debug_tsdf_state, a test hook) -> dict(D, W, WC: (rz, ry, rx) float32, C: (3, rz, ry, rx))"""
+        rx, ry, rz = self.res
+        out = dict(D=np.zeros((rz, ry, rx), np.float32), W=np.zeros((rz, ry, rx), np.float32), WC=np.zeros((rz, ry, rx), np.float32),
+                   C=np.zeros((3, rz, ry, rx), np.float32))
+        self._chk(self.ctx.lib.prv_debug_tsdf_state(self.handle, _ptr(out["D"]), _ptr(out["W"]), _ptr(out["WC"]), _ptr(out["C"])))
+        return out
 
 
 class NNIndex(_Handle):
@@ -1342,18 +1443,60 @@ class Testbed:
         finally:
             m.close()
 
+    TSDF_VIEW_BATCH = 16  # views rendered and fused per batch by compute_tsdf_mesh (the batches change no byte)
+
+    def compute_tsdf_mesh(self, camset, view_ids, width, height, resolution=(256, 256, 256), aabb=None, trunc=None, level=0.5,
+                          min_weight=0.0, keep_largest=0, min_triangles=0):
+        """the surface the views `view_ids` of `camset` (None: all) SEE in the current model, by depth-map fusion (this build's
+        own; include/prv.h, depth-map fusion): each view is rendered at width x height, one sample per pixel, under the Testbed's
+        stepping rule -- `render_surface` for the first-crossing depth at opacity `level` (weight = hit, 0 or 1 at one sample per
+        pixel) and `render_rgba8` for the colour -- fused into a volume of `resolution` points over `aabb` (engine frame, None:
+        the unit cube) with truncation `trunc` (None: three grid steps), and the zero level is meshed; keep_largest /
+        min_triangles: the floater filter of compute_and_save_marching_cubes_mesh.  -> Mesh, engine frame (close it)"""
+        if not self._have_model:
+            raise PrvError(L.PRV_E_STATE, "no model loaded")
+        ids = self.ctx._ids(camset, view_ids)
+        opts = engine_render_opts(width, height, self.nerf.samples_per_ray, 1, self.nerf.render_min_transmittance)
+        with self.ctx.tsdf_volume(resolution, aabb, trunc, colors=True) as vol:
+            for i in range(0, len(ids), self.TSDF_VIEW_BATCH):
+                batch = ids[i:i + self.TSDF_VIEW_BATCH]
+                _, _, depth, hit, _ = self.ctx.render_surface(self._slot, camset, batch, opts, level, want_stats=False)
+                rgba8, _ = self.ctx.render_rgba8(self._slot, camset, batch, opts, want_stats=False)
+                vol.integrate(camset, batch, depth, weight=hit, rgba8=rgba8)
+            return self._without_floaters(vol.mesh(min_weight), keep_largest, min_triangles)
+
+    def compute_and_save_tsdf_mesh(self, filename, camset, view_ids, width, height, resolution=(256, 256, 256), aabb=None, trunc=None,
+                                   level=0.5, min_weight=0.0, keep_largest=0, min_triangles=0):
+        """compute_tsdf_mesh, saved as compute_and_save_marching_cubes_mesh saves (.ply / .obj, dataset frame)"""
+        m = self.compute_tsdf_mesh(camset, view_ids, width, height, resolution, aabb, trunc, level, min_weight, keep_largest, min_triangles)
+        try:
+            m.save(filename, self.scale, self.offset)
+        finally:
+            m.close()
+
     def compute_geometry_metrics(self, reference_points, resolution=(256, 256, 256), n_samples=1 << 20, tau=None, thresh=2.5, seed=0,
-                                 keep_largest=0, min_triangles=0):
+                                 keep_largest=0, min_triangles=0, surface="density", tsdf=None):
         """mesh the current model (marching cubes at `resolution`, iso-level `thresh`), sample n_samples surface points and
         compare them with reference_points ((n, 3), dataset frame) -> dict of prv_geom_metrics' fields in DATASET units.
         tau (dataset units) defaults to 1 % of the reference's largest extent.  keep_largest / min_triangles (0: off): the
-        mesh is filtered first (Mesh.filter), so floaters do not enter accuracy and hausdorff_rec."""
+        mesh is filtered first (Mesh.filter), so floaters do not enter accuracy and hausdorff_rec.
+        surface = "tsdf": the mesh is compute_tsdf_mesh's at `resolution` instead; tsdf = dict(camset=, view_ids=, width=, height=)
+        and optionally trunc, level, min_weight, aabb (thresh is not used)."""
         if not self._have_model:
             raise PrvError(L.PRV_E_STATE, "no model loaded")
+        if surface not in ("density", "tsdf"):
+            raise ValueError('surface must be "density" or "tsdf"')
+        if surface == "tsdf" and (not tsdf or any(k not in tsdf for k in ("camset", "width", "height"))):
+            raise ValueError('surface="tsdf" needs tsdf=dict(camset=, view_ids=, width=, height=, ...)')
         ref = np.asarray(reference_points, np.float64).reshape(-1, 3)
         if tau is None:
             tau = 0.01 * float((ref.max(axis=0) - ref.min(axis=0)).max())
-        m = self._without_floaters(self.ctx.marching_cubes(self._slot, resolution, None, thresh, colors=False), keep_largest, min_triangles)
+        if surface == "tsdf":
+            kw = dict(tsdf)
+            m = self.compute_tsdf_mesh(kw.pop("camset"), kw.pop("view_ids", None), kw.pop("width"), kw.pop("height"), resolution,
+                                       keep_largest=keep_largest, min_triangles=min_triangles, **kw)
+        else:
+            m = self._without_floaters(self.ctx.marching_cubes(self._slot, resolution, None, thresh, colors=False), keep_largest, min_triangles)
         try:
             rec = m.sample(n_samples, seed)
         finally:

@@ -49,11 +49,11 @@ def hipcc():
 
 def build_hip(force=False):
     out = os.path.join(HERE, "libprv_hip.so")
-    srcs = [os.path.join(CSRC, f) for f in ("prv_kernels.hip", "prv_train.hip", "prv_mesh.hip", "prv_components.hip", "prv_geom.hip", "prv_select.hip", "prv_coverage.hip", "prv_raster.hip", "prv_api.cpp")]
+    srcs = [os.path.join(CSRC, f) for f in ("prv_kernels.hip", "prv_train.hip", "prv_mesh.hip", "prv_components.hip", "prv_geom.hip", "prv_select.hip", "prv_coverage.hip", "prv_raster.hip", "prv_tsdf.hip", "prv_api.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("prv_buffer.hpp", "prv_device.hpp", "prv_kernels.hpp", "prv_json.hpp", "prv_train.hpp",
                                                    "prv_train_api.inc", "prv_train_switches.hpp", "prv_comm_api.inc", "prv_star.hpp", "prv_levels.hpp", "prv_field_plan.hpp", "prv_ingp.hpp",
                                                    "prv_mesh.hpp", "prv_mesh_api.inc", "prv_mc_tables.hpp", "prv_geom.hpp", "prv_geom_api.inc", "prv_select.hpp", "prv_select_api.inc",
-                                                   "prv_coverage.hpp", "prv_coverage_api.inc", "prv_raster.hpp", "prv_raster_api.inc", "prv_raster_color_api.inc")] + [
+                                                   "prv_coverage.hpp", "prv_coverage_api.inc", "prv_raster.hpp", "prv_raster_api.inc", "prv_raster_color_api.inc", "prv_tsdf.hpp", "prv_tsdf_api.inc")] + [
         os.path.join(ROOT, "include", "prv.h")]
     # the flags the library was built with (PRV_ABLATE / PRV_TRAIN_ABLATE / PRV_EXTRA_HIPFLAGS timing builds change them, not the
     # sources: a comparison of "two builds" that skipped the second compile measures one binary twice)

@@ -25,6 +25,7 @@
 #include "prv_select.hpp"
 #include "prv_coverage.hpp"
 #include "prv_raster.hpp"
+#include "prv_tsdf.hpp"
 #include "prv_levels.hpp"
 #include "prv_field_plan.hpp"
 #include "prv_ingp.hpp"
@@ -2158,3 +2159,4 @@ int prv_debug_field(prv_ctx* c, int slot, const float* pos, const float* dir, in
 #include "prv_raster_api.inc"
 #include "prv_raster_color_api.inc"
 #include "prv_coverage_api.inc"
+#include "prv_tsdf_api.inc"

@@ -71,10 +71,30 @@ __global__ __launch_bounds__(256) void mesh_density_kernel(FieldDev fd, MeshGrid
   if (ok) sigma[out] = occ ? fast_exp((grp ? densB[8] : densA[0]) + fd.density_bias) : 0.0f;
 }
 
+// ------------------------------------------------------------------ kept cells (masked extraction only)
+// kept[point] = 1 iff the point is the low corner of a cell whose eight corners are all valid; the tail of the last block is 0
+__global__ __launch_bounds__(256) void mesh_kept_kernel(const uint8_t* __restrict__ valid, MeshGrid g, uint32_t n_points, uint8_t* __restrict__ kept) {
+  const uint32_t idx = blockIdx.x * 256 + threadIdx.x;
+  const uint32_t rx = (uint32_t)g.res[0], ry = (uint32_t)g.res[1], rz = (uint32_t)g.res[2], rxy = rx * ry;
+  uint32_t k = 0;
+  if (idx < n_points) {
+    const uint32_t x = idx % rx, y = (idx % rxy) / rx, z = idx / rxy;
+    if (x + 1 < rx && y + 1 < ry && z + 1 < rz) {
+      k = 1;
+#pragma unroll
+      for (int c = 0; c < 8; c++) k &= (uint32_t)(valid[idx + (c & 1) + ((c >> 1) & 1) * rx + (c >> 2) * rxy] != 0);
+    }
+  }
+  kept[idx] = (uint8_t)k;
+}
+
 // ------------------------------------------------------------------ classify
+// kept == nullptr: every cell counts.  Otherwise only kept cells have a case, and a crossing edge has a vertex only if one of
+// the (up to four) cells around it is kept
 __global__ __launch_bounds__(256) void mesh_classify_kernel(const float* __restrict__ sigma, MeshGrid g, float thr, uint32_t n_points,
-                                                            uint8_t* __restrict__ flags, uint8_t* __restrict__ cases,
-                                                            uint64_t* __restrict__ wave_v, uint64_t* __restrict__ wave_t) {
+                                                            const uint8_t* __restrict__ kept, uint8_t* __restrict__ flags,
+                                                            uint8_t* __restrict__ cases, uint64_t* __restrict__ wave_v,
+                                                            uint64_t* __restrict__ wave_t) {
   const uint32_t idx = blockIdx.x * 256 + threadIdx.x;
   const uint32_t rx = (uint32_t)g.res[0], ry = (uint32_t)g.res[1], rz = (uint32_t)g.res[2], rxy = rx * ry;
   uint32_t fl = 0, cs = 0;
@@ -89,6 +109,24 @@ __global__ __launch_bounds__(256) void mesh_classify_kernel(const float* __restr
       for (int c = 0; c < 8; c++) {
         const uint32_t q = idx + (c & 1) + ((c >> 1) & 1) * rx + (c >> 2) * rxy;
         cs |= (uint32_t)(sigma[q] > thr) << c;
+      }
+    }
+    if (kept) { // uniform
+      if (!kept[idx]) cs = 0;
+      // the cells around the +a edge of this point: the point's own and those one step back along the other two axes (a point
+      // without a cell has kept = 0, so only the steps below 0 need a test)
+      const uint32_t pos[3] = {x, y, z}, stride[3] = {1u, rx, rxy};
+#pragma unroll
+      for (int a = 0; a < 3; a++) {
+        if (!((fl >> a) & 1u)) continue;
+        const int b = (a + 1) % 3, c = (a + 2) % 3;
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const uint32_t db = k & 1, dc = k >> 1;
+          if (pos[b] >= db && pos[c] >= dc) any = any || kept[idx - db * stride[b] - dc * stride[c]] != 0;
+        }
+        if (!any) fl &= ~(1u << a);
       }
     }
   }
@@ -289,11 +327,17 @@ hipError_t launch_mesh_density(const FieldDev& fd, const MeshGrid& g, int use_oc
   return hipGetLastError();
 }
 
-hipError_t launch_mesh_classify(const float* sigma, const MeshGrid& g, float thr, uint8_t* flags, uint8_t* cases, uint64_t* wave_v,
-                                uint64_t* wave_t, hipStream_t s) {
+hipError_t launch_mesh_kept(const uint8_t* valid, const MeshGrid& g, uint8_t* kept, hipStream_t s) {
+  const size_t waves = mesh_waves(g); // a multiple of 4: every thread of the launch has its byte of kept
+  hipLaunchKernelGGL(mesh_kept_kernel, dim3((unsigned)(waves / 4)), dim3(256), 0, s, valid, g, (uint32_t)mesh_points(g), kept);
+  return hipGetLastError();
+}
+
+hipError_t launch_mesh_classify(const float* sigma, const MeshGrid& g, float thr, const uint8_t* kept, uint8_t* flags, uint8_t* cases,
+                                uint64_t* wave_v, uint64_t* wave_t, hipStream_t s) {
   const size_t waves = mesh_waves(g); // a multiple of 4: every thread of the launch has its byte of flags / cases
   hipLaunchKernelGGL(mesh_classify_kernel, dim3((unsigned)(waves / 4)), dim3(256), 0, s, sigma, g, thr, (uint32_t)mesh_points(g),
-                     flags, cases, wave_v, wave_t);
+                     kept, flags, cases, wave_v, wave_t);
   return hipGetLastError();
 }
 

@@ -23,8 +23,12 @@ size_t mesh_scan_scratch(size_t n);
 hipError_t launch_mesh_density(const FieldDev& fd, const MeshGrid& g, int use_occ, int brick, float* sigma, hipStream_t s);
 // per point: crossing flags of its +x/+y/+z edge (bits 0..2) and the case of the cell it is the low corner of; per wave of
 // 64 points: vertices (crossing edges) and triangles.  flags / cases: mesh_waves * 64 bytes (the tail is written as 0).
-hipError_t launch_mesh_classify(const float* sigma, const MeshGrid& g, float thr, uint8_t* flags, uint8_t* cases, uint64_t* wave_v,
-                                uint64_t* wave_t, hipStream_t s);
+// kept (launch_mesh_kept's bytes, or nullptr: no mask): a cell that is not kept has case 0, and a crossing edge is flagged only
+// if a cell around it is kept -- the emit passes then need no mask of their own.
+hipError_t launch_mesh_classify(const float* sigma, const MeshGrid& g, float thr, const uint8_t* kept, uint8_t* flags, uint8_t* cases,
+                                uint64_t* wave_v, uint64_t* wave_t, hipStream_t s);
+// kept[point] = 1 iff the point is the low corner of a cell whose eight corners all have valid != 0; mesh_waves * 64 bytes
+hipError_t launch_mesh_kept(const uint8_t* valid, const MeshGrid& g, uint8_t* kept, hipStream_t s);
 // exclusive scan of n uint64 in place; the grand total to *total (device); scratch: mesh_scan_scratch(n) elements
 hipError_t launch_mesh_scan(uint64_t* a, size_t n, uint64_t* scratch, uint64_t* total, hipStream_t s);
 // vertices in edge-id order (3 * point + axis): position and normal (-grad sigma)

@@ -41,7 +41,7 @@ int mesh_grid(prv_ctx* c, const prv_mesh_opts* o, MeshGrid& g) {
 }
 
 struct MeshWork { // the extraction's scratch and its events
-  Buffer sigma, flags, cases, wave_v, wave_t, scratch, totals;
+  Buffer sigma, flags, cases, kept, wave_v, wave_t, scratch, totals;
   // stage brackets: [0, 1] density grid, [1, 2] classify + scans, [3, 4] emit, [4, 5] colours (the readback sits in [2, 3])
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   ~MeshWork() {
@@ -50,17 +50,23 @@ struct MeshWork { // the extraction's scratch and its events
   }
 };
 
-// sigma grid -> mesh; fd != nullptr: vertex colours from that field.  The caller has recorded w.ev[0] and w.ev[1].
-int mesh_extract(prv_ctx* c, const float* sigma, const MeshGrid& g, float thr, const FieldDev* fd, MeshWork& w, prv_mesh** out) {
+// sigma grid -> mesh; fd != nullptr: vertex colours from that field; valid != nullptr: only cells whose eight corners are valid
+// give triangles (prv_marching_cubes_grid_valid).  The caller has recorded w.ev[0] and w.ev[1].
+int mesh_extract(prv_ctx* c, const float* sigma, const uint8_t* valid, const MeshGrid& g, float thr, const FieldDev* fd, MeshWork& w,
+                 prv_mesh** out) {
   const size_t waves = mesh_waves(g);
   int rc;
+  if (valid) {
+    if ((rc = ensure(c, w.kept, waves * 64)) != PRV_OK) return rc;
+    HIPCHK(c, launch_mesh_kept(valid, g, (uint8_t*)w.kept.p, c->stream));
+  }
   if ((rc = ensure(c, w.flags, waves * 64)) != PRV_OK || (rc = ensure(c, w.cases, waves * 64)) != PRV_OK ||
       (rc = ensure(c, w.wave_v, waves * 8)) != PRV_OK || (rc = ensure(c, w.wave_t, waves * 8)) != PRV_OK ||
       (rc = ensure(c, w.scratch, mesh_scan_scratch(waves) * 8)) != PRV_OK || (rc = ensure(c, w.totals, 16)) != PRV_OK)
     return rc;
   uint64_t* tot = (uint64_t*)w.totals.p;
-  HIPCHK(c, launch_mesh_classify(sigma, g, thr, (uint8_t*)w.flags.p, (uint8_t*)w.cases.p, (uint64_t*)w.wave_v.p, (uint64_t*)w.wave_t.p,
-                                 c->stream));
+  HIPCHK(c, launch_mesh_classify(sigma, g, thr, valid ? (const uint8_t*)w.kept.p : nullptr, (uint8_t*)w.flags.p, (uint8_t*)w.cases.p,
+                                 (uint64_t*)w.wave_v.p, (uint64_t*)w.wave_t.p, c->stream));
   HIPCHK(c, launch_mesh_scan((uint64_t*)w.wave_v.p, waves, (uint64_t*)w.scratch.p, tot, c->stream));
   HIPCHK(c, launch_mesh_scan((uint64_t*)w.wave_t.p, waves, (uint64_t*)w.scratch.p, tot + 1, c->stream));
   HIPCHK(c, hipEventRecord(w.ev[2], c->stream));
@@ -352,10 +358,10 @@ int prv_marching_cubes(prv_ctx* c, int slot, const prv_mesh_opts* o, prv_mesh** 
   HIPCHK(c, hipEventRecord(w.ev[0], c->stream));
   if ((rc = density_grid(c, slot, o, g, (float*)w.sigma.p)) != PRV_OK) return rc;
   HIPCHK(c, hipEventRecord(w.ev[1], c->stream));
-  return mesh_extract(c, (const float*)w.sigma.p, g, o->threshold, o->colors ? &c->models[slot].dev : nullptr, w, out);
+  return mesh_extract(c, (const float*)w.sigma.p, nullptr, g, o->threshold, o->colors ? &c->models[slot].dev : nullptr, w, out);
 } catch (...) { return caught(c); }
 
-int prv_marching_cubes_grid(prv_ctx* c, const float* sigma_dev, const prv_mesh_opts* o, prv_mesh** out) try {
+static int marching_cubes_grid(prv_ctx* c, const float* sigma_dev, const uint8_t* valid_dev, const prv_mesh_opts* o, prv_mesh** out) {
   if (!c) return PRV_E_INVALID;
   if (!out) return fail(c, PRV_E_INVALID, "out is NULL");
   *out = nullptr;
@@ -363,13 +369,21 @@ int prv_marching_cubes_grid(prv_ctx* c, const float* sigma_dev, const prv_mesh_o
   MeshGrid g;
   if ((rc = mesh_grid(c, o, g)) != PRV_OK) return rc;
   if (!sigma_dev) return fail(c, PRV_E_INVALID, "sigma_dev is NULL");
-  if ((rc = check_device_ptr(c, sigma_dev, "sigma_dev")) != PRV_OK) return rc;
+  if ((rc = check_device_ptr(c, sigma_dev, "sigma_dev")) != PRV_OK || (rc = check_device_ptr(c, valid_dev, "valid_dev")) != PRV_OK) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   MeshWork w;
   if ((rc = mesh_events(c, w)) != PRV_OK) return rc;
   HIPCHK(c, hipEventRecord(w.ev[0], c->stream));
   HIPCHK(c, hipEventRecord(w.ev[1], c->stream));
-  return mesh_extract(c, sigma_dev, g, o->threshold, nullptr, w, out);
+  return mesh_extract(c, sigma_dev, valid_dev, g, o->threshold, nullptr, w, out);
+}
+
+int prv_marching_cubes_grid(prv_ctx* c, const float* sigma_dev, const prv_mesh_opts* o, prv_mesh** out) try {
+  return marching_cubes_grid(c, sigma_dev, nullptr, o, out);
+} catch (...) { return caught(c); }
+
+int prv_marching_cubes_grid_valid(prv_ctx* c, const float* grid_dev, const uint8_t* valid_dev, const prv_mesh_opts* o, prv_mesh** out) try {
+  return marching_cubes_grid(c, grid_dev, valid_dev, o, out);
 } catch (...) { return caught(c); }
 
 int prv_debug_mesh_stages(prv_ctx* c, float ms[4]) {
