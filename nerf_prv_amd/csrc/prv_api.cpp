@@ -98,9 +98,7 @@ struct prv_ctx {
   std::vector<hipEvent_t> ev_render, ev_march; // start/stop pairs of the current profiling window
   std::vector<hipEvent_t> ev_free;             // recycled events: a profiling window creates none once the pool is warm
   std::vector<float> last_render_ms;           // the render launches of the last closed window, one duration each (prv_profile_render_launches)
-  void* pin = nullptr;                         // pinned host staging of the per-call camera upload (no pageable copy, no stream sync)
-  size_t pin_cap = 0;
-  hipEvent_t pin_ev = nullptr; // recorded after the upload: the staging is rewritten only once that copy has run
+  PinnedStage pin;                             // pinned host staging of the per-call camera upload (stage_views / send_views)
   int blocks_per_cu = -1; // persistent render blocks per CU (PRV_BLOCKS_PER_CU); -1 = by table and image size, see render_blocks
   int cell_cache = -1;    // render_queue64 per-lane corner cache (PRV_CELL_CACHE=0/1; -1 = by stepping rule and image size, see render_policy)
   std::vector<prv_handle*> handles;          // the live handles of this context (made inert by prv_destroy)
@@ -329,10 +327,14 @@ int check_model(prv_ctx* c, int slot) {
   return PRV_OK;
 }
 
+int check_image_size(prv_ctx* c, int W, int H) {
+  if (W < 1 || H < 1 || W > 16384 || H > 16384) return fail(c, PRV_E_INVALID, "bad image size %dx%d", W, H);
+  return PRV_OK;
+}
+
 int check_opts(prv_ctx* c, const prv_render_opts* o) {
   if (!o) return fail(c, PRV_E_INVALID, "render options are NULL");
-  if (o->width < 1 || o->height < 1 || o->width > 16384 || o->height > 16384)
-    return fail(c, PRV_E_INVALID, "bad image size %dx%d", o->width, o->height);
+  if (check_image_size(c, o->width, o->height) != PRV_OK) return PRV_E_INVALID;
   if (o->step_mode != PRV_STEP_FIXED_S && o->step_mode != PRV_STEP_NGP)
     return fail(c, PRV_E_INVALID, "step_mode must be PRV_STEP_FIXED_S (0) or PRV_STEP_NGP (1), got %d", o->step_mode);
   if (o->step_mode == PRV_STEP_FIXED_S && (o->samples_per_ray < 1 || o->samples_per_ray > kMaxSamples))
@@ -483,41 +485,48 @@ OccBox union_box(const prv_ctx* c, const int* slots, int E) {
   return any ? u : OccBox{};
 }
 
-// The cameras of a render call, uploaded per call (tiny): built with their cull rectangles against `box` in pinned memory
-// and sent with one asynchronous copy to c->view_ids = {cams[n_views], ids[n_views] = 0, 1, ...}.  The staging is rewritten
-// only once the previous upload has run (pin_ev).
+// The cameras of a call that takes a camera set and a view list, uploaded per call (tiny).  stage_views builds them in the
+// context's pinned staging (with their cull rectangles against `box`; a null box leaves them as gather_cams does); send_views
+// sends {cams[n_views], ids[n_views] = 0, 1, ...} with one asynchronous copy to c->view_ids, which nothing else touches.  The
+// staging guards itself (PinnedStage): no caller waits for the stream.  upload_views is the two in a row; they are apart for the
+// callers that refuse a lens (on Upload::cams) and allocate buffers of their own in between, so that a bad view id still wins
+// over a refused lens and that over a failed allocation.  Nothing else is staged between a stage_views and its send_views.
 struct Upload {
-  const CamDev* cams; // the pinned host copy
-  const CamDev* cams_dev;
+  const CamDev* cams; // the pinned host copy, valid until the next stage_views
+  int n_views;
+  const CamDev* cams_dev; // (send_views)
   const int* ids_dev;
 };
-int upload_views(prv_ctx* c, const prv_camset* cs, const int* view_ids, int n_views, int W, int H, const OccBox& box, Upload& up) {
-  const size_t up_bytes = (size_t)n_views * (sizeof(CamDev) + sizeof(int));
-  if (c->pin_cap < up_bytes) {
-    if (c->pin_ev) HIPCHK(c, hipEventSynchronize(c->pin_ev));
-    if (c->pin) (void)hipHostFree(c->pin);
-    c->pin = nullptr;
-    c->pin_cap = 0;
-    HIPCHK(c, hipHostMalloc(&c->pin, std::max<size_t>(up_bytes, 8192), hipHostMallocDefault));
-    c->pin_cap = std::max<size_t>(up_bytes, 8192);
-  }
-  if (!c->pin_ev) HIPCHK(c, hipEventCreateWithFlags(&c->pin_ev, hipEventDisableTiming));
-  else HIPCHK(c, hipEventSynchronize(c->pin_ev));
-  CamDev* cams = (CamDev*)c->pin;
-  int* ids = (int*)((char*)c->pin + (size_t)n_views * sizeof(CamDev));
+size_t upload_bytes(int n_views) { return (size_t)n_views * (sizeof(CamDev) + sizeof(int)); }
+int stage_views(prv_ctx* c, const prv_camset* cs, const int* view_ids, int n_views, int W, int H, const OccBox* box, Upload& up) {
+  const char* call = "";
+  void* pin = nullptr;
+  const hipError_t e = c->pin.acquire(upload_bytes(n_views), &pin, &call);
+  if (e != hipSuccess) return fail(c, PRV_E_HIP, "%s failed: %s", call, hipGetErrorString(e));
+  CamDev* cams = (CamDev*)pin;
+  int* ids = (int*)(cams + n_views);
   int rc;
   if ((rc = gather_cams(c, cs, view_ids, n_views, W, H, cams)) != PRV_OK) return rc;
   for (int i = 0; i < n_views; i++) {
-    set_cull_rect(cams[i], box, W, H);
+    if (box) set_cull_rect(cams[i], *box, W, H);
     ids[i] = i;
   }
-  if ((rc = ensure(c, c->view_ids, up_bytes)) != PRV_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->view_ids.p, c->pin, up_bytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipEventRecord(c->pin_ev, c->stream));
-  up.cams = cams;
-  up.cams_dev = (const CamDev*)c->view_ids.p;
-  up.ids_dev = (const int*)((char*)c->view_ids.p + (size_t)n_views * sizeof(CamDev));
+  up = Upload{cams, n_views, nullptr, nullptr};
   return PRV_OK;
+}
+int send_views(prv_ctx* c, Upload& up) {
+  int rc;
+  if ((rc = ensure(c, c->view_ids, upload_bytes(up.n_views))) != PRV_OK) return rc;
+  const char* call = "";
+  const hipError_t e = c->pin.send(c->view_ids.p, upload_bytes(up.n_views), c->stream, &call);
+  if (e != hipSuccess) return fail(c, PRV_E_HIP, "%s failed: %s", call, hipGetErrorString(e));
+  up.cams_dev = (const CamDev*)c->view_ids.p;
+  up.ids_dev = (const int*)(up.cams_dev + up.n_views);
+  return PRV_OK;
+}
+int upload_views(prv_ctx* c, const prv_camset* cs, const int* view_ids, int n_views, int W, int H, const OccBox* box, Upload& up) {
+  const int rc = stage_views(c, cs, view_ids, n_views, W, H, box, up);
+  return rc != PRV_OK ? rc : send_views(c, up);
 }
 
 constexpr int kSubRegions = 8, kMaxSegments = 8 * kSubRegions; // queue regions (<= 8: one per XCD) x their sub-regions
@@ -703,8 +712,9 @@ struct RenderTargets {
 };
 
 // The render of n_views views into t.  Views are dealt to the queue in batches so the queue stays within queue_budget bytes.
+// *up_out (n_views > 0): the cameras the call rendered with, for a caller that reads t through their cull rectangles.
 int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids, int n_views, const prv_render_opts* o,
-                 const RenderTargets& t) {
+                 const RenderTargets& t, Upload* up_out = nullptr) {
   const bool colour = t.mode == kRenderColour || t.mode == kRenderDepth; // the launch writes an RGBA image
   const bool surface = t.mode == kRenderSurface, term = t.mode == kRenderTermination;
   const bool depth = t.mode == kRenderDepth || t.mode == kRenderFootprint || surface;
@@ -722,8 +732,10 @@ int render_views(prv_ctx* c, int slot, const prv_camset* cs, const int* view_ids
     if (t.zero_stats) HIPCHK(c, hipMemsetAsync(stat, 0, kCountersBytes - kStatOffset, c->stream));
     return PRV_OK;
   }
+  const OccBox box = box_of(m);
   Upload up;
-  if ((rc = upload_views(c, cs, view_ids, n_views, W, H, box_of(m), up)) != PRV_OK) return rc;
+  if ((rc = upload_views(c, cs, view_ids, n_views, W, H, &box, up)) != PRV_OK) return rc;
+  if (up_out) *up_out = up;
 
   // all spp sub-samples of a batch of views go through ONE march + ONE render launch: sub-sample k of
   // view v is image (k*nb + v) of a staging buffer, reduced over k in order afterwards (spp = 1 renders
@@ -907,7 +919,7 @@ int render_ensemble_ngp(prv_ctx* c, const int* slots, int E, const prv_camset* c
   // the members' union box: clip range and cull rectangles (conservative for every member)
   const OccBox box = union_box(c, slots, E);
   Upload up;
-  if ((rc = upload_views(c, cs, view_ids, n_views, W, H, box, up)) != PRV_OK) return rc;
+  if ((rc = upload_views(c, cs, view_ids, n_views, W, H, &box, up)) != PRV_OK) return rc;
 
   // the members' occupancy, interleaved: byte c = bit c of every member's bitfield (fine grid, then the dilated coarse one)
   const bool have_coarse = m0.dev.occ_coarse != nullptr;
@@ -1091,8 +1103,7 @@ void prv_destroy(prv_ctx* c) {
   for (hipEvent_t e : c->ev_render) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_march) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_free) (void)hipEventDestroy(e);
-  if (c->pin) (void)hipHostFree(c->pin);
-  if (c->pin_ev) (void)hipEventDestroy(c->pin_ev);
+  c->pin.release();
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
   g_live_contexts.fetch_sub(1);
@@ -1677,12 +1688,9 @@ int prv_first_hit(prv_ctx* c, int slot, const prv_camset* cs, const int* view_id
   if (n_views == 0) return PRV_OK;
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = check_device_ptr(c, out, "out_voxel_dev")) != PRV_OK) return rc;
-  std::vector<CamDev> cams(n_views);
-  if ((rc = gather_cams(c, cs, view_ids, n_views, W, H, cams.data())) != PRV_OK) return rc;
-  if ((rc = ensure(c, c->view_ids, (size_t)n_views * (sizeof(CamDev) + sizeof(int)))) != PRV_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->view_ids.p, cams.data(), (size_t)n_views * sizeof(CamDev), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, launch_first_hit(c->models[slot].dev, (const CamDev*)c->view_ids.p, n_views, W, H, max_range, out, c->stream));
+  Upload up;
+  if ((rc = upload_views(c, cs, view_ids, n_views, W, H, nullptr, up)) != PRV_OK) return rc;
+  HIPCHK(c, launch_first_hit(c->models[slot].dev, up.cams_dev, n_views, W, H, max_range, out, c->stream));
   return PRV_OK;
 } catch (...) { return caught(c); }
 
@@ -1699,14 +1707,11 @@ int prv_splat_points(prv_ctx* c, const float* xyz, const uint8_t* rgb, size_t n,
   if ((rc = check_device_ptr(c, xyz, "xyz_dev")) != PRV_OK || (rc = check_device_ptr(c, rgb, "rgb_dev")) != PRV_OK ||
       (rc = check_device_ptr(c, out, "out_rgba8_dev")) != PRV_OK)
     return rc;
-  std::vector<CamDev> cams(n_views);
-  if ((rc = gather_cams(c, cs, view_ids, n_views, W, H, cams.data())) != PRV_OK) return rc;
-  if ((rc = ensure(c, c->view_ids, (size_t)n_views * (sizeof(CamDev) + sizeof(int)))) != PRV_OK) return rc;
+  Upload up;
+  if ((rc = upload_views(c, cs, view_ids, n_views, W, H, nullptr, up)) != PRV_OK) return rc;
   if ((rc = ensure(c, c->stage, (size_t)n_views * W * H * 8)) != PRV_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->view_ids.p, cams.data(), (size_t)n_views * sizeof(CamDev), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
   const float off[3] = {(float)(offset ? offset[0] : 0.5), (float)(offset ? offset[1] : 0.5), (float)(offset ? offset[2] : 0.5)};
-  HIPCHK(c, launch_splat_points(xyz, rgb, n, (float)scale, off, (const CamDev*)c->view_ids.p, n_views, W, H, point_size,
+  HIPCHK(c, launch_splat_points(xyz, rgb, n, (float)scale, off, up.cams_dev, n_views, W, H, point_size,
                                 flip180, (unsigned long long*)c->stage.p, (uint32_t*)out, c->stream));
   return PRV_OK;
 } catch (...) { return caught(c); }
@@ -1993,14 +1998,15 @@ int prv_score_views(prv_ctx* c, int method, const int* model_slots, int n_models
     if (n_views && (rc = score_ensemble_dev(c, method, imgs, n_models, n_views, npix, rec)) != PRV_OK) return rc;
   } else {
     // the image is a private temporary of the round: only the tiles inside each view's cull rectangle are rendered and
-    // the score reads it through the same rectangles (view i of this call = camera i of the upload in c->view_ids)
+    // the score reads it through the same rectangles (view i of this call = camera i of the render's upload)
     const bool priv = o->spp == 1;
     RenderTargets t;
     t.rgba = (float*)c->img_f32.p;
     t.private_output = priv;
-    if ((rc = render_views(c, model_slots[0], cs, view_ids, n_views, o, t)) != PRV_OK) return rc;
+    Upload up{};
+    if ((rc = render_views(c, model_slots[0], cs, view_ids, n_views, o, t, &up)) != PRV_OK) return rc;
     if (n_views && (rc = score_psnr_dev(c, (const float*)c->img_f32.p, gt, n_views, npix, o->background, c->coverage_weight, rec,
-                                        priv ? (const CamDev*)c->view_ids.p : nullptr, o->width)) != PRV_OK)
+                                        priv ? up.cams_dev : nullptr, o->width)) != PRV_OK)
       return rc;
   }
   if (rec_dev && n_views)

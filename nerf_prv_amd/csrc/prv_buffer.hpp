@@ -2,6 +2,7 @@
 //   Buffer      a block of device memory, freed by its destructor;
 //   BufferPool  the blocks destroyed trainers leave to their context, taken again by size;
 //   ensure      the grow-only allocation every workspace goes through;
+//   PinnedStage the pinned host block a context builds its per-call camera upload in, and the event that guards it;
 //   Handle      the base of every object a context hands out (trainer, communicator, mesh, index, coverage handle): the
 //               context keeps one list of them and makes them inert when it goes first.
 // Host code only, and nothing of HIP but the runtime calls made here: tests/test_buffers_host.py compiles this file into a
@@ -118,6 +119,88 @@ inline hipError_t ensure(Buffer& b, size_t bytes, hipStream_t stream, BufferPool
   g_live_buffer_bytes.fetch_add(bytes);
   return hipSuccess;
 }
+
+// The pinned host block that small per-call uploads are built in and sent from: no pageable copy, and the host never waits
+// for the stream.  What makes that safe is in these two functions and nowhere else: send() records an event behind its copy,
+// and acquire() waits for that event before it hands the block out to be rewritten (or frees it to grow).  An acquire that no
+// send follows -- the caller returned early -- leaves nothing to wait for.  *call names the runtime call that failed, as the
+// error text of the ABI spells it.
+struct PinnedStage {
+  static constexpr size_t kMinBytes = 8192;
+  void* p = nullptr;
+  size_t cap = 0;
+  hipEvent_t ev = nullptr; // created on first use, timing disabled
+  bool in_flight = false;  // ev was recorded behind a copy out of p and has not been waited for since
+
+  PinnedStage() = default;
+  PinnedStage(const PinnedStage&) = delete;
+  PinnedStage& operator=(const PinnedStage&) = delete;
+  PinnedStage(PinnedStage&& o) noexcept : p(o.p), cap(o.cap), ev(o.ev), in_flight(o.in_flight) { o.forget(); }
+  PinnedStage& operator=(PinnedStage&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p, cap = o.cap, ev = o.ev, in_flight = o.in_flight;
+      o.forget();
+    }
+    return *this;
+  }
+  ~PinnedStage() { release(); }
+
+  // *out = the block, at least `bytes`, free to be written.  After a refused allocation the stage is empty and may be used again
+  hipError_t acquire(size_t bytes, void** out, const char** call) {
+    hipError_t e;
+    if (in_flight) {
+      *call = "hipEventSynchronize(c->pin_ev)";
+      if ((e = hipEventSynchronize(ev)) != hipSuccess) return e;
+      in_flight = false;
+    }
+    if (cap < bytes) {
+      if (p) (void)hipHostFree(p);
+      p = nullptr;
+      cap = 0;
+      const size_t want = std::max(bytes, kMinBytes);
+      *call = "hipHostMalloc(&c->pin, std::max<size_t>(up_bytes, 8192), hipHostMallocDefault)";
+      if ((e = hipHostMalloc(&p, want, hipHostMallocDefault)) != hipSuccess) {
+        p = nullptr;
+        return e;
+      }
+      cap = want;
+    }
+    if (!ev) {
+      *call = "hipEventCreateWithFlags(&c->pin_ev, hipEventDisableTiming)";
+      if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) {
+        ev = nullptr;
+        return e;
+      }
+    }
+    *out = p;
+    return hipSuccess;
+  }
+  // the first `bytes` of the block to `dst` on `stream`, one asynchronous copy; the block is not to be written before the next acquire
+  hipError_t send(void* dst, size_t bytes, hipStream_t stream, const char** call) {
+    *call = "hipMemcpyAsync(c->view_ids.p, c->pin, up_bytes, hipMemcpyHostToDevice, c->stream)";
+    hipError_t e = hipMemcpyAsync(dst, p, bytes, hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) return e;
+    *call = "hipEventRecord(c->pin_ev, c->stream)";
+    if ((e = hipEventRecord(ev, stream)) == hipSuccess) in_flight = true;
+    return e;
+  }
+  // frees the block and the event without waiting: the owner has drained the stream (prv_destroy does, first of all).  An empty
+  // stage makes no runtime call
+  void release() {
+    if (p) (void)hipHostFree(p);
+    if (ev) (void)hipEventDestroy(ev);
+    forget();
+  }
+
+private:
+  void forget() {
+    p = nullptr;
+    cap = 0;
+    ev = nullptr;
+    in_flight = false;
+  }
+};
 
 // An object a context hands out.  Ctx has `device`, `stream` and `std::vector<Handle<Ctx>*> handles`.  A handle is in its
 // context's list from construction to destruction, so a create function that returns early has nothing to undo.

@@ -30,8 +30,8 @@ int coverage_check_opts(prv_ctx* c, const prv_coverage_opts* o) {
 }
 
 // stages A and B, batch by batch, then the per-view counts and the union's.  occluder != nullptr: stage A rasterises that mesh
-// (prv_raster_api.inc) and stage B lets an empty pixel pass; nullptr: the points occlude each other
-int coverage_build(prv_ctx* c, prv_coverage* x, const float* xyz, const prv_mesh* occluder, const std::vector<CamDev>& cams, int W, int H,
+// (prv_raster_api.inc) and stage B lets an empty pixel pass; nullptr: the points occlude each other.  up: staged by the caller
+int coverage_build(prv_ctx* c, prv_coverage* x, const float* xyz, const prv_mesh* occluder, Upload& up, int W, int H,
                    const prv_coverage_opts& o, float* depth_out) {
   int rc;
   const int V = x->n_views;
@@ -41,9 +41,7 @@ int coverage_build(prv_ctx* c, prv_coverage* x, const float* xyz, const prv_mesh
   RasterWork raster;
   if ((rc = ensure(c, z, (size_t)per_batch * npix * 4)) != PRV_OK) return rc;
   if (occluder && (rc = raster_begin(c, raster, occluder, per_batch)) != PRV_OK) return rc;
-  if ((rc = ensure(c, c->view_ids, (size_t)V * (sizeof(CamDev) + sizeof(int)))) != PRV_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->view_ids.p, cams.data(), (size_t)V * sizeof(CamDev), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream)); // (the host vector may go away)
+  if ((rc = send_views(c, up)) != PRV_OK) return rc;
   if (x->words > 0) {
     if ((rc = ensure(c, x->bits, (size_t)V * x->words * 8)) != PRV_OK || (rc = ensure(c, x->covered, x->words * 8)) != PRV_OK) return rc;
   }
@@ -53,7 +51,7 @@ int coverage_build(prv_ctx* c, prv_coverage* x, const float* xyz, const prv_mesh
   unsigned long long* bits = (unsigned long long*)x->bits.p;
   for (int v0 = 0; v0 < V; v0 += per_batch) {
     const int nb = std::min(per_batch, V - v0);
-    const CamDev* bc = (const CamDev*)c->view_ids.p + v0;
+    const CamDev* bc = up.cams_dev + v0;
     if (occluder) {
       if ((rc = raster_fill(c, raster, occluder, bc, nb, W, H, zbuf)) != PRV_OK) return rc;
       HIPCHK(c, launch_raster_visible(xyz, (size_t)x->n, bc, nb, W, H, zbuf, tol1, bits + (size_t)v0 * x->words, x->words, c->stream));
@@ -85,19 +83,19 @@ int coverage_create(prv_ctx* c, const float* xyz, uint64_t n, const prv_mesh* oc
                     int width, int height, const prv_coverage_opts& o, float* depth_out, prv_coverage** out) {
   int rc;
   if (!cs || n_views < 1) return fail(c, PRV_E_INVALID, "bad camset / view count");
-  if (width < 1 || height < 1 || width > 16384 || height > 16384) return fail(c, PRV_E_INVALID, "bad image size %dx%d", width, height);
+  if ((rc = check_image_size(c, width, height)) != PRV_OK) return rc;
   if (n > kCoverageMaxPoints) return fail(c, PRV_E_INVALID, "%llu points exceed 2^31", (unsigned long long)n);
   if (n > 0 && !xyz) return fail(c, PRV_E_INVALID, "xyz_dev is NULL");
   HIPCHK(c, hipSetDevice(c->device));
   if ((n > 0 && (rc = check_device_ptr(c, xyz, "xyz_dev")) != PRV_OK) || (rc = check_device_ptr(c, depth_out, "depth_out_dev")) != PRV_OK) return rc;
-  std::vector<CamDev> cams((size_t)n_views);
-  if ((rc = gather_cams(c, cs, view_ids, n_views, width, height, cams.data())) != PRV_OK) return rc;
-  if (occluder && (rc = raster_refuse_lenses(c, cams)) != PRV_OK) return rc;
+  Upload up; // staged here, sent by coverage_build: a bad view id or a lens is reported before any allocation can fail
+  if ((rc = stage_views(c, cs, view_ids, n_views, width, height, nullptr, up)) != PRV_OK) return rc;
+  if (occluder && (rc = raster_refuse_lenses(c, up.cams, n_views)) != PRV_OK) return rc;
   std::unique_ptr<prv_coverage> x(new prv_coverage(c));
   x->n = n;
   x->n_views = n_views;
   x->words = (size_t)((n + 63) / 64);
-  if ((rc = coverage_build(c, x.get(), xyz, occluder, cams, width, height, o, depth_out)) != PRV_OK) {
+  if ((rc = coverage_build(c, x.get(), xyz, occluder, up, width, height, o, depth_out)) != PRV_OK) {
     (void)hipStreamSynchronize(c->stream); // (before the handle's buffers go)
     return rc;
   }

@@ -12,10 +12,10 @@ int zbuf_views_per_batch(int n_views, size_t npix, size_t key_bytes = 4) {
   return (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)n_views, (size_t)kCoverageMaxBatch), budget / (npix * key_bytes)));
 }
 
-int raster_refuse_lenses(prv_ctx* c, const std::vector<CamDev>& cams) {
-  for (size_t i = 0; i < cams.size(); i++)
+int raster_refuse_lenses(prv_ctx* c, const CamDev* cams, int n) {
+  for (int i = 0; i < n; i++)
     if (cams[i].lens[0] != 0.0f || cams[i].lens[1] != 0.0f || cams[i].lens[2] != 0.0f || cams[i].lens[3] != 0.0f)
-      return fail(c, PRV_E_INVALID, "view %d of the list has a lens: a mesh is rasterised for pinhole cameras only (a straight edge does not stay straight)", (int)i);
+      return fail(c, PRV_E_INVALID, "view %d of the list has a lens: a mesh is rasterised for pinhole cameras only (a straight edge does not stay straight)", i);
   return PRV_OK;
 }
 
@@ -123,24 +123,22 @@ int prv_mesh_depth(prv_ctx* c, const prv_mesh* m, const prv_camset* cs, const in
   int rc;
   if ((rc = raster_check_mesh(c, m, "mesh")) != PRV_OK) return rc;
   if (!cs || n_views < 1) return fail(c, PRV_E_INVALID, "bad camset / view count");
-  if (width < 1 || height < 1 || width > 16384 || height > 16384) return fail(c, PRV_E_INVALID, "bad image size %dx%d", width, height);
+  if ((rc = check_image_size(c, width, height)) != PRV_OK) return rc;
   if (!depth_out) return fail(c, PRV_E_INVALID, "depth_out_dev is NULL");
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = check_device_ptr(c, depth_out, "depth_out_dev")) != PRV_OK) return rc;
-  std::vector<CamDev> cams((size_t)n_views);
-  if ((rc = gather_cams(c, cs, view_ids, n_views, width, height, cams.data())) != PRV_OK || (rc = raster_refuse_lenses(c, cams)) != PRV_OK) return rc;
+  Upload up; // staged here, sent below: a bad view id or a lens is reported before any allocation can fail
+  if ((rc = stage_views(c, cs, view_ids, n_views, width, height, nullptr, up)) != PRV_OK || (rc = raster_refuse_lenses(c, up.cams, n_views)) != PRV_OK) return rc;
   const size_t npix = (size_t)width * (size_t)height;
   const int per_batch = zbuf_views_per_batch(n_views, npix);
   Buffer z;
   RasterWork w;
   if ((rc = ensure(c, z, (size_t)per_batch * npix * 4)) != PRV_OK || (rc = raster_begin(c, w, m, per_batch)) != PRV_OK) return rc;
-  if ((rc = ensure(c, c->view_ids, (size_t)n_views * (sizeof(CamDev) + sizeof(int)))) != PRV_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->view_ids.p, cams.data(), (size_t)n_views * sizeof(CamDev), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream)); // (the host vector may go away)
+  if ((rc = send_views(c, up)) != PRV_OK) return rc;
   uint32_t* zbuf = (uint32_t*)z.p;
   for (int v0 = 0; v0 < n_views; v0 += per_batch) {
     const int nb = std::min(per_batch, n_views - v0);
-    if ((rc = raster_fill(c, w, m, (const CamDev*)c->view_ids.p + v0, nb, width, height, zbuf)) != PRV_OK) break;
+    if ((rc = raster_fill(c, w, m, up.cams_dev + v0, nb, width, height, zbuf)) != PRV_OK) break;
     hipError_t e = launch_coverage_resolve(zbuf, (size_t)nb * npix, depth_out + (size_t)v0 * npix, c->stream);
     if (e != hipSuccess) {
       rc = fail(c, PRV_E_HIP, "mesh depth failed: %s", hipGetErrorString(e));

@@ -26,27 +26,25 @@ int prv_mesh_render(prv_ctx* c, const prv_mesh* m, const prv_camset* cs, const i
   int rc;
   if ((rc = raster_check_mesh(c, m, "mesh")) != PRV_OK) return rc;
   if (!cs || n_views < 1) return fail(c, PRV_E_INVALID, "bad camset / view count");
-  if (width < 1 || height < 1 || width > 16384 || height > 16384) return fail(c, PRV_E_INVALID, "bad image size %dx%d", width, height);
+  if ((rc = check_image_size(c, width, height)) != PRV_OK) return rc;
   if (!out) return fail(c, PRV_E_INVALID, "out_rgba8_dev is NULL");
   if (!m->colors) return fail(c, PRV_E_INVALID, "the mesh has no colours: call prv_mesh_set_colors first (or extract it with colours)");
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = check_device_ptr(c, out, "out_rgba8_dev")) != PRV_OK || (depth_out && (rc = check_device_ptr(c, depth_out, "depth_out_dev")) != PRV_OK) ||
       (tri_out && (rc = check_device_ptr(c, tri_out, "tri_out_dev")) != PRV_OK))
     return rc;
-  std::vector<CamDev> cams((size_t)n_views);
-  if ((rc = gather_cams(c, cs, view_ids, n_views, width, height, cams.data())) != PRV_OK || (rc = raster_refuse_lenses(c, cams)) != PRV_OK) return rc;
+  Upload up; // staged here, sent below: a bad view id or a lens is reported before any allocation can fail
+  if ((rc = stage_views(c, cs, view_ids, n_views, width, height, nullptr, up)) != PRV_OK || (rc = raster_refuse_lenses(c, up.cams, n_views)) != PRV_OK) return rc;
   const size_t npix = (size_t)width * (size_t)height;
   const int per_batch = zbuf_views_per_batch(n_views, npix, 8);
   Buffer z;
   RasterWork w;
   if ((rc = ensure(c, z, (size_t)per_batch * npix * 8)) != PRV_OK || (rc = raster_begin(c, w, m, per_batch)) != PRV_OK) return rc;
-  if ((rc = ensure(c, c->view_ids, (size_t)n_views * (sizeof(CamDev) + sizeof(int)))) != PRV_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->view_ids.p, cams.data(), (size_t)n_views * sizeof(CamDev), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream)); // (the host vector may go away)
+  if ((rc = send_views(c, up)) != PRV_OK) return rc;
   unsigned long long* keys = (unsigned long long*)z.p;
   for (int v0 = 0; v0 < n_views; v0 += per_batch) {
     const int nb = std::min(per_batch, n_views - v0);
-    const CamDev* bc = (const CamDev*)c->view_ids.p + v0;
+    const CamDev* bc = up.cams_dev + v0;
     if ((rc = raster_fill(c, w, m, bc, nb, width, height, keys)) != PRV_OK) break;
     hipError_t e = launch_raster_shade((const float*)m->xyz.p, (const uint32_t*)m->tri.p, (const uint8_t*)m->rgb.p, bc, nb, width, height, keys,
                                        flip180, (uint32_t*)out + (size_t)v0 * npix, depth_out ? depth_out + (size_t)v0 * npix : nullptr,

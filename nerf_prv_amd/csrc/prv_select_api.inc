@@ -18,10 +18,8 @@ int select_rounds(prv_ctx* c, const prv_camset* cs, const int* view_ids, int n_v
   int rc;
   const size_t npix = (size_t)W * (size_t)H, n = npix * (size_t)n_views;
   if (n > ((size_t)1 << 31)) return fail(c, PRV_E_INVALID, "%d views of %dx%d pixels: more than 2^31 pixels", n_views, W, H);
-  std::vector<CamDev> cams((size_t)n_views);
-  if ((rc = gather_cams(c, cs, view_ids, n_views, W, H, cams.data())) != PRV_OK) return rc;
-  if ((rc = ensure(c, c->view_ids, (size_t)n_views * (sizeof(CamDev) + sizeof(int)))) != PRV_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->view_ids.p, cams.data(), (size_t)n_views * sizeof(CamDev), hipMemcpyHostToDevice, c->stream));
+  Upload up;
+  if ((rc = upload_views(c, cs, view_ids, n_views, W, H, nullptr, up)) != PRV_OK) return rc;
   if (!voxel_dev) {
     if ((rc = ensure(c, c->sel_voxel, n * 4)) != PRV_OK) return rc;
     voxel_dev = (uint32_t*)c->sel_voxel.p;
@@ -40,7 +38,7 @@ int select_rounds(prv_ctx* c, const prv_camset* cs, const int* view_ids, int n_v
   HIPCHK(c, hipMemsetAsync(done, 0, (size_t)n_views * 4, c->stream));
   SelectFootprintParams fp;
   memset(&fp, 0, sizeof(fp));
-  fp.cams = (const CamDev*)c->view_ids.p;
+  fp.cams = up.cams_dev;
   fp.W = W;
   fp.H = H;
   fp.n_views = n_views;
@@ -90,7 +88,7 @@ int prv_select_from_images(prv_ctx* c, const prv_camset* cs, const int* view_ids
   if ((rc = select_check_opts(c, so, n_views)) != PRV_OK) return rc;
   if (!c) return fail(nullptr, PRV_E_INVALID, "the context is NULL");
   if (!cs || n_views < 0) return fail(c, PRV_E_INVALID, "bad camset / view count");
-  if (width < 1 || height < 1 || width > 16384 || height > 16384) return fail(c, PRV_E_INVALID, "bad image size %dx%d", width, height);
+  if ((rc = check_image_size(c, width, height)) != PRV_OK) return rc;
   if (!entropy_dev || !alpha_dev || !depth_dev || !chosen_out) return fail(c, PRV_E_INVALID, "the entropy, alpha and depth planes and chosen_out are required");
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = check_device_ptr(c, entropy_dev, "entropy_dev")) != PRV_OK || (rc = check_device_ptr(c, alpha_dev, "alpha_dev")) != PRV_OK ||

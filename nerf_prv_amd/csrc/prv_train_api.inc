@@ -465,7 +465,7 @@ int prv_train_create(prv_ctx* c, int slot, const prv_camset* cs, const uint8_t* 
   int rc = check_model(c, slot);
   if (rc != PRV_OK) return rc;
   if (!cs || cs->cams.empty() || !images_rgba8_dev || !o) return fail(c, PRV_E_INVALID, "NULL / empty training data");
-  if (width < 1 || height < 1 || width > 16384 || height > 16384) return fail(c, PRV_E_INVALID, "bad image size %dx%d", width, height);
+  if ((rc = check_image_size(c, width, height)) != PRV_OK) return rc;
   if (o->n_rays < 1 || o->n_rays > (1 << 22)) return fail(c, PRV_E_INVALID, "n_rays must be in [1, 2^22], got %d", o->n_rays);
   if (o->step_mode != PRV_STEP_FIXED_S && o->step_mode != PRV_STEP_NGP) return fail(c, PRV_E_INVALID, "step_mode must be PRV_STEP_FIXED_S or PRV_STEP_NGP, got %d", o->step_mode);
   const int max_s = o->step_mode == PRV_STEP_NGP ? prv::kMaxTrainSteps : prv::kMaxTrainSamples;

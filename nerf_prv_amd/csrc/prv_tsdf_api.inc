@@ -87,7 +87,7 @@ int prv_tsdf_integrate(prv_tsdf* t, const prv_camset* cs, const int* view_ids, i
   if (rc != PRV_OK) return rc;
   prv_ctx* c = t->ctx;
   if (!cs || n_views < 0) return fail(c, PRV_E_INVALID, "bad camset / view count");
-  if (width < 1 || height < 1 || width > 16384 || height > 16384) return fail(c, PRV_E_INVALID, "bad image size %dx%d", width, height);
+  if ((rc = check_image_size(c, width, height)) != PRV_OK) return rc;
   if (n_views == 0) return PRV_OK;
   if (!depth) return fail(c, PRV_E_INVALID, "depth_dev is NULL");
   HIPCHK(c, hipSetDevice(c->device));

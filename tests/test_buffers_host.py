@@ -1,7 +1,8 @@
 """The C ABI's owners of device memory and of context-owned handles (nerf_prv_amd/csrc/prv_buffer.hpp) against a counting
 stub of the runtime calls they make: every block is freed exactly once -- at scope exit, across moves, when a buffer grows,
 on the out-of-memory path, through the parked pool, whichever of a handle and its context goes first, and on an early return
-out of a create function.  Host code only: a stand-alone program built with the address and undefined-behaviour sanitizers."""
+out of a create function.  The pinned upload staging (PinnedStage) likewise, and its protocol call for call: it waits for its
+event exactly when a copy out of it may be in flight, and before it frees.  Host code only: a stand-alone program built with the address and undefined-behaviour sanitizers."""
 import os
 import subprocess
 
@@ -12,13 +13,16 @@ PROGRAM = r"""
 #include "prv_buffer.hpp"
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <set>
 #include <string>
 using namespace prv;
 
 // ---- the counting stub: every block is a heap block, so a double free or a leak is also the sanitizer's finding.  The log
-// holds one letter per call: M hipMalloc, m a refused hipMalloc, F hipFree, S hipStreamSynchronize, D hipSetDevice, L hipGetLastError
+// holds one letter per call: M hipMalloc, m a refused hipMalloc, F hipFree, S hipStreamSynchronize, D hipSetDevice, L hipGetLastError,
+// H hipHostMalloc, h a refused hipHostMalloc, f hipHostFree, E hipEventCreateWithFlags, W hipEventSynchronize, R hipEventRecord,
+// X hipEventDestroy, C hipMemcpyAsync.  A pinned block has its real size and the copy is made, so the sanitizer sees both ends
 static std::string calls;
 static std::set<void*> live;
 static int n_malloc, n_free, refuse_next;
@@ -49,6 +53,58 @@ hipError_t hipStreamSynchronize(hipStream_t s) { if (s != STREAM) exit(4); call(
 hipError_t hipSetDevice(int d) { if (d != 3) exit(4); call('D'); return hipSuccess; }
 hipError_t hipGetLastError(void) { call('L'); return hipSuccess; }
 }
+struct Event { bool recorded = false; };
+static std::set<void*> pinned;
+static std::set<Event*> events;
+static int refuse_host_next;
+extern "C" {
+hipError_t hipHostMalloc(void** p, size_t bytes, unsigned int flags) {
+  if (flags != hipHostMallocDefault) exit(4);
+  if (refuse_host_next > 0) { refuse_host_next--; call('h'); *p = nullptr; return hipErrorOutOfMemory; }
+  call('H');
+  *p = malloc(bytes);
+  pinned.insert(*p);
+  return hipSuccess;
+}
+hipError_t hipHostFree(void* p) {
+  call('f');
+  if (!pinned.erase(p)) { printf("pinned block freed twice, or never allocated: %p\n", p); exit(3); }
+  free(p);
+  return hipSuccess;
+}
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned flags) {
+  if (flags != hipEventDisableTiming) exit(4);
+  call('E');
+  Event* ev = new Event();
+  events.insert(ev);
+  *e = (hipEvent_t)ev;
+  return hipSuccess;
+}
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
+  if (s != STREAM || !events.count((Event*)e)) exit(4);
+  call('R');
+  ((Event*)e)->recorded = true;
+  return hipSuccess;
+}
+hipError_t hipEventSynchronize(hipEvent_t e) {
+  if (!events.count((Event*)e)) exit(4);
+  if (!((Event*)e)->recorded) { printf("waited for an event that was never recorded\n"); exit(6); }
+  call('W');
+  return hipSuccess;
+}
+hipError_t hipEventDestroy(hipEvent_t e) {
+  call('X');
+  if (!events.erase((Event*)e)) { printf("event destroyed twice, or never created\n"); exit(3); }
+  delete (Event*)e;
+  return hipSuccess;
+}
+hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+  if (s != STREAM || kind != hipMemcpyHostToDevice || !pinned.count((void*)src)) exit(4);
+  call('C');
+  memcpy(dst, src, bytes);
+  return hipSuccess;
+}
+}
 
 #define CHECK(c) do { if (!(c)) { printf("line %d: %s (calls so far: %s)\n", __LINE__, #c, calls.c_str()); exit(1); } } while (0)
 // the calls since the last look, exactly
@@ -60,9 +116,11 @@ struct Ctx { // what prv_ctx is to this header
   hipStream_t stream = STREAM;
   std::vector<Handle<Ctx>*> handles;
   BufferPool parked;
-  void end() { // prv_destroy's steps 2 and 3
+  PinnedStage pin;
+  void end() { // prv_destroy's steps 2, 3 and 4
     detach_handles(this);
     parked.clear();
+    pin.release();
   }
 };
 static hipError_t grow(Ctx& c, Buffer& b, size_t bytes, const char** call_out = nullptr) {
@@ -242,6 +300,69 @@ static void early_return() {
   CHECK(made("FF") && held() == 0);
 }
 
+static hipError_t acquire(PinnedStage& s, size_t bytes, void** p, const char** call_out = nullptr) {
+  const char* call = "";
+  const hipError_t e = s.acquire(bytes, p, &call);
+  if (call_out) *call_out = call;
+  return e;
+}
+static hipError_t send(PinnedStage& s, void* dst, size_t bytes) {
+  const char* call = "";
+  return s.send(dst, bytes, STREAM, &call);
+}
+
+static void pinned_stage() {
+  static char dev[16384];
+  Ctx* c = new Ctx();
+  PinnedStage& s = c->pin;
+  void *p = nullptr, *q = nullptr;
+  CHECK(acquire(s, 100, &p) == hipSuccess && p && s.cap == 8192 && made("HE")); // first use: the block (8192 at the least), the event, no wait
+  memset(p, 1, 8192);
+  CHECK(acquire(s, 8192, &q) == hipSuccess && q == p && made("")); // the caller returned early, nothing was sent: nothing to wait for
+  CHECK(send(s, dev, 100) == hipSuccess && dev[99] == 1 && dev[100] == 0 && made("CR"));
+  CHECK(acquire(s, 8192, &q) == hipSuccess && q == p && made("W")); // after a send: the wait, no allocation
+  CHECK(acquire(s, 1, &q) == hipSuccess && q == p && made(""));      // ... once
+  CHECK(send(s, dev, 8192) == hipSuccess && made("CR"));
+  CHECK(acquire(s, 8193, &p) == hipSuccess && s.cap == 8193 && made("WfH")); // growth in flight: wait, then free, then allocate
+  memset(p, 2, 8193);
+  CHECK(acquire(s, 9000, &p) == hipSuccess && s.cap == 9000 && made("fH")); // growth with nothing in flight
+  CHECK(send(s, dev, 9000) == hipSuccess && made("CR"));
+  refuse_host_next = 1; // refused: the old block went (once), the stage is empty, the event stays
+  const char* call = nullptr;
+  CHECK(acquire(s, 10000, &q, &call) == hipErrorOutOfMemory && !s.p && s.cap == 0 && s.ev && made("Wfh"));
+  CHECK(std::string(call) == "hipHostMalloc(&c->pin, std::max<size_t>(up_bytes, 8192), hipHostMallocDefault)");
+  CHECK(acquire(s, 100, &p) == hipSuccess && p && s.cap == 8192 && made("H")); // ... and usable again, with nothing to wait for
+  CHECK(send(s, dev, 100) == hipSuccess && made("CR"));
+  {
+    PinnedStage m(std::move(s)); // move-construct: the source lets go of block, event and the pending wait; no call
+    CHECK(m.p == p && m.cap == 8192 && m.ev && !s.p && !s.cap && !s.ev && made(""));
+    CHECK(acquire(m, 10, &q) == hipSuccess && q == p && made("W"));
+    PinnedStage other;
+    CHECK(acquire(other, 10, &q) == hipSuccess && q != p && made("HE"));
+    other = std::move(m); // move-assign over a live stage: what it held goes, once
+    CHECK(other.p == p && !m.p && !m.ev && made("fX"));
+    PinnedStage& self = other;
+    other = std::move(self);
+    CHECK(other.p == p && made(""));
+    s = std::move(other);
+    CHECK(s.p == p && made(""));
+  } // (m and other are empty: no call)
+  CHECK(made(""));
+  {
+    PinnedStage local, empty;
+    CHECK(acquire(local, 10, &q) == hipSuccess && made("HE"));
+    empty.release();
+  }
+  CHECK(made("fX") && pinned.size() == 1 && events.size() == 1); // destruction: one free, one event destroyed
+  CHECK(send(s, dev, 10) == hipSuccess && made("CR"));
+  c->end(); // (prv_destroy has drained the stream: no wait)
+  CHECK(made("fX") && pinned.empty() && events.empty());
+  frozen = true; // no runtime call follows the context's end
+  delete c;
+  frozen = false;
+  CHECK(made(""));
+}
+
 int main() { // (after each case: what its locals freed when they left their scope)
   scope_exit_and_moves();
   CHECK(made(""));
@@ -254,6 +375,8 @@ int main() { // (after each case: what its locals freed when they left their sco
   child_before_context();
   context_before_child();
   early_return();
+  pinned_stage();
+  CHECK(made("") && pinned.empty() && events.empty());
   CHECK(made("") && live.empty() && n_malloc == n_free && held() == 0);
   printf("ok %d\n", n_malloc);
   return 0;
