@@ -72,7 +72,8 @@ typedef struct prv_field_desc {
   int32_t base_res;
   int32_t finest_res;
   int32_t occ_res;
-  float density_bias; /* sigma = exp(out0 + density_bias) */
+  float density_bias; /* sigma = exp(out0 + density_bias); a sigma below 2^-126 (a logit under about -87.3) may be returned as 0,
+                         a logit above 88.72 gives +Inf (tests/test_gpu_field_regimes.py::test_field_outputs, `saturated`) */
   float table_amp;    /* synthetic generator only: table ~ U(-amp, amp) */
   float per_level_scale; /* 0: the levels grow geometrically from base_res to finest_res (double precision, nominal
                             integer resolutions hit exactly).  > 0: tiny-cuda-nn's recipe in float32 -- scale_l =

@@ -9,7 +9,10 @@ points: sub-sample offset, ray generation, box intersection, occupancy, field ev
   * `composite`: sum_i w_i v_i, w_i = alpha_i T_i, the colour composite's sum for any per-sample values;
   * `mean`: per pixel the sub-samples summed in order, then scaled by 1 / spp;
   * `assert_alpha_is_the_oracles`: the self-check of every reference built on these against the oracle's own render.
-fmaf is computed in float64 and rounded to float32; everything else is float32 arithmetic.
+fmaf is computed in float64 and rounded to float32; everything else is float32 arithmetic.  exp is the C library's expf, the function
+the oracle calls.  The oracle library does not export it: `lib.expf` resolves because dlsym on a library's handle also searches the
+library's dependencies, and libprv_oracle.so links libm.  numpy's float32 exp is a different one-ulp implementation, and where
+sigma dt is about 2^-25 (the empty space of a trained field) one ulp of exp(-sigma dt) is a whole alpha = 1 - exp(-sigma dt).
 """
 import ctypes as C
 
@@ -26,6 +29,14 @@ def fmaf(a, b, c):
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def expf(lib, x):
+    """the oracle's expf: libm's, a dependency of the oracle library"""
+    fn = lib.expf
+    if fn.restype is not C.c_float:
+        fn.restype, fn.argtypes = C.c_float, [C.c_float]
+    return f32(fn(float(x)))
 
 
 def forward_cos(cam, d):
@@ -77,7 +88,7 @@ def ray_samples(lib, field, o, d, step_mode, S, min_T):
         if not lib.orc_occupied(field.ptr, _p(p)):
             continue
         lib.orc_eval(field.ptr, _p(p), _p(d), C.byref(sigma), _p(rgb), _p(raw))
-        alpha = f32(1) - f32(np.exp(-f32(f32(sigma.value) * dt)))
+        alpha = f32(1) - expf(lib, -f32(f32(sigma.value) * dt))
         steps.append(i)
         ts.append(t)
         alphas.append(alpha)
